@@ -5,6 +5,7 @@ integration) issued through the C ABI exactly as MrBayes' src/mbbeagle.c issues 
 move dirties the whole tree (reference src/proposal.c:17682, src/mbbeagle.c:400-537).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--no-cpu-baseline] [--no-also] [--no-mcmc]
+                    [--dump-outputs DIR]
 
 Default workload: BASELINE configs[3]'s shape, synthetic DNA 1000 taxa x 50 000 patterns GTR+G4 (the shape the
 >=100x target is quoted on; it fits one GPU), one chain per GPU.  At N=1 the line also carries, under "also", the
@@ -249,9 +250,22 @@ def mpi_mcmc(nranks, emulate=False, full=False):
             "unit": "generations/s (all chains advance one generation)"}
 
 
-def measure(args, cfg, steps, warmup, rank, local_rank, world, dist, device, emulate, lib, want_cpu_baseline, verbose=True):
+def dump_outputs(dump_dir, cfg, lnl, site_lnl):
+    """--dump-outputs: what the caller of a full-tree evaluation receives from the engine -- the log-likelihood and the per-site
+    log-likelihoods behind it (beagleGetSiteLogLikelihoods) -- as <dump_dir>/<config>_lnL.npy and <config>_site_lnL.npy, float64.
+    The inputs are the committed golden case, so two builds run with the same arguments can be compared array by array.  Whole
+    arrays: 8 bytes per pattern, under 1 MB for all four workloads together."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, cfg + "_lnL.npy"), np.array([lnl], dtype=np.float64))
+    np.save(os.path.join(dump_dir, cfg + "_site_lnL.npy"), np.asarray(site_lnl, dtype=np.float64))
+
+
+def measure(args, cfg, steps, warmup, rank, local_rank, world, dist, device, emulate, lib, want_cpu_baseline, verbose=True,
+            dump_dir=None):
     """One workload: build the division from its golden case, check the lnL against the reference's, time `steps`
-    full-tree evaluations.  Returns the JSON object (rank 0) or None."""
+    full-tree evaluations.  Returns the JSON object (rank 0) or None.  With `dump_dir`, rank 0 also writes what the last
+    timed evaluation returned to its caller (see dump_outputs)."""
     import torch
     from mrbayes_amd import likelihood as lk
     from mrbayes_amd.division import division_from_golden, synthetic_division
@@ -321,6 +335,8 @@ def measure(args, cfg, steps, warmup, rank, local_rank, world, dist, device, emu
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     assert ablation or abs(lnl - lnl0) <= 1e-9 * abs(lnl0), (lnl, lnl0)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, cfg, lnl, bd.inst.get_site_log_likelihoods())
     bd.finalize()
     if rank != 0:
         return None
@@ -469,7 +485,7 @@ def arithmetic_report(args, cfg, o, device, lib):
     o["site_error_vs_fp64_engine"] = site_error(cfg, lib)
     if o["config"]["states"] >= 40 and os.path.exists(mbbuild.FP32_CHAIN_LIB):
         alt = bg.BeagleLibrary(mbbuild.FP32_CHAIN_LIB)
-        m = measure(args, cfg, max(args.steps, 200), args.warmup, 0, 0, 1, None, device, False, alt, False, verbose=False)
+        m = measure(args, cfg, args.steps, args.warmup, 0, 0, 1, None, device, False, alt, False, verbose=False)
         o["fp32_chain_variant"] = {
             "what": "the same sources with the contraction on v_mfma_f32_32x32x2_f32 (mrbayes_amd/libhmsbeagle_fp32chain.so, -DMBAMD_WG_BF_MIN=999)",
             "ms_per_step": m["ms_per_step"], "all_kernels_ms_per_step": m["roofline"]["all_kernels_ms_per_step"],
@@ -527,7 +543,7 @@ def box_write_rate(device):
         return None
 
 
-def double_precision_line(cfg, steps, lib):
+def double_precision_line(cfg, steps, warmup, lib):
     """The same workload through the double-precision engine (BEAGLE_FLAG_PRECISION_DOUBLE, `set beagleprecision=double`): lnL
     against the reference's double build, wall time of replayed full-tree evaluations.  A report beside the fp32 line."""
     from mrbayes_amd import likelihood as lk
@@ -544,7 +560,7 @@ def double_precision_line(cfg, steps, lib):
         assert abs(lnl0 - ref) <= 2e-6 + 2e-9 * abs(ref), (cfg, lnl0, ref)
         bd.AcceptMove(0)
         evals = [lk.record_evaluation(bd), lk.record_evaluation(bd)]
-        for i in range(5):
+        for i in range(warmup):
             evals[i & 1].run()
         t0 = time.perf_counter()
         for i in range(steps):
@@ -677,6 +693,9 @@ def main():
     ap.add_argument("--emulate", action="store_true",
                     help="TEST ONLY: run the control flow on the CPU (host-emulation engine, gloo, tiny workload); "
                          "the JSON line is marked invalid")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps of every workload, write what its last step returned (lnL, per-site lnL) "
+                         "as DIR/<config>_<name>.npy (float64): two builds run with the same arguments compare output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -732,7 +751,8 @@ def main():
         out = None
         if rank == 0:
             os.environ["MBAMD_SHARD"] = str(world)
-            out = measure(args, args.config, args.steps, args.warmup, 0, 0, 1, None, device, emulate, lib, False)
+            out = measure(args, args.config, args.steps, args.warmup, 0, 0, 1, None, device, emulate, lib, False,
+                          dump_dir=args.dump_outputs)
             out["n_gpus"] = world
             out["scaling"] = "strong"
             out["config"]["chains"] = 1
@@ -742,7 +762,7 @@ def main():
                 raise SystemExit("bench.py --shard: the %d shards of the instance sit on %s" % (world, out["instance_devices"]))
     else:
         out = measure(args, args.config, args.steps, args.warmup, rank, dev_index, world, dist, device, emulate, lib,
-                      not args.no_cpu_baseline)
+                      not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     if world > 1 and dist is not None:
         # which physical GPU every rank computes on (PCI bus id of its resource): a scaling line whose ranks share a device is
         # not a scaling line -- refuse it instead of reporting it
@@ -793,8 +813,8 @@ def main():
                 if other == args.config:
                     continue
                 try:
-                    out["also"].append(measure(args, other, max(args.steps, 200), args.warmup, 0, dev_index, 1, None, device,
-                                               False, lib, not args.no_cpu_baseline, verbose=False))
+                    out["also"].append(measure(args, other, args.steps, args.warmup, 0, dev_index, 1, None, device,
+                                               False, lib, not args.no_cpu_baseline, verbose=False, dump_dir=args.dump_outputs))
                     if other in ("c3", "c5") and not args.no_arith:
                         try:
                             arithmetic_report(args, other, out["also"][-1], device, lib)
@@ -814,7 +834,7 @@ def main():
             out["double_precision"] = []
             for other in (args.config, "c5"):
                 try:
-                    out["double_precision"].append(double_precision_line(other, 50, lib))
+                    out["double_precision"].append(double_precision_line(other, args.steps, args.warmup, lib))
                 except Exception as exc:
                     out["double_precision"].append({"workload": other, "error": repr(exc)[:300]})
         if not args.no_mcmc:

@@ -39,5 +39,15 @@ def build():
     return OUT
 
 
+def build_linked(*targets):
+    """Where the reference sources are (oracle/Makefile's REF), this build and the reference binaries `targets` linked to it
+    (e.g. "_ref/mb", "_ref/mb_emu"), made or brought up to date: a fresh checkout has no oracle/_ref binaries until something
+    makes them, and a test must not rely on another test having run first.  Elsewhere nothing is built: the caller checks for
+    the binaries and skips without them."""
+    if os.path.isdir("/root/reference/src"):
+        build()
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")] + list(targets), stdout=subprocess.DEVNULL)
+
+
 if __name__ == "__main__":
     print(build())

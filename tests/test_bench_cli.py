@@ -11,6 +11,14 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
         "vs_baseline", "dtype", "data", "config", "roofline"}
 
 
+def _mpi_on_shim():
+    """Whether the reference's MPI build on the emulated engine (what bench.py --emulate's mpi_mcmc runs) is there, built first
+    where the reference sources are."""
+    from tests.hostemu import build_emu
+    build_emu.build_linked("_ref/mb_emu_mpi", "_ref/mbamd_mpirun")
+    return os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mb_emu_mpi")) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mbamd_mpirun"))
+
+
 def _json_line(out):
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out[-2000:]
@@ -26,7 +34,28 @@ def test_single_process():
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
 
 
+def test_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's lnL and per-site lnLs as float64 .npy files; the same inputs every run (here two
+    runs with different step counts), the lnL the one the line reports, the site values summing to it."""
+    import numpy as np
+    got = []
+    for steps in (2, 5):
+        d = tmp_path / ("s%d" % steps)
+        res = subprocess.run([sys.executable, "bench.py", "--emulate", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = _json_line(res.stdout)
+        assert line["steps"] == steps
+        assert sorted(os.listdir(d)) == ["c4_lnL.npy", "c4_site_lnL.npy"]
+        lnl, site = np.load(d / "c4_lnL.npy"), np.load(d / "c4_site_lnL.npy")
+        assert lnl.dtype == site.dtype == np.float64 and lnl.shape == (1,) and site.shape == (line["config"]["patterns"],)
+        assert lnl[0] == line["config"]["lnL"] and abs(site.sum() - lnl[0]) <= 1e-9 * abs(lnl[0])
+        got.append((lnl, site))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
 def test_two_ranks():
+    mpi = _mpi_on_shim()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29671", "bench.py", "--gpus", "2",
@@ -45,7 +74,7 @@ def test_two_ranks():
     assert ps["host_synchronisations_per_step"] == 1        # the block sums meet on the device (mbamdReduceLogLikelihood + all-reduce)
     assert abs(ps["lnL"] - ps["lnL_reference_fp64"]) <= 2e-6 * abs(ps["lnL"])
     # the reference's own MPI build on the shim, two ranks (only where the reference binaries were built)
-    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mb_emu_mpi")) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mbamd_mpirun")):
+    if mpi:
         m = d["mpi_mcmc"]
         assert m["ranks"] == 2 and m["cases"][0]["generations_per_s"] > 0, m
         assert set(m["devices_of_rank"]) == {"0", "1"} and m["distinct_devices"] >= 1, m      # every rank's engine reported its device
@@ -87,6 +116,7 @@ def test_eight_ranks():
     """The launch the driver uses on an 8-GPU node, emulated (eight processes, gloo, host-emulation engine): chain-parallel replay,
     the pattern-sharded chain and -- where the reference binaries were built -- the MPI-build MCMC on eight ranks; the JSON the
     driver parses, a device per rank, the compact summary at the end of the line."""
+    mpi = _mpi_on_shim()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                           "--master-addr", "127.0.0.1", "--master-port", "29677", "bench.py", "--gpus", "8",
@@ -100,7 +130,7 @@ def test_eight_ranks():
     assert "error" not in ps, ps
     assert ps["n_gpus"] == 8 and ps["scaling"] == "strong" and abs(ps["lnL"] - ps["lnL_reference_fp64"]) <= 2e-6 * abs(ps["lnL"])
     assert "timed_out" not in d and list(d)[-1] == "summary" and "columns" in d["summary"]
-    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mb_emu_mpi")) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mbamd_mpirun")):
+    if mpi:
         m = d["mpi_mcmc"]
         assert "error" not in m, m
         assert m["ranks"] == 8 and m["cases"][0]["chains"] == 8 and m["cases"][0]["generations_per_s"] > 0, m
@@ -110,7 +140,7 @@ def test_eight_ranks():
 def test_secondary_modes_are_bounded():
     """A secondary mode that does not come back must not cost the scaling line: with a 20 ms budget (the emulated MPI run
     and the pattern-sharded chain taking longer) every rank leaves, rank 0 prints the primary measurement and says what it gave up on."""
-    if not (os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mb_emu_mpi")) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "mbamd_mpirun"))):
+    if not _mpi_on_shim():
         import pytest
         pytest.skip("needs the reference's MPI build on the shim (oracle/_ref)")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from mrbayes_amd import tree as mbtree
+from tests.hostemu import build_emu
 from tools import refrun
 
 REF = os.path.join(refrun.ROOT, "oracle", "_ref")
@@ -120,6 +121,7 @@ def _check(case, binary, marker):
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_restriction_and_doublet_on_emulated_engine(case):
+    build_emu.build_linked("_ref/mb_scalar", "_ref/mb_emu")
     _check(case, os.path.join(REF, "mb_emu"), "mbamd")
 
 

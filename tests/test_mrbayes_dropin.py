@@ -17,6 +17,7 @@ import pytest
 
 from mrbayes_amd import data as mbdata
 from mrbayes_amd import tree as mbtree
+from tests.hostemu import build_emu
 from tools import refrun
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,6 +96,7 @@ def _clock_nexus(beagle, ngen=1):
 
 @pytest.mark.parametrize("scaling", ["dynamic", "always"])
 def test_clock_tree_on_emulated_engine(scaling):
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     if not os.path.exists(refrun.REF_MB_EMU):
         pytest.skip("oracle/_ref/mb_emu not built (build container only)")
     native = refrun.initial_lnl(refrun.run_mb(refrun.REF_MB, _clock_nexus(None))[0])
@@ -135,6 +137,7 @@ def _ambiguous_nexus(beagle):
 
 
 def test_ambiguity_codes_on_emulated_engine():
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     if not os.path.exists(refrun.REF_MB_EMU):
         pytest.skip("oracle/_ref/mb_emu not built (build container only)")
     native = refrun.initial_lnl(refrun.run_mb(refrun.REF_MB, _ambiguous_nexus(None))[0])
@@ -215,6 +218,7 @@ def _check_multi_partition(binary):
 
 
 def test_multi_partition_v3_on_emulated_engine():
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu_v3")
     if not (os.path.exists(refrun.REF_MB_EMU_V3) and os.path.exists(refrun.REF_MB)):
         pytest.skip("oracle/_ref binaries not built (build container only)")
     _check_multi_partition(refrun.REF_MB_EMU_V3)
@@ -228,6 +232,7 @@ def test_multi_partition_v3_on_mi355x():
 
 
 def test_partitioned_analysis_on_emulated_engine():
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     if not (os.path.exists(refrun.REF_MB_EMU) and os.path.exists(refrun.REF_MB)):
         pytest.skip("oracle/_ref binaries not built (build container only)")
     _check_partitioned(refrun.REF_MB_EMU, "Impl Name : mbamd")
@@ -281,6 +286,7 @@ def _check_m3(binary, oracle):
 
 
 def test_general_state_models_on_emulated_engine(oracle):
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     if not os.path.exists(refrun.REF_MB_EMU):
         pytest.skip("oracle/_ref/mb_emu not built (build container only)")
     _check_wag(refrun.REF_MB_EMU)
@@ -308,6 +314,7 @@ def _tap_expected():
 def test_tap_style_run_on_emulated_engine():
     """Short version on the CPU (host-emulation engine): mixed nst + invgamma (pInvar goes through
     beagleGetSiteLogLikelihoods), 2 runs x 4 chains, swaps: completes and climbs to a sane likelihood."""
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     if not os.path.exists(refrun.REF_MB_EMU):
         pytest.skip("oracle/_ref/mb_emu not built (build container only)")
     from tools import gen_tap_fixture as tap

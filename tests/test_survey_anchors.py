@@ -20,6 +20,7 @@ import pytest
 
 from mrbayes_amd import data as mbdata
 from mrbayes_amd.model import AA_ORDER, NUC, sense_codons
+from tests.hostemu import build_emu
 from tools import refrun
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,12 +166,14 @@ def _check_gen2000(binary, marker):
 
 @pytest.mark.parametrize("key", sorted(CASES))
 def test_anchor_start_states_native_and_emulated(key):
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     _need(refrun.REF_MB)
     _need(refrun.REF_MB_EMU)
     _check_start(key, refrun.REF_MB_EMU, "mbamd")
 
 
 def test_anchor_primates_generation_2000_native_and_emulated():
+    build_emu.build_linked("_ref/mb", "_ref/mb_emu")
     _need(refrun.REF_MB)
     _need(refrun.REF_MB_EMU)
     _check_gen2000(refrun.REF_MB_EMU, "mbamd")
