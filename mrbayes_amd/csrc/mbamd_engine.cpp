@@ -27,6 +27,7 @@
 #include "libhmsbeagle/mbamd_reports.h"
 #include "mbamd_walk4_host.h"
 #include "mbamd_kernels_mfma.h"
+#include "mbamd_switches.h"
 
 #include <chrono>
 
@@ -44,10 +45,10 @@ static ApiStats g_stats[] = {{"beagleUpdateTransitionMatrices"}, {"beagleUpdateP
                              {"  (launching the deferred work)"}, {"  (waiting for the device)"},
                              {"  (parsimony: compiling the queued passes)"}, {"  (parsimony: waiting for the device)"}};
 enum { ST_MATRICES = 0, ST_PARTIALS, ST_LNL, ST_SCALE, ST_SET, ST_SITE, ST_PLAN, ST_PARS_PASS, ST_PARS_SCORE, ST_FLUSH, ST_WAIT, ST_PARS_COMPILE, ST_PARS_WAIT };
-static const bool g_statsOn = std::getenv("MBAMD_STATS") != nullptr;
+// the process-level diagnostics (MBAMD_STATS, MBAMD_API_TRACE, MBAMD_VERBOSE in fail()): read once, when the library loads
+static const Switches g_loadSwitches = read_switches();
 // MBAMD_API_TRACE=1: one stderr line per C-ABI call (integration debugging: what does the client really send?)
-static const bool g_apiTrace = std::getenv("MBAMD_API_TRACE") != nullptr;
-#define API_TRACE(...) do { if (g_apiTrace) { std::fprintf(stderr, "[mbamd api] " __VA_ARGS__); std::fputc('\n', stderr); } } while (0)
+#define API_TRACE(...) do { if (g_loadSwitches.apiTrace) { std::fprintf(stderr, "[mbamd api] " __VA_ARGS__); std::fputc('\n', stderr); } } while (0)
 static std::string trace_ints(const int* v, int n) {
     std::string r = "[";
     for (int i = 0; v && i < n; ++i) r += (i ? "," : "") + std::to_string(v[i]);
@@ -62,11 +63,11 @@ static std::string trace_doubles(const double* v, int n) {
 struct StatTimer {
     int id;
     std::chrono::steady_clock::time_point t0;
-    explicit StatTimer(int i) : id(i) { if (g_statsOn) t0 = std::chrono::steady_clock::now(); }
+    explicit StatTimer(int i) : id(i) { if (g_loadSwitches.stats) t0 = std::chrono::steady_clock::now(); }
     bool stopped = false;
     void stop()                                      // (a span that ends before its scope does)
     {
-        if (!g_statsOn || stopped) return;
+        if (!g_loadSwitches.stats || stopped) return;
         stopped = true;
         g_stats[id].calls++;
         g_stats[id].seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -79,7 +80,7 @@ static thread_local std::string g_last_error;
 static int fail(int code, const char* what, const char* detail = "")
 {
     g_last_error = std::string(what) + (detail[0] ? ": " : "") + detail;
-    if (std::getenv("MBAMD_VERBOSE")) std::fprintf(stderr, "[mbamd] error %d: %s\n", code, g_last_error.c_str());
+    if (g_loadSwitches.verbose) std::fprintf(stderr, "[mbamd] error %d: %s\n", code, g_last_error.c_str());
     return code;
 }
 
@@ -206,7 +207,6 @@ struct Instance {
     bool noWalkG = false;            // the arenas of that path did not fit: level kernels with buffers allocated on first use
     bool arena() const { return s4 || wg; }   // buffers are slices of arenas, exponents are per (pattern, category)
     bool mfma = false;               // general-state path on the matrix cores (mbamd_kernels_mfma.h)
-    bool mfmaWhole = false;          // MBAMD_MFMA_WHOLE: one wave per (operation, 32 patterns) instead of per factor tile
     int walkWaves = 1, lastWalkSteps = 0;   // (kernel trace bookkeeping of the serial MFMA kernels, tools/trace_*.py)
     // ---- 4-state tree-walk path (mbamd_walk4.h / mbamd_walk4_host.h) -------------------------------------------
     Walk4Builder w4;                 // launch geometry limits + the program compiler
@@ -242,8 +242,6 @@ struct Instance {
     int32_t* heldPathCum = nullptr;
     bool heldPathFresh = false;
     int heldPathDst = -1;                        // the partials buffer the path's last operation writes
-    bool noFusePath = false;                     // MBAMD_NO_FUSE_PATH: never hold a path
-    bool noForkPath = false;                     // MBAMD_NO_FORK_PATH: paths that join are compiled for k_walk4_t (A/B)
     int runHeldPath();
     int integratePath4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx);
     int updatePartialsG(const BeagleOperation* ops, int n, int cumIdx);
@@ -251,8 +249,6 @@ struct Instance {
     int runWalkG(const Plan& plan);
     bool buildPath4(Plan& plan, const BeagleOperation* ops, int n);
     bool buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl);
-    bool noPathG = false;                        // MBAMD_NO_PATHG: root-ward paths of the general-state walk through k_walkg
-    bool noPath4 = false;                        // MBAMD_NO_PATH4: root-ward paths on k_walk4_t too
     void postResultFlag();
     bool scaleOpsIndependentOfPending(const int* idx, int n, int cumIdx) const;
     uint64_t launchClock = 0, syncedClock = 0;   // launches issued / launches known complete (last stream synchronisation)
@@ -284,7 +280,6 @@ struct Instance {
     double* h_site = nullptr;
     double* h_site_dev = nullptr;
     bool siteToHost = false, siteOnHost = false;   // mode / where the latest evaluation put its values
-    bool noSiteHost = false;                       // MBAMD_NO_SITE_HOST: always copy from device memory (comparison switch)
     int nblocks = 0;                  // partial sums of the weighted site log-likelihoods (one per integration workgroup)
     std::vector<RatesArg> rateSets;   // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
@@ -310,8 +305,8 @@ struct Instance {
     // bit pattern no sum can have; fetchResult then waits for every block sum to differ from it -- no gap + stream write behind the
     // kernel (8.6 us of every evaluation, profiles/r06_walk61.txt), and no fence in the kernel (each sum is one 8-byte store to
     // host-coherent memory).  Armed only when nothing else can still write h_sums (no unfetched result) and not in deferred mode
-    // (mbamdReduceLogLikelihood reads them on the device).  MBAMD_NO_SUM_POLL=1: the stream's flag only (A/B).
-    bool pollSums = false, sumsArmed = false, flagWritten = false;
+    // (mbamdReduceLogLikelihood reads them on the device).
+    bool sumsArmed = false, flagWritten = false;
     static constexpr uint64_t kSumSentinel = 0x7FF4DEADBEEF0001ull;      // a signalling NaN with a payload no arithmetic produces
     void armSums();
     unsigned char* stage_dev = nullptr;   // the device-side address of the staging ring
@@ -400,7 +395,7 @@ struct Instance {
         // (round 6: small transfers -- eigen-systems, frequencies, weights, compiled programs -- go through the pinned ring and a copy
         //  kernel of ours: hipMemcpyAsync costs the host ~10 us a call and its blit kernel left the walk behind it 30 % slower,
         //  profiles/r06_ring_copy.txt)
-        if (!noRingCopy && bytes <= ((size_t) 256 << 10) && bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) return ringCopy(dst, src, bytes);
+        if (bytes <= ((size_t) 256 << 10) && bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) return ringCopy(dst, src, bytes);
         size_t need = (bytes + 63) & ~(size_t) 63;
         if (stageOff + need > stageCap) {
             HIP_TRY(hipStreamSynchronize(stream));
@@ -462,7 +457,7 @@ struct Instance {
     float* matrixPtr(int idx) const { return matrices + (size_t) idx * matrixFloats; }
 
     int create(int tipCount_, int partialsBufferCount, int compactBufferCount, int stateCount, int patternCount,
-               int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev);
+               int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev, const Switches& switches);
     void destroy();
 
     int configureWalk();
@@ -499,16 +494,8 @@ struct Instance {
     std::vector<MatrixJob> pendingJobs;          // queued beagleUpdateTransitionMatrices work
     std::vector<char> pendingMatrixOut;          // matrix buffers the queued jobs write
     int submit(Plan* plan, int cumIdx, int32_t* cumPtr);
-    bool noDefer = false;            // MBAMD_NO_DEFER: run every list at once
-    bool noInlineJobs = false;       // MBAMD_NO_INLINE_JOBS: a branch move's matrix jobs through the pinned ring too (A/B)
-    bool noRingCopy = false;         // MBAMD_NO_RING_COPY: a walk program reaches its device buffer by hipMemcpyAsync (A/B)
-    bool eagerMatrices = false;      // four states (one call per evaluation): beagleUpdateTransitionMatrices launches the matrix kernel itself -- it runs while
-                                     // MrBayes assembles the operation list (+2 % on both chains, profiles/r06_scale_read.txt); MBAMD_LAZY_MATRICES=1: queued as for the other models
-    bool noInlinePrograms = false;   // MBAMD_NO_INLINE_PROGRAMS: every walk program through a device buffer
-    bool envVerbose = false, envTrace = false;   // MBAMD_VERBOSE, MBAMD_WALK_TRACE (read once)
-    bool noSpine = false;            // MBAMD_NO_SPINE: serial launches use the plain (not software-pipelined) kernel
-    int spineWidth = 1;              // MBAMD_SPINE_WIDTH: trailing levels of at most this many operations join the serial launch
-    int serialRatio = 4;             // MBAMD_MFMA_SERIAL: lists with <= ratio * levels operations run as ONE serial launch (0 = never)
+    Switches sw;                     // the environment switches, read when the instance was created (mbamd_switches.h)
+    int serialRatio = 4;             // lists with <= ratio * levels operations run as ONE serial launch (0 = never; MBAMD_MFMA_SERIAL)
     bool independentOfPending(const Plan& plan, int cumIdx);
     int accumulate(const int* idx, int n, int cumIdx, int sign, bool fresh = false);   // fresh: cumIdx was reset just before -- store, do not add
     int integrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
@@ -526,14 +513,15 @@ static std::vector<Instance*> g_instances;
 // A new engine for one device.  The 20/61-state tree walk allocates every buffer up front (arenas); if that does not fit,
 // the same instance is set up once more on the level kernels, which allocate a buffer when it is first written.
 static int new_engine(Instance*& out, long flags, int tipCount, int partialsBufferCount, int compactBufferCount, int stateCount,
-                      int patternCount, int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev)
+                      int patternCount, int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev,
+                      const Switches& sw)
 {
     for (int attempt = 0; attempt < 2; ++attempt) {
         Instance* c = new Instance();
         c->flags = flags;
         c->noWalkG = attempt == 1;
         const int rc = c->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                                 matrixBufferCount, categoryCount, scaleBufferCount, dev);
+                                 matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
         if (rc == BEAGLE_SUCCESS) { out = c; return rc; }
         const bool retry = rc == BEAGLE_ERROR_OUT_OF_MEMORY && c->wg && attempt == 0;
         c->destroy();
@@ -554,8 +542,9 @@ static Instance* lookup(int id)
 // ---------------------------------------------------------------------------------------------
 int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCount, int stateCount,
                      int patternCount, int eigenBufferCount, int matrixBufferCount, int categoryCount,
-                     int scaleBufferCount, int dev)
+                     int scaleBufferCount, int dev, const Switches& switches)
 {
+    sw = switches;
     device = dev;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -568,14 +557,13 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
     nEigen = eigenBufferCount;
     nMatrices = matrixBufferCount;
     nScale = scaleBufferCount;
-    const bool forceGeneric = std::getenv("MBAMD_FORCE_GENERIC") != nullptr;
     // the 4-state tree walk addresses buffers with 32-bit byte offsets inside a (block, category) column set (Walk4Entry)
-    s4 = (S == 4 && !forceGeneric && (size_t) nBuffers * K * 1024 < ((size_t) 1 << 32) && (size_t) nMatrices * K * 64 < ((size_t) 1 << 32) &&
+    s4 = (S == 4 && !sw.forceGeneric && (size_t) nBuffers * K * 1024 < ((size_t) 1 << 32) && (size_t) nMatrices * K * 64 < ((size_t) 1 << 32) &&
           (size_t) (nScale + MBAMD_W4_SCRATCH_ROWS) * K * 64 < ((size_t) 1 << 32));
     // 20 / 61 states: the tree-walk kernel on the matrix cores (MBAMD_NO_WALKG=1: the level kernels of mbamd_kernels_mfma.h)
     {
         const size_t tb = wg_block_bytes(S), mf = (size_t) K * 64 * 64 + (size_t) K * wg_table_floats(S);
-        wg = !s4 && wg_compiled(S) && K <= 16 && !forceGeneric && !noWalkG && std::getenv("MBAMD_NO_WALKG") == nullptr &&
+        wg = !s4 && wg_compiled(S) && K <= 16 && !sw.forceGeneric && !noWalkG && !sw.noWalkG &&
              (size_t) (nBuffers + 1) * K * tb < ((size_t) 1 << 32) && (size_t) nMatrices * mf * 4 < ((size_t) 1 << 32) &&
              (size_t) (nScale + MBAMD_WG_SCRATCH_ROWS) * K * 64 < ((size_t) 1 << 32) && (size_t) nBuffers * MBAMD_WG_TW < ((size_t) 1 << 32);
     }
@@ -588,33 +576,16 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
     else SP = 64;
     NT = (S + 31) / 32;
     T = (S + 1) / 2;
-    mfma = !s4 && !wg && S >= 5 && S <= 64 && ((NT == 1 && K <= 4) || (NT == 2 && K <= 2)) &&
-           std::getenv("MBAMD_NO_MFMA") == nullptr;
+    mfma = !s4 && !wg && S >= 5 && S <= 64 && ((NT == 1 && K <= 4) || (NT == 2 && K <= 2)) && !sw.noMfma;
     if (mfma) SP = 32 * NT;          // transposed matrices padded to the MFMA tile height
-    mfmaWhole = std::getenv("MBAMD_MFMA_WHOLE") != nullptr;
-    noDefer = std::getenv("MBAMD_NO_DEFER") != nullptr;
-    noInlineJobs = std::getenv("MBAMD_NO_INLINE_JOBS") != nullptr;
-    noRingCopy = std::getenv("MBAMD_NO_RING_COPY") != nullptr;
-    eagerMatrices = s4 && std::getenv("MBAMD_LAZY_MATRICES") == nullptr;
-    noInlinePrograms = std::getenv("MBAMD_NO_INLINE_PROGRAMS") != nullptr;
-    noPath4 = std::getenv("MBAMD_NO_PATH4") != nullptr;
-    noFusePath = std::getenv("MBAMD_NO_FUSE_PATH") != nullptr;
-    noForkPath = std::getenv("MBAMD_NO_FORK_PATH") != nullptr;
-    noPathG = std::getenv("MBAMD_NO_PATHG") != nullptr;
-    if (const char* e = std::getenv("MBAMD_MFMA_SERIAL")) serialRatio = std::max(0, std::atoi(e));
-    noSpine = std::getenv("MBAMD_NO_SPINE") != nullptr;
-    if (const char* e = std::getenv("MBAMD_SPINE_WIDTH")) spineWidth = std::max(1, std::atoi(e));
+    if (sw.mfmaSerial) serialRatio = std::max(0, *sw.mfmaSerial);
     // serial / spine kernels exist for these shapes only (other category counts: level launches throughout)
     if (!((NT == 1 && (K == 1 || K == 2 || K == 4)) || (NT == 2 && (K == 1 || K == 2)))) serialRatio = 0;
-    envVerbose = std::getenv("MBAMD_VERBOSE") != nullptr;
-    envTrace = std::getenv("MBAMD_WALK_TRACE") != nullptr;
-    if (std::getenv("MBAMD_REPORT_DEVICE")) {    // one line per instance: which physical GPU (multi-rank drivers collect them: bench.py mpi_mcmc)
+    if (sw.reportDevice) {    // one line per instance: which physical GPU (multi-rank drivers collect them: bench.py mpi_mcmc)
         char bus[64] = "?";
         if (hipDeviceGetPCIBusId(bus, (int) sizeof bus, device) != hipSuccess) (void) hipGetLastError();
-        const char* mr = std::getenv("MBAMD_MPI_RANK");
-        std::fprintf(stderr, "[mbamd] instance on device %d pci %s mpi-rank %s\n", device, bus, mr ? mr : "-");
+        std::fprintf(stderr, "[mbamd] instance on device %d pci %s mpi-rank %s\n", device, bus, sw.mpiRank.empty() ? "-" : sw.mpiRank.c_str());
     }
-    noSiteHost = std::getenv("MBAMD_NO_SITE_HOST") != nullptr;
     partialsFloats = s4 ? (size_t) K * Ppad * 4 : (size_t) K * S * Ppad;
     matrixFloats = (size_t) K * SP * SP + (mfma ? (size_t) K * NT * T * 64 : 0);
     if (wg) {
@@ -651,7 +622,7 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
         HIP_TRY(hipMemsetAsync(arenaExp, 0, eBytes, stream));
         wideScale.assign(scale.size(), nullptr);
         scaleState.assign(scale.size(), 0);
-        if (std::getenv("MBAMD_VERBOSE"))
+        if (sw.verbose)
             std::fprintf(stderr, "[mbamd] arenas: partials %p +%zu, tips %p +%zu, exponents %p +%zu\n",
                          (void*) arenaPartials, pBytes, (void*) arenaTips, tBytes, (void*) arenaExp, eBytes);
         for (int i = 0; i < nBuffers; ++i) partials[i] = arenaPartials + (size_t) i * nb * K * 64 * 4;
@@ -676,7 +647,7 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
         HIP_TRY(hipMemsetAsync(arenaExp, 0, eBytes, stream));
         wideScale.assign(scale.size(), nullptr);
         scaleState.assign(scale.size(), 0);
-        if (envVerbose)
+        if (sw.verbose)
             std::fprintf(stderr, "[mbamd] arenas: partials +%zu, tips +%zu, exponents +%zu bytes\n", pBytes, tBytes, eBytes);
         for (int i = 0; i < nBuffers; ++i) partials[i] = arenaPartials + (size_t) i * K * tb / 4;
     }
@@ -699,11 +670,10 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
     if (wg) nblocks = Ppad / MBAMD_INTEGRATE_WG_PATTERNS;      // the tree-walk layout's integration kernel, whatever the state count
     HIP_TRY(hipHostMalloc(&h_sums, (size_t) nblocks * sizeof(double), hipHostMallocDefault));
     HIP_TRY(hipHostGetDevicePointer((void**) &h_sums_dev, h_sums, 0));
-    if (std::getenv("MBAMD_NO_POLL") == nullptr) {
+    if (!sw.noPoll) {
         if (hipHostMalloc((void**) &h_flag, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer((void**) &h_flag_dev, h_flag, 0) == hipSuccess) {
             *h_flag = 0;
             pollResult = true;
-            pollSums = std::getenv("MBAMD_NO_SUM_POLL") == nullptr;
         } else {
             (void) hipGetLastError();
         }
@@ -777,7 +747,7 @@ int Instance::configureWalk()
         MBAMD_WG_DISPATCH(S, raise_walkg_lds, maxLds);
         wgGeometry(1, w4.maxW, w4.maxSlots);
         w4.maxSlots1 = w4.maxSlots;
-        if (!std::getenv("MBAMD_WALK_WAVES") && !std::getenv("MBAMD_MAX_LDS_SLOTS")) {   // a single-wave program may use the LDS of the whole workgroup
+        if (!sw.walkWaves && !sw.maxLdsSlots) {   // a single-wave program may use the LDS of the whole workgroup
             const long wgsG = (long) (Ppad / MBAMD_WG_TW) * K;
             const int perCUG = (int) std::max(1L, (wgsG + numCU - 1) / numCU);
             w4.maxSlots1 = std::max(w4.maxSlots, std::min(24, (int) (((160 * 1024) / std::min(perCUG, 32) - 64 - MBAMD_WG_STAGE) / (int) slotBytes)));
@@ -785,8 +755,8 @@ int Instance::configureWalk()
         w4.memSlots = false;
         w4.leadNops = MBAMD_WG_LEAD; w4.unroll = 3; w4.tailNops = MBAMD_WG_TAIL;
         w4.prefetchDistance = 0;
-        if (const char* e = std::getenv("MBAMD_WALK_SMALL_PHASE")) w4.smallPhase = std::max(1, std::atoi(e));
-        if (envVerbose) std::fprintf(stderr, "[mbamd] tree walk (%d states): %ld workgroups, up to %d waves x %d slots of %u bytes\n",
+        if (sw.walkSmallPhase) w4.smallPhase = std::max(1, *sw.walkSmallPhase);
+        if (sw.verbose) std::fprintf(stderr, "[mbamd] tree walk (%d states): %ld workgroups, up to %d waves x %d slots of %u bytes\n",
                                      S, (long) (Ppad / MBAMD_WG_TW) * K, w4.maxW, w4.maxSlots, slotBytes);
         return BEAGLE_SUCCESS;
     }
@@ -800,18 +770,17 @@ int Instance::configureWalk()
     //  -- 15 waves per CU, 190 entries per wave instead of 264 -- the evaluation takes 0.158-0.164 ms instead of 0.181; four: 0.192.)
     int W = (int) std::max(1L, std::min((long) MBAMD_W4_MAXW, (14L * numCU + wgs / 2) / wgs));
     while (W > 1 && slotsFor(W) < 7) --W;
-    if (const char* e = std::getenv("MBAMD_WALK_WAVES")) W = std::max(1, std::min(MBAMD_W4_MAXW, std::atoi(e)));
+    if (sw.walkWaves) W = std::max(1, std::min(MBAMD_W4_MAXW, *sw.walkWaves));
     int slots = std::max(3, std::min(48, slotsFor(W)));
-    if (const char* e = std::getenv("MBAMD_MAX_LDS_SLOTS")) slots = std::max(3, std::min(150 / W, std::atoi(e)));
+    if (sw.maxLdsSlots) slots = std::max(3, std::min(150 / W, *sw.maxLdsSlots));
     w4.maxW = W;
     w4.maxSlots = slots;
-    w4.maxSlots1 = std::max(slots, std::min(40, slotsFor(1)));
-    if (std::getenv("MBAMD_MAX_LDS_SLOTS")) w4.maxSlots1 = slots;
-    if (const char* e = std::getenv("MBAMD_WALK_PREFETCH")) w4.prefetchDistance = std::max(0, std::atoi(e));
-    w4.forward = std::getenv("MBAMD_WALK_NO_FORWARD") == nullptr;
-    w4.safeWaits = std::getenv("MBAMD_WALK_SAFE") != nullptr;
-    if (const char* e = std::getenv("MBAMD_WALK_SMALL_PHASE")) w4.smallPhase = std::max(1, std::atoi(e));
-    if (envVerbose) std::fprintf(stderr, "[mbamd] tree walk: %ld workgroups (%d per CU), up to %d waves x %d slots\n", wgs, perCU, W, slots);
+    w4.maxSlots1 = sw.maxLdsSlots ? slots : std::max(slots, std::min(40, slotsFor(1)));
+    if (sw.walkPrefetch) w4.prefetchDistance = std::max(0, *sw.walkPrefetch);
+    w4.forward = true;
+    w4.safeWaits = sw.walkSafe;
+    if (sw.walkSmallPhase) w4.smallPhase = std::max(1, *sw.walkSmallPhase);
+    if (sw.verbose) std::fprintf(stderr, "[mbamd] tree walk: %ld workgroups (%d per CU), up to %d waves x %d slots\n", wgs, perCU, W, slots);
     return BEAGLE_SUCCESS;
 }
 
@@ -833,9 +802,9 @@ void Instance::wgGeometry(int lists, int& W, int& slots) const
     W = 1;
     while (W * 2 <= want) W *= 2;
     while (W > 1 && slotsFor(W) < 4) W /= 2;
-    if (const char* e = std::getenv("MBAMD_WALK_WAVES")) W = std::max(1, std::min(maxW, std::atoi(e)));
+    if (sw.walkWaves) W = std::max(1, std::min(maxW, *sw.walkWaves));
     slots = std::max(3, std::min(24, slotsFor(W)));
-    if (const char* e = std::getenv("MBAMD_MAX_LDS_SLOTS")) slots = std::max(1, std::min((160 * 1024 / W - MBAMD_WG_STAGE) / slotBytes, std::atoi(e)));
+    if (sw.maxLdsSlots) slots = std::max(1, std::min((160 * 1024 / W - MBAMD_WG_STAGE) / slotBytes, *sw.maxLdsSlots));
 }
 
 // 4-state path: one tip's state masks (bit i = state i compatible) -> four 64-bit bitplanes per pattern block
@@ -987,7 +956,7 @@ int Instance::setRateMatrices(int first, int count, const double* q, const doubl
         ldsRaised[device] = 1;
     }
     // (beyond 32 states a step's 2 x 2 blocks are spread over 1 024 threads: four waves per SIMD hide the LDS round trips of a Jacobi step)
-    if (S > 32 && std::getenv("MBAMD_EIGEN_256") == nullptr)
+    if (S > 32 && !sw.eigen256)
         MBAMD_LAUNCH_BARRIER(k_eigen_reversible<32>, (unsigned) count, 1024, eigen_lds_doubles(S) * sizeof(double), stream, djobs, S, 30);
     else
         MBAMD_LAUNCH_BARRIER(k_eigen_reversible<8>, (unsigned) count, 256, eigen_lds_doubles(S) * sizeof(double), stream, djobs, S, 30);
@@ -1056,7 +1025,9 @@ int Instance::updateMatrices(int eigenIndex, const int* probIdx, const double* l
         pendingJobs.push_back(j);
         pendingMatrixOut[probIdx[i]] = 1;
     }
-    if (eagerMatrices) return flushMatrices();
+    // four states (one call per evaluation): the matrix kernel is launched here, so that it runs while MrBayes assembles the
+    // operation list (+2 % on both chains, profiles/r06_scale_read.txt)
+    if (s4) return flushMatrices();
     return BEAGLE_SUCCESS;
 }
 
@@ -1066,7 +1037,7 @@ int Instance::flushMatrices()
     const RatesArg rates = rateSets[pendingRateSet];
     const int count = (int) pendingJobs.size();
     { int src = spanBegin(); if (src) return src; }
-    if (s4 && count <= MBAMD_S4_INLINE_JOBS && count * K <= 64 && !noInlineJobs) {
+    if (s4 && count <= MBAMD_S4_INLINE_JOBS && count * K <= 64) {
         // a branch move's one or two matrices: the jobs in the kernel arguments (mbamd_kernels.h)
         MatrixJobs4 ja;
         std::memset(&ja, 0, sizeof ja);
@@ -1183,7 +1154,7 @@ int Instance::updatePartials(const BeagleOperation* ops, int n, int cumIdx)
             return submit(pl, cumIdx, cumPtr);
         }
     planMisses++;
-    if (!mfma || mfmaWhole || noDefer || pending.empty()) {
+    if (!mfma || sw.mfmaWhole || sw.noDefer || pending.empty()) {
         // launch the queued transition-matrix jobs now: the kernel runs while the host compiles the list
         int mrc = flushMatrices();
         if (mrc) return mrc;
@@ -1286,7 +1257,7 @@ int Instance::submit(Plan* plan, int cumIdx, int32_t* cumPtr)
         int mrc = flushMatrices();
         if (mrc) return mrc;
     }
-    if (!s4 && mfma && !mfmaWhole && !noDefer) {
+    if (!s4 && mfma && !sw.mfmaWhole && !sw.noDefer) {
         if ((int) pending.size() >= MBAMD_MAX_TABLES || !independentOfPending(*plan, cumIdx)) {
             int rc = flushPending();
             if (rc) return rc;
@@ -1593,7 +1564,7 @@ int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumIdx)
     listsTotal++;
     if (plan->path) { listsPath++; if (plan->forked) forkedPaths++; }
     else { listsWalked++; opsWalked += n; }
-    if (plan->path && !noFusePath && K <= 8 && plan->inlineProg.size() <= MBAMD_W4_INLINE) {
+    if (plan->path && !sw.noFusePath && K <= 8 && plan->inlineProg.size() <= MBAMD_W4_INLINE) {
         // hold it: the next call decides (runHeldPath / integratePath4)
         heldPath = plan;
         heldPaths++;
@@ -1630,7 +1601,7 @@ int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int
         key.clear();
         key.reserve(seg.size() * 3 + 4);
         key.push_back((int) seg.size()); key.push_back(w4.maxW); key.push_back(w4.maxSlots + 256 * w4.maxSlots1);
-        key.push_back(w4.prefetchDistance * 2 + (w4.safeWaits ? 1 : 0) + (w4.forward ? 512 : 0));
+        key.push_back(w4.prefetchDistance * 2 + (w4.safeWaits ? 1 : 0));
         {
             std::vector<int>& writer = w4writer;          // buffer -> operation of this segment that writes it (-1 outside this block)
             for (size_t o = 0; o < seg.size(); ++o) {
@@ -1808,12 +1779,12 @@ int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int
     }
     int rc = flushSegment();
     if (rc) return rc;
-    if (envVerbose)
+    if (sw.verbose)
         std::fprintf(stderr, "[mbamd] walk plan: %d ops, %zu segment(s), W=%d, %d entries/wave, %d slots/wave, %d phases, %d reloads, %d external children\n",
                      n, plan.segments.size(), lastWalkW, lastWalkEntries, lastWalkSlots, phases, reloads, externals);
     // a short program goes out with the launch itself (k_walk4_t<Walk4ArgsInline>, k_walkg<..., WalkGArgsInline>)
     plan.inlineProg.clear();
-    if (!noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE) {
+    if (!sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE) {
         plan.inlineProg = w4table;
         return BEAGLE_SUCCESS;
     }
@@ -1858,7 +1829,7 @@ int Instance::ringCopy(void* dst, const void* src, size_t bytes)
 // (false) is compiled by buildWalk.
 bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
 {
-    if (noPath4 || n < 1 || n > MBAMD_W4_INLINE) return false;
+    if (sw.noPath4 || n < 1 || n > MBAMD_W4_INLINE) return false;
     const int scratchScale = (int) scale.size();
     const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
     std::vector<Walk4Entry>& prog = plan.inlineProg;
@@ -1880,7 +1851,7 @@ bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
         bool join = false;
         if (start) {
             if (i > 0) {
-                if (noForkPath || saved >= 0) return false;                // (two results waiting: not this kernel's shape)
+                if (sw.noForkPath || saved >= 0) return false;                // (two results waiting: not this kernel's shape)
                 saved = prev;
                 prog[(size_t) armStart].ctl |= (uint32_t) (i - armStart) << 16;
                 armStart = i;
@@ -1944,7 +1915,7 @@ bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
 static inline bool pathg_compiled(int S) { return S == 20 || (S >= 60 && S <= 63); }
 bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl)
 {
-    if (noPathG || !pathg_compiled(S) || nl < 1 || nl > MBAMD_WG_MAXLISTS || n < nl || n % nl != 0) return false;
+    if (sw.noPathG || !pathg_compiled(S) || nl < 1 || nl > MBAMD_WG_MAXLISTS || n < nl || n % nl != 0) return false;
     const int L = n / nl;
     if (L < 2 || (size_t) n > (size_t) MBAMD_W4_INLINE) return false;      // (a single operation gains nothing; the program travels in the kernel arguments)
     for (int q = 0; q < nl; ++q) if (starts[(size_t) q] != q * L) return false;
@@ -2003,7 +1974,7 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
             e.ctl = flags | (mode << 8) | ((uint32_t) q << 10);
         }
     }
-    if (envVerbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths (k_pathg)\n", nl, L);
+    if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths (k_pathg)\n", nl, L);
     plan.pathG = true;
     plan.lists = nl;
     plan.segments.clear();
@@ -2095,7 +2066,7 @@ int Instance::updatePartialsG(const BeagleOperation* ops, int n, int cumIdx)
     wgListStart.push_back((int) wgOps.size());
     wgListCum.push_back(cumIdx);
     wgOps.insert(wgOps.end(), ops, ops + n);
-    if (noDefer) return flushPending();
+    if (sw.noDefer) return flushPending();
     return BEAGLE_SUCCESS;
 }
 
@@ -2237,7 +2208,7 @@ int Instance::flushWalkG()
             for (int o = 0; o < n && independent; ++o)                  // a buffer one list writes must not be read by another
                 for (int c : {ops[o].child1Partials, ops[o].child2Partials})
                     if (c >= 0 && c < nBuffers && wr[c] >= 0 && wr[c] != listOf[o]) independent = false;
-            if (envVerbose) std::fprintf(stderr, "[mbamd] %d queued lists, %d operations: %s\n", nl, n, independent ? "independent" : "one forest");
+            if (sw.verbose) std::fprintf(stderr, "[mbamd] %d queued lists, %d operations: %s\n", nl, n, independent ? "independent" : "one forest");
         }
         int rc;
         {
@@ -2264,7 +2235,7 @@ int Instance::flushWalkG()
                     plan->lists = nl;
                     done = true;
                     // (several independent lists = several segments, one launch: short enough, they travel in its arguments too)
-                    if (!noInlinePrograms && w4table.size() <= (size_t) MBAMD_W4_INLINE) plan->inlineProg = w4table;
+                    if (!sw.noInlinePrograms && w4table.size() <= (size_t) MBAMD_W4_INLINE) plan->inlineProg = w4table;
                 }
             }
             if (!done) rc = buildWalk(*plan, ops.data(), n, listOf.data(), false);
@@ -2291,16 +2262,6 @@ static void launch_walkg_t(Instance& in, const WalkGArgs& a, int W, int nslots, 
         return;
     }
     auto kern = k_walkg<SC_, WMAX_, CH_, DEPTH_>;
-#if defined(MBAMD_WG_ABL_TAIL_FENCE)
-    if (std::getenv("MBAMD_WG_TAIL_FENCE")) {     // (experiment: see the end of k_walkg)
-        static long long* counters = nullptr;
-        if (!counters) { (void) hipMalloc(&counters, (size_t) (in.Ppad / MBAMD_WG_TW) * 8); (void) hipMemset(counters, 0, (size_t) (in.Ppad / MBAMD_WG_TW) * 8); }
-        WalkGArgs b = a;
-        b.reserved = counters;
-        MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, b);
-        return;
-    }
-#endif
     MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, a);
 }
 
@@ -2430,7 +2391,7 @@ static void launch_mfma_serial_t(Instance& in, const OpTables& tabs, int ntables
     constexpr int NP = 2 * KC_ * NT_;
     const int gx = in.Ppad / 32;
     auto kern = k_partials_mfma_serial<NT_, SC_, KC_>;
-    if (!in.d_trace && in.envTrace) {
+    if (!in.d_trace && in.sw.walkTrace) {
         if (hipMalloc(&in.d_trace, (size_t) 4096 * 8 * 3 * sizeof(long long)) != hipSuccess) in.d_trace = nullptr;
         else (void) hipMemset(in.d_trace, 0, (size_t) 4096 * 8 * 3 * sizeof(long long));
     }
@@ -2443,7 +2404,7 @@ static void launch_mfma_spine_t(Instance& in, const OpTables& tabs, int ntables)
 {
     constexpr int NP = 2 * KC_ * NT_;
     const int gx = in.Ppad / 32;
-    if (!in.d_trace && in.envTrace) {
+    if (!in.d_trace && in.sw.walkTrace) {
         if (hipMalloc(&in.d_trace, (size_t) 4096 * 8 * 3 * sizeof(long long)) != hipSuccess) in.d_trace = nullptr;
         else (void) hipMemset(in.d_trace, 0, (size_t) 4096 * 8 * 3 * sizeof(long long));
     }
@@ -2456,7 +2417,7 @@ static void launch_mfma_spine_t(Instance& in, const OpTables& tabs, int ntables)
 static bool launch_mfma_serial(Instance& in, const OpTables& tabs, int ntables)
 {
     const int S = in.S, K = in.K;
-    if (!in.noSpine) {                           // software-pipelined variant (MBAMD_NO_SPINE=1: plain serial kernel)
+    if (!in.sw.noSpine) {                           // software-pipelined variant (MBAMD_NO_SPINE=1: plain serial kernel)
         if (in.NT == 1 && S == 20 && K == 4) { launch_mfma_spine_t<1, 20, 4>(in, tabs, ntables); return true; }
         if (in.NT == 1 && S == 20 && K == 1) { launch_mfma_spine_t<1, 20, 1>(in, tabs, ntables); return true; }
         if (in.NT == 2 && S == 61 && K == 1) { launch_mfma_spine_t<2, 61, 1>(in, tabs, ntables); return true; }
@@ -2474,7 +2435,7 @@ static bool launch_mfma_serial(Instance& in, const OpTables& tabs, int ntables)
 static bool launch_mfma(Instance& in, const PartialsOp* ops, int count, int32_t* cum)
 {
     const int S = in.S, K = in.K;
-    if (!in.mfmaWhole) {                 // default: one wave per factor tile (MBAMD_MFMA_WHOLE=1 selects the wave-per-tile-column kernel)
+    if (!in.sw.mfmaWhole) {                 // default: one wave per factor tile (MBAMD_MFMA_WHOLE=1 selects the wave-per-tile-column kernel)
         OpTables tabs;
         std::memset(&tabs, 0, sizeof tabs);
         tabs.ops[0] = ops;
@@ -2632,6 +2593,7 @@ int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, const std::
         }
         if (plan.spineChains.empty()) {
             from = nLevels;
+            const int spineWidth = std::max(1, sw.spineWidth.value_or(1));   // trailing levels of at most this many operations join
             while (from > 0 && start[from] - start[from - 1] <= spineWidth) from--;
             if (nLevels - from >= 2) {
                 plan.serialFrom = from;
@@ -2647,7 +2609,7 @@ int Instance::runGeneric(const Plan& plan, int32_t* cum)
     const std::vector<int>& start = plan.start;
     const int nLevels = (int) start.size() - 1;
     const bool anyScale = plan.anyScale;
-    if (plan.narrow && mfma && !mfmaWhole) {
+    if (plan.narrow && mfma && !sw.mfmaWhole) {
         OpTables tabs;
         std::memset(&tabs, 0, sizeof tabs);
         int nt = 0;
@@ -2664,11 +2626,11 @@ int Instance::runGeneric(const Plan& plan, int32_t* cum)
         }
     }
     int levelEnd = nLevels;
-    if (mfma && !mfmaWhole) levelEnd = plan.serialFrom;
+    if (mfma && !sw.mfmaWhole) levelEnd = plan.serialFrom;
     for (int l = 0; l < levelEnd; ++l) {
         int off = start[l];
         int remaining = start[l + 1] - start[l];
-        if (l == 0 && mfma && !mfmaWhole && plan.tipTip > 0 && plan.tipTip <= 8192) {
+        if (l == 0 && mfma && !sw.mfmaWhole && plan.tipTip > 0 && plan.tipTip <= 8192) {
             OpTables tabs;
             std::memset(&tabs, 0, sizeof tabs);
             tabs.ops[0] = plan.d_table;
@@ -2996,7 +2958,7 @@ int Instance::integrate4(const int* parent, const int* child, const int* prob, c
 // the block sums as their own completion signal: fill them with the pattern fetchResult waits to see overwritten
 void Instance::armSums()
 {
-    sumsArmed = pollSums && pollResult && !pendingResult && !deferred;
+    sumsArmed = pollResult && !pendingResult && !deferred;
     if (!sumsArmed) return;
     uint64_t* p = reinterpret_cast<uint64_t*>(h_sums);
     for (int i = 0; i < nblocks; ++i) p[i] = kSumSentinel;
@@ -3123,7 +3085,7 @@ int Instance::getSites(double* out)
         if (!h_site && hipHostMalloc((void**) &h_site, (size_t) Ppad * sizeof(double), hipHostMallocDefault) == hipSuccess) {
             if (hipHostGetDevicePointer((void**) &h_site_dev, h_site, 0) != hipSuccess) h_site_dev = nullptr;
         }
-        siteToHost = h_site_dev != nullptr && !noSiteHost;   // this client reads them: later evaluations write to the host directly
+        siteToHost = h_site_dev != nullptr;   // this client reads them: later evaluations write to the host directly
     }
     return BEAGLE_SUCCESS;
 }
@@ -3275,7 +3237,7 @@ int Instance::makeChildren(const std::vector<std::pair<int, int>>& ranges)
             Instance* c = nullptr;
             const int dev = shardDevices.empty() ? device : shardDevices[i % shardDevices.size()];
             int rc = new_engine(c, flags, createArgs[0], createArgs[1], createArgs[2], createArgs[3], n, createArgs[5], createArgs[6],
-                                createArgs[7], createArgs[8], dev);
+                                createArgs[7], createArgs[8], dev, sw);
             if (rc) { destroyChildren(); return rc; }
             c->logOpen = false;
             children.push_back(Child{c, start + done, n, (int) p});
@@ -3484,14 +3446,16 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
     } else {
         devices.push_back(0);
     }
-    if (const char* e = std::getenv("MBAMD_SHARD")) {      // MrBayes names at most one resource: shard over g devices from there
-        const int g = std::max(1, std::min(64, std::atoi(e)));
+    const Switches sw = read_switches();
+    if (sw.shard) {      // MrBayes names at most one resource: shard over g devices from there
+        const int g = std::max(1, std::min(64, *sw.shard));
         const int first = devices[0];
         devices.clear();
         for (int i = 0; i < g; ++i) devices.push_back((first + i) % ndev);
     }
     const int dev = devices[0];
     Instance* in = new Instance();
+    in->sw = sw;                                   // (a handle or facade keeps them too: its children are created from them)
     in->flags = kSupport | (requirementFlags & (BEAGLE_FLAG_SCALING_ALWAYS | BEAGLE_FLAG_SCALING_DYNAMIC));
     const int args[9] = {tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
                          matrixBufferCount, categoryCount, scaleBufferCount};
@@ -3506,7 +3470,7 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         in->flags = (in->flags & ~BEAGLE_FLAG_PRECISION_SINGLE) | BEAGLE_FLAG_PRECISION_DOUBLE;
         in->f64 = new Engine64();
         rc = in->f64->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                             matrixBufferCount, categoryCount, scaleBufferCount, dev);
+                             matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
     } else if (devices.size() > 1 && patternCount > 64) {
         // facade from the start: dimensions only, the children own the device memory
         in->device = dev;
@@ -3518,7 +3482,7 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
     } else {
         in->shardDevices.assign(1, dev);
         rc = in->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                        matrixBufferCount, categoryCount, scaleBufferCount, dev);
+                        matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
         if (rc == BEAGLE_ERROR_OUT_OF_MEMORY && in->wg) {
             // the arenas of the 20/61-state tree walk did not fit: once more on the level kernels (buffers allocated on first use)
             const long fl = in->flags;
@@ -3531,7 +3495,7 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
             std::memcpy(in->createArgs, args, sizeof args);
             in->shardDevices.assign(1, dev);
             rc = in->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                            matrixBufferCount, categoryCount, scaleBufferCount, dev);
+                            matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
         }
     }
     if (rc != BEAGLE_SUCCESS) {
@@ -3577,7 +3541,7 @@ int beagleFinalizeInstance(int instance)
         in = g_instances[instance];
         g_instances[instance] = nullptr;
     }
-    if (g_statsOn) {
+    if (g_loadSwitches.stats) {
         std::fprintf(stderr, "[mbamd] instance %d: plan cache %ld hits / %ld misses; tree-walk schedules re-used %llu / built %llu; root-ward paths held %ld, run with their log-likelihood as one launch %ld\n", instance,
                      in->planHits, in->planMisses, (unsigned long long) in->scheduleHits, (unsigned long long) in->scheduleMisses, in->heldPaths, in->fusedPaths);
         if (in->listsTotal)
@@ -4432,7 +4396,7 @@ int mbamdParsCreateInstance(int setCount, int patternCount, int wordsPerSet, int
         dev = in->facade() ? in->children[0].in->device : in->device;
     }
     ParsInstance* pi = new ParsInstance();
-    int rc = pi->create(setCount, patternCount, wordsPerSet, setBits, dev);
+    int rc = pi->create(setCount, patternCount, wordsPerSet, setBits, dev, read_switches());
     if (rc != BEAGLE_SUCCESS) {
         delete pi;
         return rc;

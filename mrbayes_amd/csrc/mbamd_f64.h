@@ -1278,24 +1278,20 @@ public:
     std::vector<QueuedOp> queue;
     std::vector<char> queuedScale;          // [nScale]: an exponent buffer some queued operation reads, writes or accumulates into
     uint64_t walkLaunches = 0, levelLaunches = 0;
-    bool walkAlways = false, walkVerbose = false;   // MBAMD_F64_WALK_ALWAYS, MBAMD_VERBOSE
-    bool noMfma = false;                           // MBAMD_F64_NO_MFMA: the vector-ALU level kernels for 16..64 states too
-    bool walkOff = false;                          // MBAMD_F64_NO_WALK (read when the instance is created): level kernels only
+    Switches sw;                                   // the environment switches, read when the instance was created (mbamd_switches.h)
     size_t bufDoubles = 0, matDoubles = 0, eigDoubles = 0;
 
     ~Engine64() { destroy(); }
 
     static int blockOf(int S) { return S <= 4 ? 4 : S <= 8 ? 8 : S <= 16 ? 16 : S <= 20 ? 20 : 32; }
 
-    int create(int tips, int partialsBuffers, int compactBuffers, int states, int patterns, int eigens, int matrices, int cats, int scales, int dev)
+    int create(int tips, int partialsBuffers, int compactBuffers, int states, int patterns, int eigens, int matrices, int cats, int scales, int dev,
+               const Switches& switches)
     {
+        sw = switches;
         device = dev; tipCount = tips; nBuffers = partialsBuffers + compactBuffers; S = states; P = patterns; Ppad = round_up(patterns, 64);
         K = cats; nEigen = eigens; nMatrices = matrices; nScale = scales;
         IB = blockOf(S);
-        walkOff = std::getenv("MBAMD_F64_NO_WALK") != nullptr;
-        walkAlways = std::getenv("MBAMD_F64_WALK_ALWAYS") != nullptr;
-        walkVerbose = std::getenv("MBAMD_VERBOSE") != nullptr;
-        noMfma = std::getenv("MBAMD_F64_NO_MFMA") != nullptr;
         SPAD = (S + IB - 1) / IB * IB;
         bufDoubles = (size_t) K * S * Ppad;
         matDoubles = (size_t) K * S * S + (size_t) K * S * SPAD;
@@ -1347,7 +1343,7 @@ public:
     int ringPut(const void* src, size_t bytes, uint8_t** hostSlot, uint8_t** devSlot)
     {
         *hostSlot = *devSlot = nullptr;
-        if (bytes > RING_MAX_ITEM || std::getenv("MBAMD_F64_NO_RING") != nullptr) return BEAGLE_SUCCESS;
+        if (bytes > RING_MAX_ITEM || sw.f64NoRing) return BEAGLE_SUCCESS;
         if (h_ring == nullptr) {
             HIP_TRY(hipHostMalloc((void**) &h_ring, RING_BYTES, hipHostMallocDefault));
             HIP_TRY(hipMalloc((void**) &d_ring, RING_BYTES));
@@ -1505,7 +1501,7 @@ public:
     }
     void launchMatrices(const MatrixJob64* dj, int count)
     {
-        if (S >= 16 && S <= 64 && !noMfma) {
+        if (S >= 16 && S <= 64) {
             const unsigned grid = (unsigned) (count * K);
             switch ((S + 15) / 16) {
                 case 1: MBAMD_LAUNCH_BARRIER(k64_matrices_mfma<1>, grid, 64, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
@@ -1563,7 +1559,7 @@ public:
             matQueued[(size_t) prob[i]] = 1;
             matQueue.push_back({matrixPtr(prob[i]), lengths[i], d_eigen + (size_t) eigenIdx * eigDoubles, 0.0});
         }
-        return std::getenv("MBAMD_F64_NO_MATRIX_QUEUE") != nullptr ? flushMatrices() : BEAGLE_SUCCESS;
+        return sw.f64NoMatrixQueue ? flushMatrices() : BEAGLE_SUCCESS;
     }
     // v3: an eigen-system and a category-rate vector per matrix; one launch per run of equal rate vectors
     int updateMatricesMulti(const int* eigenIdx, const int* rateIdx, const int* prob, const double* lengths, int count)
@@ -1624,11 +1620,11 @@ public:
     int tryWalk4(const QueuedOp* q, int n)
     {
         // (the kernel addresses with 32-bit lane offsets: a plane of partials and the whole exponent array below 4 GiB)
-        if (walkOff || S != 4 || K > 8 || !parts.empty() || n < 2 || (bufDoubles >> 29) != 0 || (((size_t) nScale + 1) * Ppad >> 30) != 0 || ((size_t) nMatrices * matDoubles >> 29) != 0) return 1;
+        if (sw.f64NoWalk || S != 4 || K > 8 || !parts.empty() || n < 2 || (bufDoubles >> 29) != 0 || (((size_t) nScale + 1) * Ppad >> 30) != 0 || ((size_t) nMatrices * matDoubles >> 29) != 0) return 1;
         // the walk is one latency chain per wave: it wins when there are enough waves (break-even about 1.2 per SIMD) and on short lists (a
         // root-ward path: one launch instead of one per operation); mid-sized full evaluations stay on the level kernels
         // (measured: profiles/r03_f64_walk.txt).  MBAMD_F64_WALK_ALWAYS=1: every eligible list.
-        if (!walkAlways && n > 64 && (long) (Ppad / 64) * K < 1200) return 1;
+        if (!sw.f64WalkAlways && n > 64 && (long) (Ppad / 64) * K < 1200) return 1;
         std::unique_ptr<StatTimer> st_(new StatTimer(ST_PLAN));      // (MBAMD_STATS: the host side of the walk, up to the upload)
         std::vector<Walk4Op>& wops = walkOps;
         wops.clear();
@@ -1662,7 +1658,7 @@ public:
         const int perCU = (int) std::min(16L, std::max(1L, (waves + 255) / 256));
         const int fixedBytes = 2 * KP * 18 * (int) sizeof(double) + 64;      // the parked matrices (+ allocation granularity)
         int nslots = std::max(2, std::min(24, ((160 * 1024) / perCU - fixedBytes) / slotBytes));
-        if (const char* e = std::getenv("MBAMD_F64_WALK_SLOTS")) nslots = std::max(2, std::min((160 * 1024 - fixedBytes) / slotBytes, std::atoi(e)));
+        if (sw.f64WalkSlots) nslots = std::max(2, std::min((160 * 1024 - fixedBytes) / slotBytes, *sw.f64WalkSlots));
         // structure key: who produces whose child, which children are tips (the indices only fill the program)
         std::vector<int> key;
         key.reserve((size_t) n * 3 + 2);
@@ -1718,7 +1714,7 @@ public:
                 writtenAt[e.dst] = (int) i;
             }
         }
-        if (walkVerbose) {
+        if (sw.verbose) {
             int mem = 0, tips = 0;
             for (const Walk64Entry& e : walkProg) {
                 mem += ((e.ctl & 3u) == 1u) + (((e.ctl >> 2) & 3u) == 1u);
@@ -1911,8 +1907,8 @@ public:
         {
             const int NTr = (S + 15) / 16;
             const size_t ldsBytes = (size_t) 2 * K * ((((S + 3) / 4) + 3) & ~3) * NTr * 64 * sizeof(double);
-            if (n >= 2 && S > 16 && S <= 64 && !noMfma && parts.empty() && K >= 1 && K <= 4 && NTr * K <= 8 && ldsBytes <= 65536 &&
-                std::getenv("MBAMD_F64_UNFUSED") == nullptr && std::getenv("MBAMD_F64_MFMA_NO_LDS") == nullptr && std::getenv("MBAMD_F64_NO_CHAIN") == nullptr) {
+            if (n >= 2 && S > 16 && S <= 64 && parts.empty() && K >= 1 && K <= 4 && NTr * K <= 8 && ldsBytes <= 65536 && !sw.f64MfmaNoLds &&
+                !sw.f64NoChain) {
                 std::vector<int> root((size_t) n);
                 for (int i = 0; i < n; ++i) root[i] = i;
                 auto find = [&](int x) { while (root[x] != x) x = root[x] = root[root[x]]; return x; };
@@ -1992,7 +1988,7 @@ public:
         int rc = stage(sorted.data(), sorted.size() * sizeof(Op64), &dv);
         if (rc) return rc;
         const Op64* dops = static_cast<const Op64*>(dv);
-        const bool fused = K == 4 && IB == 4 && S <= IB && std::getenv("MBAMD_F64_UNFUSED") == nullptr;
+        const bool fused = K == 4 && IB == 4 && S <= IB;
         for (int l = 0; l < nLevels; ++l) {
             const int first = start[l], cnt = start[(size_t) l + 1] - first;
             if (cnt <= 0) continue;
@@ -2003,14 +1999,14 @@ public:
                 MBAMD_LAUNCH(kern, grid, 64, 0, stream, dops + first, S, SPAD, Ppad);
                 continue;
             }
-            if (S >= 16 && S <= 64 && !noMfma) {
+            if (S >= 16 && S <= 64) {
                 const int NTr = (S + 15) / 16;
-                const bool fuse = K >= 1 && K <= 4 && NTr * K <= 8 && std::getenv("MBAMD_F64_UNFUSED") == nullptr;   // all K categories' tiles in registers
+                const bool fuse = K >= 1 && K <= 4 && NTr * K <= 8;   // all K categories' tiles in registers
                 // operations on two compact tips: the gather kernel (fused rescale only, K x ceil(S / 4) <= 32 products per lane)
                 const int NSL = (S + 3) / 4 <= 5 ? 5 : (S + 3) / 4 <= 8 ? 8 : 16;
-                int ntt = (fuse && NSL * K <= 32 && std::getenv("MBAMD_F64_NO_TIPS_KERNEL") == nullptr) ? tipsOf[l] : 0;
+                int ntt = (fuse && NSL * K <= 32 && !sw.f64NoTipsKernel) ? tipsOf[l] : 0;
                 const size_t tipsLds = (size_t) 2 * K * S * (SPAD | 1) * sizeof(double);
-                if (ntt > 0 && tipsLds <= 65536 && std::getenv("MBAMD_F64_TIPS_NO_LDS") == nullptr) {
+                if (ntt > 0 && tipsLds <= 65536) {
                     const dim3 tgrid((unsigned) ((Ppad + 255) / 256), (unsigned) ntt);
                     MBAMD_LAUNCH_BARRIER(k64_partials_tips_lds, tgrid, 256, tipsLds, stream, dops + first, S, SPAD, K, Ppad);
                 } else if (ntt > 0) {
@@ -2037,10 +2033,10 @@ public:
                 const size_t ldsBytes = (size_t) 2 * (fuse ? K : 1) * ((((S + 3) / 4) + 3) & ~3) * NTr * 64 * sizeof(double);
                 // (codon M3 0.90 -> 0.81 ms per evaluation; at 20 states x 4 categories the matrices are 5 KiB each and stay in the L1: 1.19 -> 1.16 ms
                 //  with four waves per workgroup since all eight are parked in ONE batch of loads -- a batch per category was 1.38)
-                const bool viaLds = NTr >= 2 && ldsBytes <= 65536 && std::getenv("MBAMD_F64_MFMA_NO_LDS") == nullptr;
+                const bool viaLds = NTr >= 2 && ldsBytes <= 65536 && !sw.f64MfmaNoLds;
                 // (eight waves per workgroup where that still gives every CU two workgroups; beyond 32 states: with four categories' accumulators
                 //  the 128 registers of four waves per SIMD mean spills, 1.55 ms)
-                const bool wide = NTr >= 3 && (size_t) ((Ppad + 127) / 128) * (size_t) (cnt - ntt) >= 512 && std::getenv("MBAMD_F64_MFMA_4WAVES") == nullptr;
+                const bool wide = NTr >= 3 && (size_t) ((Ppad + 127) / 128) * (size_t) (cnt - ntt) >= 512;
                 const dim3 lgrid((unsigned) (wide ? (Ppad + 127) / 128 : Ppad / 64), (unsigned) (cnt - ntt), (unsigned) (fuse ? 1 : K));
 #define MBAMD_F64_MFMA_CASE(NT_, KF_) do { \
                     if (viaLds && wide) MBAMD_LAUNCH_BARRIER((k64_partials_mfma_lds<NT_, KF_, 8>), lgrid, 512, ldsBytes, stream, dops + first + ntt, S, SPAD, Ppad); \
@@ -2068,12 +2064,10 @@ public:
 #undef MBAMD_F64_MFMA_CASE
                 if (fuse) continue;
             } else
-            switch (IB) {
+            switch (IB) {                                         // (fewer than 16 states)
                 case 4: launchPartials<4>(dops + first, cnt); break;
                 case 8: launchPartials<8>(dops + first, cnt); break;
-                case 16: launchPartials<16>(dops + first, cnt); break;
-                case 20: launchPartials<20>(dops + first, cnt); break;
-                default: launchPartials<32>(dops + first, cnt); break;
+                default: launchPartials<16>(dops + first, cnt); break;
             }
             bool anyScale = false;
             for (int i = first; i < first + cnt; ++i) anyScale |= sorted[i].mode != 0;

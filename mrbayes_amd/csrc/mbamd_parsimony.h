@@ -236,7 +236,6 @@ public:
     // wait on a stream costs ~25 us); MBAMD_NO_POLL=1: hipStreamSynchronize
     uint32_t* h_flag = nullptr;                      // pinned
     uint32_t* h_flag_dev = nullptr;
-    bool pollSums = false;                           // the sums as their own completion signal (armSums)
     uint32_t flagSeq = 0;
     bool poll = false;
     void* h_stage = nullptr;                         // pinned: one set in the device type
@@ -260,15 +259,16 @@ public:
     std::vector<std::pair<int, int>> heap;           // (subtree size, its root step)
     std::vector<ParsStep> compiled;
     std::vector<unsigned char> image;                // header + programs as they go to the device
-    bool verbose = false;                            // MBAMD_VERBOSE
+    Switches sw;                                     // the environment switches, read when the instance was created (mbamd_switches.h)
     int phaseLimit = MBAMD_PARS_MAXPHASES;           // phases per launch (MBAMD_PARS_PHASE_LIMIT: tests force programs over several launches)
     int waves = 0;                                   // MBAMD_PARS_WAVES: waves per workgroup (0: by the length of the program; 1: one serial program)
 
     ~ParsInstance() { destroy(); }
     int chunk() const { return width == 16 ? 2 : width == 8 ? 4 : 8; }
 
-    int create(int setCount, int patterns, int wordsPerSet, int setBits, int dev)
+    int create(int setCount, int patterns, int wordsPerSet, int setBits, int dev, const Switches& switches)
     {
+        sw = switches;
         device = dev;
         nSets = setCount;
         P = patterns;
@@ -295,17 +295,15 @@ public:
         HIP_TRY(hipHostMalloc(&h_stage, (size_t) Ppad * 16, hipHostMallocDefault));
         HIP_TRY(hipStreamSynchronize(stream));
         state.assign((size_t) nSets + 2, SetState());
-        verbose = std::getenv("MBAMD_VERBOSE") != nullptr;
-        if (std::getenv("MBAMD_NO_POLL") == nullptr && hipHostMalloc((void**) &h_flag, 64, hipHostMallocDefault) == hipSuccess &&
+        if (!sw.noPoll && hipHostMalloc((void**) &h_flag, 64, hipHostMallocDefault) == hipSuccess &&
             hipHostGetDevicePointer((void**) &h_flag_dev, h_flag, 0) == hipSuccess) {
             *h_flag = 0;
-            pollSums = std::getenv("MBAMD_NO_SUM_POLL") == nullptr;
             poll = true;
         } else {
             (void) hipGetLastError();
         }
-        if (const char* e = std::getenv("MBAMD_PARS_PHASE_LIMIT")) phaseLimit = std::max(1, std::min(MBAMD_PARS_MAXPHASES, std::atoi(e)));
-        if (const char* e = std::getenv("MBAMD_PARS_WAVES")) waves = std::max(1, std::min(MBAMD_PARS_MAXW, std::atoi(e)));
+        if (sw.parsPhaseLimit) phaseLimit = std::max(1, std::min(MBAMD_PARS_MAXPHASES, *sw.parsPhaseLimit));
+        if (sw.parsWaves) waves = std::max(1, std::min(MBAMD_PARS_MAXW, *sw.parsWaves));
         return BEAGLE_SUCCESS;
     }
 
@@ -443,13 +441,9 @@ public:
         std::memcpy(s.h, src, bytes);
         if (!direct) {
             // (round 6: a copy kernel of ours instead of hipMemcpyAsync -- ~10 us of host time per call, profiles/r06_ring_copy.txt)
-            static const bool noRingCopy = std::getenv("MBAMD_NO_RING_COPY") != nullptr;
-            if (noRingCopy) HIP_TRY(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, stream));
-            else {
-                const unsigned n4 = (unsigned) ((bytes + 3) / 4);
-                MBAMD_LAUNCH(k_copy_from_ring4, (n4 + 255u) / 256u, 256, 0, stream, static_cast<const unsigned*>(s.hdev), static_cast<unsigned*>(s.d), n4);
-                HIP_TRY(hipGetLastError());
-            }
+            const unsigned n4 = (unsigned) ((bytes + 3) / 4);
+            MBAMD_LAUNCH(k_copy_from_ring4, (n4 + 255u) / 256u, 256, 0, stream, static_cast<const unsigned*>(s.hdev), static_cast<unsigned*>(s.d), n4);
+            HIP_TRY(hipGetLastError());
         }
         *out = direct ? s.hdev : s.d;
         *used = &s;
@@ -474,12 +468,12 @@ public:
     }
     // Round 6: the sums are their own completion signal (as the likelihood engine's block sums, mbamd_engine.cpp armSums): the host
     // fills the `count` sums the next launch writes with a bit pattern no sum has, and waits until all of them have changed -- no
-    // stream operation behind the kernel.  MBAMD_NO_SUM_POLL=1: the stream's flag (A/B).
+    // stream operation behind the kernel.
     static constexpr uint64_t kSumSentinel = 0x7FF4DEADBEEF0001ull;
     size_t armed = 0;
     void armSums(size_t count)
     {
-        armed = (poll && pollSums) ? count : 0;
+        armed = poll ? count : 0;
         uint64_t* p = reinterpret_cast<uint64_t*>(h_out);
         for (size_t i = 0; i < armed; ++i) p[i] = kSumSentinel;
         __atomic_thread_fence(__ATOMIC_RELEASE);
@@ -791,7 +785,7 @@ public:
                     header[(size_t) (ph * MBAMD_PARS_MAXW + wq) * 2] = (int) (first / (size_t) CH);
                     header[(size_t) (ph * MBAMD_PARS_MAXW + wq) * 2 + 1] = nchunks;
                 }
-            if (verbose) {
+            if (sw.verbose) {
                 std::fprintf(stderr, "[mbamd] parsimony program: %d steps, %d waves, %d phases; chunks per wave:", taken, W, nphases);
                 for (int ph = 0; ph < nphases; ++ph) {
                     std::fprintf(stderr, " |");

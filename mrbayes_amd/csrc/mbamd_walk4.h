@@ -344,11 +344,7 @@ __device__ __forceinline__ int walk4_path_run(const Walk4Entry* pp, int n, unsig
             er[i] = 0;
             if (i < cnt) {
                 const Walk4Entry e = walk4_entry_from_lds(q + i);
-#if defined(MBAMD_P4_ABL_NO_LOAD)
-                F[i] = f4{0.25f, 0.25f, 0.25f, 0.25f};
-#else
                 if (!(e.ctl & (MBAMD_W4_TIP2 | MBAMD_P4_JOIN))) F[i] = walk4_at_kib(P0, e.c2)[lane];
-#endif
                 if (e.ctl & MBAMD_W4_READS) er[i] = walk4_at(E0, e.eread)[lane];
             }
         }
@@ -403,12 +399,8 @@ __device__ __forceinline__ int walk4_path_run(const Walk4Entry* pp, int n, unsig
                         cum_e += ew;
                         o.x = scale_pow2(o.x, -ex); o.y = scale_pow2(o.y, -ex);
                         o.z = scale_pow2(o.z, -ex); o.w = scale_pow2(o.w, -ex);
-#if defined(MBAMD_P4_ABL_NO_STORE)
-                        if (o.x == 123.456f) walk4_store_partials(walk4_at_kib(P0, e[u].dst), lane, o);
-#else
                         if (wm) walk4_store(walk4_at_kib(P0, e[u].dst), walk4_at(E0, e[u].ewrite), lane, o, ex);
                         else walk4_store_partials(walk4_at_kib(P0, e[u].dst), lane, o);
-#endif
                         prev = o;
                     }
                 }

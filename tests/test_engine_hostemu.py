@@ -45,6 +45,26 @@ def test_product_sources_have_no_emulation_fork():
         assert os.path.exists(os.path.join(root, "tests", "hostemu", f)), "no emulation twin for " + f
 
 
+def test_engine_switches_read_in_one_place():
+    """The engine reads its environment in mrbayes_amd/csrc/mbamd_switches.h only, and INTEGRATION.md names every switch read there."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "mrbayes_amd", "csrc")
+    readers = []
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if "getenv" in open(os.path.join(d, f), errors="replace").read():
+                readers.append(os.path.relpath(os.path.join(d, f), csrc))
+    assert readers == ["mbamd_switches.h"], readers
+    header = open(os.path.join(csrc, "mbamd_switches.h")).read()
+    names = set(re.findall(r'"(MBAMD_[A-Z0-9_]+)"', header))
+    assert len(names) > 30, sorted(names)
+    doc = open(os.path.join(root, "INTEGRATION.md")).read()
+    missing = sorted(n for n in names if not re.search(re.escape(n) + r"(?![A-Z0-9_])", doc))
+    assert not missing, missing
+
+
 @pytest.mark.parametrize("case", ["primates_gtr_g4", "avian_wag_g4", "replicase_m3"])
 def test_transition_matrices(emu, oracle, golden_dir, case):
     ec.check_transition_matrices(emu, oracle, division_from_golden(golden_dir, case))
