@@ -4,23 +4,27 @@
 integration) issued through the C ABI exactly as MrBayes' src/mbbeagle.c issues it for a generation whose
 move dirties the whole tree (reference src/proposal.c:17682, src/mbbeagle.c:400-537).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--no-cpu-baseline] [--no-also] [--no-mcmc]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-also] [--no-mcmc] ...]
 
 Default workload: BASELINE configs[3]'s shape, synthetic DNA 1000 taxa x 50 000 patterns GTR+G4 (the shape the
->=100x target is quoted on; it fits one GPU), one chain per GPU.  At N=1 the line also carries, under "also", the
-same measurement on the other three workloads (configs[1] DNA 500 x 20 000, configs[2] protein 200 x 10 000 WAG+G4,
-configs[4]'s codon M3 100 x 5 000) and, under "mcmc_gen_per_s", whole-MCMC generations/s of the
-unmodified MrBayes binary on this engine next to its native CPU kernels (short windows; --no-also / --no-mcmc skip
-them).  Every workload is a committed golden case (tests/golden/bench_c*.json): alignment seeds, tree and parameters
-are those the REAL reference was run on by tools/gen_golden.py, and the lnL printed in "config" is asserted against
-the reference's value before anything is timed.
+>=100x target is quoted on; it fits one GPU), one chain per GPU.  A plain run measures that workload alone: set-up,
+warm-up, the timed steps, the outputs if asked for, the line.  (--dump-outputs at N=1 writes the outputs of all four
+workloads: the other three are stepped for that, seconds, and stay out of the line.)  Everything else is behind --full
+(minutes): the reference CPU baseline, the box's write-stream rate and, at N=1, under "also" the same measurement on the
+other three workloads (configs[1] DNA 500 x 20 000, configs[2] protein 200 x 10 000 WAG+G4, configs[4]'s codon M3
+100 x 5 000), the double-precision engine, the per-site arithmetic report and, under "mcmc_gen_per_s", whole-MCMC
+generations/s of the unmodified MrBayes binary on this engine next to its native CPU kernels (short windows; --no-also /
+--no-mcmc skip them).  Every workload is a committed golden case (tests/golden/bench_c*.json): alignment seeds, tree
+and parameters are those the REAL reference was run on by tools/gen_golden.py, and the lnL printed in "config" is
+asserted against the reference's value before anything is timed.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): every rank owns one heated chain of the same
 shape on its own GPU (chain-parallel MCMCMC, the reference's MPI strategy, src/mcmc.c:18331-18384); the only
 exchange is the per-generation swap attempt: the two ranks that own the drawn chains send each other (lnL,
 lnPrior, heat) over RCCL, everybody else carries on (src/mcmc.c:653-668).  Weak scaling.  (A scaling harness: every
 rank replays full evaluations of its own chain state; the swap decision is made but does not change what is replayed.)
+With --full the line also carries the pattern-sharded chain and the MPI-build MCMC.
 
 Prints ONE JSON line on rank 0.  Unit of work = node-pattern update: one interior-node
 conditional-likelihood update of one unique site pattern over all categories, rescale included.
@@ -674,6 +678,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline workload, everything else the line can carry (minutes): the reference CPU baselines, "
+                         "the box's write-stream rate, at N=1 the other workloads, the double-precision engine, the per-site arithmetic "
+                         "report and whole-MCMC generations/s, at N > 1 the pattern-sharded chain, the MPI-build MCMC.  The --no-* "
+                         "options below, --mcmc, --mpi-full and --secondary-timeout shape what --full runs (--no-also also keeps "
+                         "--dump-outputs to the headline workload, as it always has)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-patterns", type=int, default=8000)
     ap.add_argument("--no-whole-cpu-baseline", action="store_true",
@@ -762,7 +772,7 @@ def main():
                 raise SystemExit("bench.py --shard: the %d shards of the instance sit on %s" % (world, out["instance_devices"]))
     else:
         out = measure(args, args.config, args.steps, args.warmup, rank, dev_index, world, dist, device, emulate, lib,
-                      not args.no_cpu_baseline, dump_dir=args.dump_outputs)
+                      args.full and not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     if world > 1 and dist is not None:
         # which physical GPU every rank computes on (PCI bus id of its resource): a scaling line whose ranks share a device is
         # not a scaling line -- refuse it instead of reporting it
@@ -775,11 +785,11 @@ def main():
             raise SystemExit("bench.py --gpus %d: ranks share a device (%s): refusing to report a scaling number" % (world, names))
         if rank == 0 and out is not None:
             out["ranks_devices"] = names
-    # The primary measurement is done.  What follows at N > 1 (pattern-sharded chain, the MPI-build MCMC) are secondary modes nobody
+    # The primary measurement is done.  What --full adds at N > 1 (pattern-sharded chain, the MPI-build MCMC) are secondary modes nobody
     # can debug on an 8-GPU node after the fact: each is bounded, and if one hangs (a collective that never completes, a child
     # process that never returns) every rank leaves after --secondary-timeout seconds and rank 0 prints the line with what finished.
     watchdog = None
-    if world > 1 and dist is not None and args.secondary_timeout > 0:
+    if world > 1 and dist is not None and args.full and args.secondary_timeout > 0:
         import threading
 
         def bail():
@@ -792,7 +802,7 @@ def main():
         watchdog = threading.Timer(args.secondary_timeout, bail)
         watchdog.daemon = True
         watchdog.start()
-    if world > 1 and not args.shard and dist is not None:
+    if world > 1 and not args.shard and dist is not None and args.full:
         try:                                     # (collective: every rank takes part; failures are reported, not fatal)
             ps = pattern_sharded(args, args.config, args.steps, args.warmup, rank, dev_index, world, dist, device, emulate, lib)
         except AssertionError:
@@ -801,7 +811,7 @@ def main():
             ps = {"error": repr(exc)[:600]}
         if rank == 0:
             out["pattern_sharded"] = ps
-    if rank == 0 and world == 1 and not emulate:
+    if rank == 0 and world == 1 and not emulate and args.full:
         fill = box_write_rate(device)
         if fill:                                 # a box-normalised reading beside the fraction of the nominal 8 TB/s
             for o in [out]:
@@ -843,7 +853,14 @@ def main():
                     out["mcmc_gen_per_s"] = mcmc_gen_per_s(json.load(fh), quick=not args.mcmc)
             except Exception as exc:
                 out["mcmc_gen_per_s"] = {"error": repr(exc)}
-    if rank == 0 and not args.no_mpi and not (world == 1 and args.no_mcmc):
+    elif rank == 0 and world == 1 and not emulate and args.dump_outputs and not args.no_also:
+        # --dump-outputs at N=1 writes the outputs of all four workloads, whether or not --full reports the other three: a plain
+        # run steps them exactly as `also` does, for their outputs alone, and puts nothing of them in the line
+        for other in ("c2", "c3", "c5", "c4"):
+            if other != args.config:
+                measure(args, other, args.steps, args.warmup, 0, dev_index, 1, None, device, False, lib, False, verbose=False,
+                        dump_dir=args.dump_outputs)
+    if rank == 0 and args.full and not args.no_mpi and not (world == 1 and args.no_mcmc):
         try:
             out["mpi_mcmc"] = mpi_mcmc(world, emulate=emulate, full=args.mpi_full)
         except Exception as exc:

@@ -1,14 +1,20 @@
 """bench.py's control flow on the CPU (--emulate: host-emulation engine, gloo): single process and the
 2-rank launch the driver uses for N>1 (torch.distributed.run on 127.0.0.1).  The numbers are meaningless;
-the contract of the JSON line and the N>1 path (rendezvous, chain exchange, max-over-ranks timing) are not."""
+the contract of the JSON line and the N>1 path (rendezvous, chain exchange, max-over-ranks timing) are not.
+One GPU test (-m gpu): the files a plain run's --dump-outputs writes on the device."""
 import json
 import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config", "roofline"}
+# what only --full puts in the line: the other workloads, precisions and baselines at N = 1, the secondary modes at N > 1
+FULL_ONLY = {"cpu_baseline", "cpu_baseline_whole_alignment", "also", "double_precision", "arith", "mcmc_gen_per_s", "mpi_mcmc",
+             "pattern_sharded", "timed_out"}
 
 
 def _mpi_on_shim():
@@ -32,6 +38,7 @@ def test_single_process():
     d = _json_line(res.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
+    assert not FULL_ONLY & set(d), sorted(FULL_ONLY & set(d))
 
 
 def test_dump_outputs(tmp_path):
@@ -54,11 +61,28 @@ def test_dump_outputs(tmp_path):
     assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
 
 
+@pytest.mark.gpu
+def test_plain_run_dumps_every_workload(tmp_path):
+    """On the GPU, --dump-outputs without --full writes the outputs of all four workloads, as it did before --full existed,
+    while the line carries the headline workload alone; each file is what that workload's last timed step returned."""
+    import numpy as np
+    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    d = _json_line(res.stdout)
+    assert KEYS <= set(d) and d["config"]["golden_case"] == "bench_c4" and not FULL_ONLY & set(d), sorted(FULL_ONLY & set(d))
+    assert sorted(os.listdir(tmp_path)) == sorted("%s_%s.npy" % (c, n) for c in ("c2", "c3", "c4", "c5") for n in ("lnL", "site_lnL"))
+    assert np.load(tmp_path / "c4_lnL.npy")[0] == d["config"]["lnL"]
+    for c in ("c2", "c3", "c4", "c5"):
+        lnl, site = np.load(tmp_path / ("%s_lnL.npy" % c)), np.load(tmp_path / ("%s_site_lnL.npy" % c))
+        assert lnl.dtype == site.dtype == np.float64 and abs(site.sum() - lnl[0]) <= 1e-9 * abs(lnl[0]), c
+
+
 def test_two_ranks():
     mpi = _mpi_on_shim()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                          "--master-addr", "127.0.0.1", "--master-port", "29671", "bench.py", "--gpus", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", "29671", "bench.py", "--gpus", "2", "--full",
                           "--steps", "3", "--warmup", "1", "--emulate"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=900)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
@@ -78,6 +102,21 @@ def test_two_ranks():
         m = d["mpi_mcmc"]
         assert m["ranks"] == 2 and m["cases"][0]["generations_per_s"] > 0, m
         assert set(m["devices_of_rank"]) == {"0", "1"} and m["distinct_devices"] >= 1, m      # every rank's engine reported its device
+
+
+def test_plain_run_leaves_the_secondary_modes_to_full():
+    """Without --full a run at N > 1 is the timed chain-parallel replay and nothing else: no pattern-sharded chain and -- although
+    the reference's MPI build on the shim is there to run where the reference sources are -- no MPI-build MCMC."""
+    _mpi_on_shim()
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", "29675", "bench.py", "--gpus", "2",
+                          "--steps", "2", "--warmup", "1", "--emulate"], cwd=ROOT, env=env, capture_output=True,
+                         text=True, timeout=900)
+    assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
+    d = _json_line(res.stdout)
+    assert KEYS <= set(d) and d["n_gpus"] == 2 and d["config"]["chains"] == 2 and d["value"] > 0
+    assert not FULL_ONLY & set(d), sorted(FULL_ONLY & set(d))
 
 
 def test_plain_command_launches_its_own_ranks():
@@ -119,7 +158,7 @@ def test_eight_ranks():
     mpi = _mpi_on_shim()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-                          "--master-addr", "127.0.0.1", "--master-port", "29677", "bench.py", "--gpus", "8",
+                          "--master-addr", "127.0.0.1", "--master-port", "29677", "bench.py", "--gpus", "8", "--full",
                           "--steps", "2", "--warmup", "1", "--emulate"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=1500)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
@@ -141,11 +180,10 @@ def test_secondary_modes_are_bounded():
     """A secondary mode that does not come back must not cost the scaling line: with a 20 ms budget (the emulated MPI run
     and the pattern-sharded chain taking longer) every rank leaves, rank 0 prints the primary measurement and says what it gave up on."""
     if not _mpi_on_shim():
-        import pytest
         pytest.skip("needs the reference's MPI build on the shim (oracle/_ref)")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                          "--master-addr", "127.0.0.1", "--master-port", "29679", "bench.py", "--gpus", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", "29679", "bench.py", "--gpus", "2", "--full",
                           "--steps", "2", "--warmup", "1", "--emulate", "--secondary-timeout", "0.02"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=900)
     d = _json_line(res.stdout)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The rows of DESIGN.md section 7 / README.md from a bench line:   python tools/bench_tables.py profiles/r04_bench_default.json"""
+"""The rows of DESIGN.md section 7 / README.md from a `bench.py --full` line:   python tools/bench_tables.py profiles/r04_bench_default.json"""
 import json
 import sys
 
