@@ -421,7 +421,7 @@ class BeagleInstance:
         return ms.value, n.value
 
     def get_list_counts(self):
-        """(lists, paths, forked paths, paths fused with their log-likelihood, tree walks, their operations) of the 4-state lists."""
+        """(lists, paths, forked paths, paths fused with their log-likelihood, tree walks, their operations) of the lists (4-state calls; 20- and 60-63-state queue flushes)."""
         out = (C.c_long * 6)()
         self._chk(self.lib.mbamdGetListCounts(self.id, out), "mbamdGetListCounts")
         return tuple(int(v) for v in out)

@@ -1910,7 +1910,8 @@ bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
 }
 
 // The same for the 20/61-state walk (k_pathg, mbamd_pathg_kernel.h): `nl` mutually independent lists (the eigen-system parts of a
-// codon model; one for a protein model), each a root-ward path, all of the same length.  Entries [list][operation] in the tile
+// codon model; one for a protein model), each a root-ward path -- or root-ward paths that join, arms as in buildPath4, at the same
+// positions in every list --, all of the same length.  Entries [list][operation] in the tile
 // arena's units (byte offsets of a buffer inside a tile, tip states at 32 bytes per buffer, matrix buffers in bytes).
 static inline bool pathg_compiled(int S) { return S == 20 || (S >= 60 && S <= 63); }
 bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl)
@@ -1924,8 +1925,10 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
     auto writtenIn = [&](int buf, int lo, int hi) { for (int o = lo; o < hi; ++o) if (ops[o].destinationPartials == buf) return true; return false; };
     std::vector<Walk4Entry>& prog = plan.inlineProg;
     prog.assign((size_t) n, Walk4Entry());
+    int arms = 1;
     for (int q = 0; q < nl; ++q) {
         const int lo = q * L;
+        int saved = -1, armsHere = 0;                // buffer of the saved result (an arm that waits for its join), or -1
         for (int i = 0; i < L; ++i) {
             const BeagleOperation& b = ops[lo + i];
             if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 || b.child1Partials >= nBuffers ||
@@ -1933,15 +1936,26 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
                 b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices) return false;      // (buildWalk reports it)
             if (tipStates[b.destinationPartials] || writtenIn(b.destinationPartials, 0, lo + i)) return false;
             int chain, sib, mchain, msib;
-            if (i == 0) { chain = b.child1Partials; sib = b.child2Partials; mchain = b.child1TransitionMatrix; msib = b.child2TransitionMatrix; }
-            else {
-                const int prev = ops[lo + i - 1].destinationPartials;
-                const bool one = b.child1Partials == prev, two = b.child2Partials == prev;
-                if (one == two) return false;
+            const int prev = i == 0 ? -1 : ops[lo + i - 1].destinationPartials;
+            const bool one = i > 0 && b.child1Partials == prev, two = i > 0 && b.child2Partials == prev;
+            if (one && two) return false;
+            const bool start = !one && !two;
+            bool join = false;
+            if (start) {
+                // FORKED paths, as buildPath4's: an operation that does not read its predecessor's result begins a new arm and the
+                // predecessor's result is saved; one saved result at a time
+                if (i > 0) {
+                    if (sw.noForkPath || saved >= 0) return false;
+                    saved = prev;
+                }
+                ++armsHere;
+                chain = b.child1Partials; sib = b.child2Partials; mchain = b.child1TransitionMatrix; msib = b.child2TransitionMatrix;
+            } else {
                 chain = one ? b.child1Partials : b.child2Partials; sib = one ? b.child2Partials : b.child1Partials;
                 mchain = one ? b.child1TransitionMatrix : b.child2TransitionMatrix; msib = one ? b.child2TransitionMatrix : b.child1TransitionMatrix;
+                if (saved >= 0 && sib == saved) { join = true; saved = -1; }              // ... an operation whose other child it is joins the arms
             }
-            for (int ext : {sib, i == 0 ? chain : -1})
+            for (int ext : {join ? -1 : sib, start ? chain : -1})
                 if (ext >= 0) {
                     if (writtenIn(ext, 0, n)) return false;                // (nothing any of the lists writes)
                     if (!tipStates[ext] && !valid[ext]) return false;
@@ -1950,12 +1964,16 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
             std::memset(&e, 0, sizeof e);
             uint32_t flags = 0, mode = SCALE_NONE;
             e.dst = (uint32_t) b.destinationPartials * pbuf;
-            if (i == 0) {
+            if (start) {
+                flags |= MBAMD_P4_START;
                 if (tipStates[chain]) { e.c1 = (uint32_t) chain * (uint32_t) MBAMD_WG_TW; flags |= MBAMD_W4_TIP1; }
                 else e.c1 = (uint32_t) chain * pbuf;
             }
-            if (tipStates[sib]) { e.c2 = (uint32_t) sib * (uint32_t) MBAMD_WG_TW; flags |= MBAMD_W4_TIP2; }
+            if (join) flags |= MBAMD_P4_JOIN;
+            else if (tipStates[sib]) { e.c2 = (uint32_t) sib * (uint32_t) MBAMD_WG_TW; flags |= MBAMD_W4_TIP2; }
             else e.c2 = (uint32_t) sib * pbuf;
+            // every list the same arms: the workgroups of one launch run the same program shape
+            if (q > 0 && ((prog[(size_t) i].ctl ^ flags) & (MBAMD_P4_START | MBAMD_P4_JOIN)) != 0) return false;
             e.m1 = (uint32_t) mchain * mbuf;
             e.m2 = (uint32_t) msib * mbuf;
             e.ewrite = e.eread = (uint32_t) scratchScale * ebuf;
@@ -1973,9 +1991,12 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
             }
             e.ctl = flags | (mode << 8) | ((uint32_t) q << 10);
         }
+        if (saved >= 0) return false;                // (an arm nobody joins: two trees in one list)
+        arms = armsHere;
     }
-    if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths (k_pathg)\n", nl, L);
+    if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths%s (k_pathg)\n", nl, L, arms > 1 ? " that join" : "");
     plan.pathG = true;
+    plan.forked = arms > 1;
     plan.lists = nl;
     plan.segments.clear();
     Plan::Segment sg;
@@ -2214,10 +2235,10 @@ int Instance::flushWalkG()
         {
             StatTimer st_(ST_PLAN);
             plan->lists = 1;
-            plan->pathG = false;
+            plan->pathG = plan->forked = false;
             rc = BEAGLE_SUCCESS;
             bool done = (nl == 1 || independent) && buildPathG(*plan, ops.data(), n, starts, nl);
-            if (!done) plan->inlineProg.clear();
+            if (!done) { plan->inlineProg.clear(); plan->pathG = plan->forked = false; }
             if (!done && independent) {
                 const int keepW = w4.maxW, keepS = w4.maxSlots, keepS1 = w4.maxSlots1;
                 wgGeometry(nl, w4.maxW, w4.maxSlots);
@@ -2242,6 +2263,10 @@ int Instance::flushWalkG()
         }
         if (rc) { plan->hash = 0; plan->key.clear(); return rc; }
     }
+    // what updatePartials4 counts; one flush = one list event, however many eigen-system parts it carries
+    listsTotal++;
+    if (plan->pathG) { listsPath++; if (plan->forked) forkedPaths++; }
+    else { listsWalked++; opsWalked += n; }
     for (int o = 0; o < n; ++o) {
         valid[ops[o].destinationPartials] = 1;
         if (ops[o].destinationScaleWrite != BEAGLE_OP_NONE) scaleState[ops[o].destinationScaleWrite] = 1;
@@ -2266,12 +2291,17 @@ static void launch_walkg_t(Instance& in, const WalkGArgs& a, int W, int nslots, 
 }
 
 template <int SC_>
-static void launch_pathg_t(Instance& in, const WalkGArgs& a, const std::vector<Walk4Entry>& prog)
+static void launch_pathg_t(Instance& in, const WalkGArgs& a, const std::vector<Walk4Entry>& prog, bool forked)
 {
     WalkGArgsInline ai;
     ai.a = a;
     ai.a.prog = nullptr;
     std::memcpy(ai.inl, prog.data(), prog.size() * sizeof(Walk4Entry));
+    if (forked) {
+        auto kern = k_pathg<SC_, WalkGArgsInline, true>;
+        MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S, true), in.stream, ai);
+        return;
+    }
     auto kern = k_pathg<SC_, WalkGArgsInline>;
     MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S), in.stream, ai);
 }
@@ -2297,11 +2327,11 @@ int Instance::runWalkG(const Plan& plan)
         a.K = K; a.Ppad = Ppad; a.ntiles = Ppad / MBAMD_WG_TW; a.S = S; a.SP = SP;
         a.lists = plan.lists;
         switch (S) {
-            case 20: launch_pathg_t<20>(*this, a, plan.inlineProg); break;
-            case 60: launch_pathg_t<60>(*this, a, plan.inlineProg); break;
-            case 61: launch_pathg_t<61>(*this, a, plan.inlineProg); break;
-            case 62: launch_pathg_t<62>(*this, a, plan.inlineProg); break;
-            default: launch_pathg_t<63>(*this, a, plan.inlineProg); break;
+            case 20: launch_pathg_t<20>(*this, a, plan.inlineProg, plan.forked); break;
+            case 60: launch_pathg_t<60>(*this, a, plan.inlineProg, plan.forked); break;
+            case 61: launch_pathg_t<61>(*this, a, plan.inlineProg, plan.forked); break;
+            case 62: launch_pathg_t<62>(*this, a, plan.inlineProg, plan.forked); break;
+            default: launch_pathg_t<63>(*this, a, plan.inlineProg, plan.forked); break;
         }
         HIP_TRY(hipGetLastError());
         pendingLaunches += 1;
@@ -3545,8 +3575,8 @@ int beagleFinalizeInstance(int instance)
         std::fprintf(stderr, "[mbamd] instance %d: plan cache %ld hits / %ld misses; tree-walk schedules re-used %llu / built %llu; root-ward paths held %ld, run with their log-likelihood as one launch %ld\n", instance,
                      in->planHits, in->planMisses, (unsigned long long) in->scheduleHits, (unsigned long long) in->scheduleMisses, in->heldPaths, in->fusedPaths);
         if (in->listsTotal)
-            std::fprintf(stderr, "[mbamd] instance %d: 4-state lists %ld: root-ward paths %ld (of them forked %ld), tree walks %ld (%.1f operations each)\n", instance,
-                         in->listsTotal, in->listsPath, in->forkedPaths, in->listsWalked, in->listsWalked ? (double) in->opsWalked / in->listsWalked : 0.0);
+            std::fprintf(stderr, "[mbamd] instance %d: %d-state lists %ld: root-ward paths %ld (of them forked %ld), tree walks %ld (%.1f operations each)\n", instance,
+                         in->S, in->listsTotal, in->listsPath, in->forkedPaths, in->listsWalked, in->listsWalked ? (double) in->opsWalked / in->listsWalked : 0.0);
         for (const ApiStats& a : g_stats)
             std::fprintf(stderr, "[mbamd]   %-34s %9ld calls %10.3f ms total %9.2f us/call\n", a.name, a.calls,
                          a.seconds * 1e3, a.calls ? a.seconds * 1e6 / a.calls : 0.0);

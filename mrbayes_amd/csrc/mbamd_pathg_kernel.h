@@ -9,17 +9,40 @@
 //   wave 0  runs the chain: its B operand is the previous result STILL IN ITS REGISTERS (the accumulator layout is the B layout,
 //           mbamd_walkg.h), so an operation is one MFMA chain, the product with the factor from the ring, the rescale and the stores.
 // The two waves keep in step through two counters in LDS (factors produced / factors consumed).
-// Entries (Walk4Entry, as k_path4's): c1 = the chain's INPUT (entry 0 only: tip states or a buffer), c2 = the sibling, m1 / m2 their
-// matrix buffers; ctl: TIP1 (entry 0), TIP2, [9:8] the scale mode, [11:10] the list.  Same arithmetic, operation by operation, as
-// k_walkg: the same bits.  blockDim.x = 128; grid = walkg_grid(ntiles, K * lists); dynamic LDS = pathg_lds_bytes(S).
+// Entries (Walk4Entry, as k_path4's): c1 = the chain's INPUT (START entries only: tip states or a buffer), c2 = the sibling, m1 / m2
+// their matrix buffers; ctl: TIP1 (START entries), TIP2, [9:8] the scale mode, [11:10] the list, MBAMD_P4_START / MBAMD_P4_JOIN.  Same
+// arithmetic, operation by operation, as k_walkg: the same bits.  blockDim.x = 128; grid = walkg_grid(ntiles, K * lists); dynamic
+// LDS = pathg_lds_bytes(S, forked); forked programs run on the FORK = true instantiation.
+//
+// FORKED paths (the list of a topology move: arm A, arm B, the operation that joins them, the stem -- buildPathG).  Entry 0 is a
+// START; a START entry j > 0 begins arm B: the chain's running result, arm A's last, is PARKED -- written once, as stored (after its
+// rescale: the rows k_walkg would read back from the buffer), into a tile of LDS behind the ring, in B layout [t][lane] -- and the
+// chain takes its new input from c1 / m1 as entry 0 does.  The JOIN entry has no c2: its sibling is the parked tile, and wave 1 forms
+// M2 x parked from it into the ring like any other factor, so the join costs the chain nothing.  One tile: one result waits at a time
+// (several forks may follow one another).
+// Counters (LDS, each written by ONE wave, read by the other):
+//   produced  wave 1: factors put into the ring          wave 0 waits   produced > j            before it takes factor j
+//   consumed  wave 0: factors taken out of the ring      wave 1 waits   j - consumed < RING     before it overwrites a slot
+//   parked    wave 0: results parked                     wave 1 waits   parked > joins so far   before it reads the tile at a JOIN
+// No deadlock: wave 0 parks at the START of arm B BEFORE it waits for that entry's factor, and it reaches that entry by taking factors
+// 0 .. j - 1 only, all of which wave 1 produces before anything that waits for the tile (wave 1 works in entry order and waits for
+// the tile at the JOIN alone, which comes after the START); so whenever wave 1 waits at a JOIN, the tile is published or wave 0 is on
+// its way to publish it with every factor it needs for that already in the ring or coming without a further wait on `parked`.  The
+// tile is not overwritten while it is read: the next START comes after the JOIN, whose factor wave 0 takes only after wave 1 has
+// read the tile into registers, contracted it and published the product.
 #ifndef MBAMD_PATHG_KERNEL_H_
 #define MBAMD_PATHG_KERNEL_H_
 namespace mbamd {
 
 #define MBAMD_PG_RING 4          // factor tiles in flight between the two waves
-__host__ __device__ inline size_t pathg_lds_bytes(int S) { return 64 + (size_t) MBAMD_PG_RING * wg_tiles(S) * 16 * 64 * sizeof(float); }
+// (the parked tile of a forked program lies BEHIND the ring: a single path's launch neither allocates nor pays for it)
+__host__ __device__ inline size_t pathg_lds_bytes(int S, bool forked = false)
+{
+    return 64 + (size_t) MBAMD_PG_RING * wg_tiles(S) * 16 * 64 * sizeof(float) + (forked ? wg_block_bytes(S) : 0u);
+}
 
-template <int SC, class ARGS = WalkGArgs>
+// FORK = false is the single path's kernel: no arm can start or join in it, and nothing of the arms' code or registers is in it.
+template <int SC, class ARGS = WalkGArgs, bool FORK = false>
 __global__ void __launch_bounds__(128)
 k_pathg(ARGS AA)
 {
@@ -46,7 +69,9 @@ k_pathg(ARGS AA)
     typedef MBAMD_AS_LDS volatile int pg_vint;
     pg_vint* const produced = (pg_vint*) lds;                 // factors wave 1 has put into the ring
     pg_vint* const consumed = (pg_vint*) (lds + 4);           // factors wave 0 has taken out of it
+    pg_vint* const parked = (pg_vint*) (lds + 8);             // results wave 0 has parked for a JOIN (forked programs)
     float* const ring = reinterpret_cast<float*>(lds + 64);   // [MBAMD_PG_RING][NT * 16][64]
+    float* const park = ring + (size_t) MBAMD_PG_RING * (NT * 16 * 64);      // [TP][64]: the parked result (forked programs only: not allocated otherwise)
     char* const P0 = reinterpret_cast<char*>(A.partials) + (size_t) tile * A.tileBytes + (size_t) k * SLOTB;
     const uint8_t* const T0 = A.tips + (size_t) tile * A.tipTileBytes;
     int8_t* const E0 = A.exps + (size_t) ((tile * TW) >> 6) * A.estride + (size_t) k * 64 + ((tile * TW) & 63u);
@@ -54,7 +79,7 @@ k_pathg(ARGS AA)
     const Walk4Entry* const prog = wg_program(AA) + (size_t) list * A.entries;
     const int n = A.entries;
 
-    if (lane == 0) { if (wave == 0) produced[0] = 0; else consumed[0] = 0; }
+    if (lane == 0) { if (wave == 0) produced[0] = 0; else { consumed[0] = 0; if (FORK) parked[0] = 0; } }
     MBAMD_SYNC();
 
     // a child's factor F[i][p] = sum_j P(i -> j) cl[j][p]: a compact tip gathers its column from the tip table, a buffer is a chain of
@@ -123,9 +148,20 @@ k_pathg(ARGS AA)
         Operands X, Y;
         Walk4Entry e = walk4_load_entry(prog);
         request((e.ctl & MBAMD_W4_TIP2) != 0, e.m2, e.c2, X);
-        auto produce = [&](int j, const Operands& cur, Operands& nxt) {
+        int joins = 0;
+        auto produce = [&](int j, Operands& cur, Operands& nxt) {
             const Walk4Entry en = walk4_load_entry(prog + (j + 1 < n ? j + 1 : j));
-            if (j + 1 < n) request((en.ctl & MBAMD_W4_TIP2) != 0, en.m2, en.c2, nxt);
+            if (j + 1 < n) {
+                if (FORK && (en.ctl & MBAMD_P4_JOIN)) load_table(en.m2, nxt.a);      // (its rows are the parked tile)
+                else request((en.ctl & MBAMD_W4_TIP2) != 0, en.m2, en.c2, nxt);
+            }
+            if (FORK && (e.ctl & MBAMD_P4_JOIN)) {
+                ++joins;
+                while (mbd_uniform(parked[0]) < joins) MBD_SPIN_PAUSE();                  // the other arm's last result is in the tile
+                MBD_COMPILER_FENCE();
+#pragma unroll
+                for (int t = 0; t < TP; ++t) cur.b[t] = park[t * 64 + lane];
+            }
             acc_t f[NT];
             factor((e.ctl & MBAMD_W4_TIP2) != 0, cur, f);
             while (j - mbd_uniform(consumed[0]) >= MBAMD_PG_RING) MBD_SPIN_PAUSE();     // the slot's last factor has been taken
@@ -160,15 +196,34 @@ k_pathg(ARGS AA)
 #pragma unroll
         for (int t = 0; t < TP; ++t) prev[t] = X.b[t];
     }
+    int nparked = 0;
     auto link = [&](int j, const Operands& cur, Operands& nxt) {
         const Walk4Entry en = walk4_load_entry(prog + (j + 1 < n ? j + 1 : j));
         const unsigned ctl = e.ctl;
         const unsigned mode = (ctl >> 8) & 3u;
         int er = 0;
         if (mode == SCALE_READ) er = as_global(E0 + e.eread)[col];
-        if (j + 1 < n) load_table(en.m1, nxt.a);     // the next operation's table: in flight under this operation's MFMA chain
+        const bool armStart = FORK && j > 0 && (ctl & MBAMD_P4_START) != 0;
+        if (armStart) {
+            // a new arm: the finished arm's result waits in LDS for its JOIN (wave 1 reads it there), the chain starts afresh
+            float* const pk = park + lane;
+#pragma unroll
+            for (int t = 0; t < TP; ++t) pk[t * 64] = prev[t];
+            MBAMD_WAVE_SYNC();                       // (every lane's rows are in front of the counter)
+            parked[0] = ++nparked;
+            MBD_COMPILER_FENCE();
+            if (!(ctl & MBAMD_W4_TIP1)) {
+#pragma unroll
+                for (int t = 0; t < TP; ++t) prev[t] = cur.b[t];
+            }
+        }
+        // the next operation's table -- the whole operand set if it starts an arm --: in flight under this operation's MFMA chain
+        if (j + 1 < n) {
+            if (FORK && (en.ctl & MBAMD_P4_START)) request((en.ctl & MBAMD_W4_TIP1) != 0, en.m1, en.c1, nxt);
+            else load_table(en.m1, nxt.a);
+        }
         acc_t f1[NT], f2[NT];
-        if (j == 0 && tipInput) factor(true, cur, f1);
+        if ((j == 0 && tipInput) || (armStart && (ctl & MBAMD_W4_TIP1))) factor(true, cur, f1);
         else contract(cur.a, prev, f1);
         while (mbd_uniform(produced[0]) <= j) MBD_SPIN_PAUSE();
         MBD_COMPILER_FENCE();
