@@ -365,8 +365,8 @@ BEAGLE_DLLEXPORT int mbamdGetListCounts(int instance, long* out6);
  * Calculate*LogLikelihoods call to the end of the next integration kernel, i.e. every kernel of a step (transition matrices,
  * partials, integration) and the gaps between them -- and how many such spans were closed. */
 BEAGLE_DLLEXPORT int mbamdGetStepTiming(int instance, double* outMilliseconds, long* outSteps, int reset);
-/* Select the partials kernel family: 0 = automatic, 1 = level-synchronous generic kernels,
- * 2 = tree-walk kernel (4-state), 3 = MFMA kernels (20/61-state).  For A/B measurements. */
+/* Accepted and ignored (kept for clients that call it): an instance picks its kernel family from its dimensions, and the A/B
+ * switches are environment variables.  path outside 0..3: BEAGLE_ERROR_OUT_OF_RANGE, as before. */
 BEAGLE_DLLEXPORT int mbamdSetKernelPath(int instance, int path);
 /* Calculate*LogLikelihoods without the device->host copy: leaves the sum on the device and returns
  * immediately; mbamdFetchLogLikelihood blocks and returns it (same error convention). */

@@ -84,15 +84,24 @@ static int fail(int code, const char* what, const char* detail = "")
     return code;
 }
 
+static int hip_fail(hipError_t e, const char* what)
+{
+    return fail(e == hipErrorOutOfMemory ? BEAGLE_ERROR_OUT_OF_MEMORY : BEAGLE_ERROR_GENERAL, what, hipGetErrorString(e));
+}
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? BEAGLE_ERROR_OUT_OF_MEMORY : BEAGLE_ERROR_GENERAL, \
-                        #expr, hipGetErrorString(e_));                                             \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr);                                          \
     } while (0)
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// FNV-1a over 32-bit words: the hash of the plan cache and of the tree-walk templates (`h`: continue an earlier hash)
+static inline uint64_t fnv1a(const int* v, size_t n, uint64_t h = 1469598103934665603ull)
+{
+    for (size_t i = 0; i < n; ++i) h = (h ^ (uint64_t) (uint32_t) v[i]) * 1099511628211ull;
+    return h;
+}
 
 // state counts the 20/61-state tree walk (mbamd_walkg.h) is instantiated for: amino acids, doublets, and the sense codons of
 // every genetic code MrBayes knows (60 vertebrate mitochondrial ... 63; reference src/model.c SetCode)
@@ -132,8 +141,6 @@ static void raise_walkg_lds(int maxLds)
         (void) hipGetLastError();
 }
 
-enum KernelPath { PATH_AUTO = 0, PATH_GENERIC = 1, PATH_WALK = 2, PATH_MFMA = 3 };
-
 // A compiled operation list: the device-resident table a partials kernel walks, cached under the exact
 // BeagleOperation array it was built from.  MrBayes re-issues the same lists all the time (every move
 // that dirties the whole tree alternates between the two buffer-flip states), so the host-side
@@ -163,6 +170,17 @@ struct Plan {
     int serialFrom = 0;                          // general path: levels >= serialFrom are narrow (the spine towards the
                                                  // root): they run as one serial launch after the level launches
     std::vector<int> bufsRead, bufsWritten, scalesUsed;   // buffer / scale indices the list touches (deferral hazards)
+};
+
+// One operation of a root-ward path as Instance::recognisePath sees it, in buffer / matrix / scale INDICES: the path kernels'
+// entries are filled from it in their own units (Instance::pathEntry).
+struct PathStep {
+    bool start, join;                // begins an arm (both children come from outside) / its other child is the saved result of the arm before
+    bool chainTip, sibTip;           // the child is a compact tip
+    int arm;                         // start: the number of operations of the arm it begins
+    int dst, chain, sib;             // partials buffers: result; the child on the path (an operand only where an arm starts); the other child
+    int mchain, msib;                // their transition matrices
+    int scaleMode, scaleIdx;         // SCALE_NONE / SCALE_WRITE / SCALE_READ and its exponent buffer
 };
 
 struct Instance {
@@ -235,7 +253,9 @@ struct Instance {
     unsigned long wgTileBytes = 0;               // partials arena: bytes between 32-pattern tiles
     unsigned wgTipTileBytes = 0;
     size_t wgTabFloats = 0;                      // first float of the tree-walk tables inside a matrix buffer
-    bool hasPending() const { return !pending.empty() || !wgListCum.empty() || heldPath != nullptr; }
+    // deferred lists (`path`: a held 4-state path counts) / anything at all that flushPending would launch
+    bool hasPending(bool path = true) const { return !pending.empty() || !wgListCum.empty() || (path && heldPath != nullptr); }
+    bool hasWork(bool path = true) const { return hasPending(path) || !pendingJobs.empty(); }
     // ---- 4-state path: a root-ward path (k_path4 plan) is HELD until the next call: if that call is the log-likelihood over the
     // path's last result, both run as one launch (k_path4_lnl); anything else runs the path first, as before
     Plan* heldPath = nullptr;
@@ -243,12 +263,20 @@ struct Instance {
     bool heldPathFresh = false;
     int heldPathDst = -1;                        // the partials buffer the path's last operation writes
     int runHeldPath();
-    int integratePath4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx);
+    int integratePath4(const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx);
     int updatePartialsG(const BeagleOperation* ops, int n, int cumIdx);
     int flushWalkG();
     int runWalkG(const Plan& plan);
+    int checkOperation(const BeagleOperation& b, const std::vector<char>& written, const char*& what) const;
+    std::vector<PathStep> pathSteps;             // recognisePath's result (scratch of buildPath4 / buildPathG)
+    bool recognisePath(const BeagleOperation* ops, int n, int L, bool& forked);
+    Walk4Entry pathEntry(const PathStep& p, uint32_t pbuf, uint32_t tipb, uint32_t mbuf, int scratchRow) const;
+    void pathPlan(Plan& plan, int entries, bool forked);
     bool buildPath4(Plan& plan, const BeagleOperation* ops, int n);
     bool buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl);
+    Walk4Args walk4Args() const;
+    WalkGArgs walkGArgs() const;
+    int prepareCumulative(int idx, bool& fresh);
     void postResultFlag();
     bool scaleOpsIndependentOfPending(const int* idx, int n, int cumIdx) const;
     uint64_t launchClock = 0, syncedClock = 0;   // launches issued / launches known complete (last stream synchronisation)
@@ -261,7 +289,6 @@ struct Instance {
     long flags = 0;
     class Engine64* f64 = nullptr;        // BEAGLE_FLAG_PRECISION_DOUBLE: this object is only the handle, the engine is mbamd_f64.h
     size_t partialsFloats = 0, matrixFloats = 0, eigenDoubles = 0;
-    int path = PATH_AUTO;
 
     std::vector<float*> partials;      // general path: allocated on first use; 4-state path: slices of the arena
     std::vector<uint8_t*> tipStates;   // non-null while the buffer holds compact tip states
@@ -354,6 +381,36 @@ struct Instance {
             (void) hipEventDestroy(ev.second);
         }
         spans.clear();
+        return BEAGLE_SUCCESS;
+    }
+    // the bracket around the partials launches of one list (or of one merged flush): opens the evaluation's span if need be
+    // and, while timing is on, records an event pair around them
+    int launchesBegin(hipEvent_t& ev0, hipEvent_t& ev1)
+    {
+        { int src = spanBegin(); if (src) return src; }
+        if (!timing) return BEAGLE_SUCCESS;
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+        return BEAGLE_SUCCESS;
+    }
+    int launchesEnd(hipEvent_t ev0, hipEvent_t ev1)
+    {
+        if (!timing) return BEAGLE_SUCCESS;
+        HIP_TRY(hipEventRecord(ev1, stream));
+        events.emplace_back(ev0, ev1);
+        return BEAGLE_SUCCESS;
+    }
+    int eventsFold()                 // (stream synchronised by the caller)
+    {
+        for (auto& ev : events) {
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, ev.first, ev.second));
+            timedMs += t;
+            (void) hipEventDestroy(ev.first);
+            (void) hipEventDestroy(ev.second);
+        }
+        events.clear();
         return BEAGLE_SUCCESS;
     }
 
@@ -481,13 +538,18 @@ struct Instance {
     int accumulate4(const int* idx, int n, int cumIdx, int sign);
     int deferredReset = -1;          // a beagleResetScaleFactors not launched yet (level-kernel path), see beagleAccumulateScaleFactors
     int runDeferredReset();
+    int checkIntegrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx, int count);
     int integrate4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
                    const int* cumIdx, int count);
+    int integrateLevels(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
+                        const int* cumIdx, int count);
     int buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, const std::vector<int>& dstIdx, const std::vector<int>& c1Idx,
                      const std::vector<int>& c2Idx);
     int runWalk(const Plan& plan, int32_t* cum);
     int runGeneric(const Plan& plan, int32_t* cum);
-    int planTable(Plan& plan, const std::vector<PartialsOp>& table);
+    Plan* cachedPlan(const int* key, size_t nints, bool& build);
+    int planBuilt(Plan& plan, int rc);
+    int planTable(Plan& plan, const void* table, size_t bytes);
     int timedRun(const Plan& plan, int32_t* cum);
     int flushPending(bool keepPath = false);
     int flushMatrices();
@@ -1119,6 +1181,67 @@ int Instance::getMatrix(int idx, double* out)
     return BEAGLE_SUCCESS;
 }
 
+// The plan cache of all three back ends: the plan compiled from exactly these ints (the operations as submitted; the
+// general-state walk appends its list starts) under the current layout epoch.  A miss (`build`) hands out a new plan or the
+// least recently used one, already keyed: the caller compiles into it and reports the outcome through planBuilt.
+Plan* Instance::cachedPlan(const int* key, size_t nints, bool& build)
+{
+    static_assert(sizeof(BeagleOperation) == 7 * sizeof(int), "BeagleOperation is 7 ints");
+    const uint64_t h = fnv1a(&layoutEpoch, 1, fnv1a(key, nints));
+    build = false;
+    for (Plan* pl : plans)
+        if (pl->hash == h && pl->key.size() == nints + 1 && pl->key[nints] == layoutEpoch &&
+            std::memcmp(pl->key.data(), key, nints * sizeof(int)) == 0) {
+            pl->lastUse = ++planClock;
+            planHits++;
+            return pl;
+        }
+    planMisses++;
+    build = true;
+    Plan* plan;
+    if (const size_t maxPlans = 24; plans.size() < maxPlans) {
+        plan = new Plan();
+        plans.push_back(plan);
+    } else {
+        plan = plans[0];
+        for (Plan* pl : plans) if (pl->lastUse < plan->lastUse) plan = pl;
+    }
+    plan->key.assign(key, key + nints);
+    plan->key.push_back(layoutEpoch);
+    plan->hash = h;
+    plan->lastUse = ++planClock;
+    return plan;
+}
+
+// the outcome of compiling into a plan cachedPlan handed out: a failed build must not be found again
+int Instance::planBuilt(Plan& plan, int rc)
+{
+    if (rc) { plan.hash = 0; plan.key.clear(); }
+    return rc;
+}
+
+// One operation of a list, whichever back end compiles it: index ranges, and children that hold something (`written`: the
+// buffers earlier operations of the same list write).  BEAGLE_SUCCESS, or the error code with its message in `what`.
+int Instance::checkOperation(const BeagleOperation& b, const std::vector<char>& written, const char*& what) const
+{
+    what = "";
+    if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 ||
+        b.child1Partials >= nBuffers || b.child2Partials < 0 || b.child2Partials >= nBuffers) {
+        what = "beagleUpdatePartials: partials index";
+    } else if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices || b.child2TransitionMatrix < 0 ||
+               b.child2TransitionMatrix >= nMatrices) {
+        what = "beagleUpdatePartials: matrix index";
+    } else if ((!written[b.child1Partials] && !tipStates[b.child1Partials] && !valid[b.child1Partials]) ||
+               (!written[b.child2Partials] && !tipStates[b.child2Partials] && !valid[b.child2Partials])) {
+        what = "beagleUpdatePartials: child buffer was never written";
+    } else if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
+        if (b.destinationScaleWrite < 0 || b.destinationScaleWrite >= nScale) what = "beagleUpdatePartials: scale write index";
+    } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
+        if (b.destinationScaleRead < 0 || b.destinationScaleRead >= nScale) what = "beagleUpdatePartials: scale read index";
+    }
+    return what[0] ? BEAGLE_ERROR_OUT_OF_RANGE : BEAGLE_SUCCESS;
+}
+
 // ---------------------------------------------------------------------------------------------
 // beagleUpdatePartials: resolve buffer indices to device pointers, then hand the list to the
 // 4-state tree-walk kernel or to the level-synchronous general kernels.
@@ -1139,104 +1262,61 @@ int Instance::updatePartials(const BeagleOperation* ops, int n, int cumIdx)
         if (rc) return rc;
         cumPtr = scale[cumIdx];
     }
-    // ---- plan cache ------------------------------------------------------------------------
-    static_assert(sizeof(BeagleOperation) == 7 * sizeof(int), "BeagleOperation is 7 ints");
-    const int* raw = reinterpret_cast<const int*>(ops);
-    const size_t nints = (size_t) n * 7;
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < nints; ++i) h = (h ^ (uint64_t) (uint32_t) raw[i]) * 1099511628211ull;
-    h = (h ^ (uint64_t) (uint32_t) layoutEpoch) * 1099511628211ull;
-    for (Plan* pl : plans)
-        if (pl->hash == h && pl->key.size() == nints + 1 && pl->key[nints] == layoutEpoch &&
-            std::memcmp(pl->key.data(), raw, nints * sizeof(int)) == 0) {
-            pl->lastUse = ++planClock;
-            planHits++;
-            return submit(pl, cumIdx, cumPtr);
-        }
-    planMisses++;
+    bool build;
+    Plan* plan = cachedPlan(reinterpret_cast<const int*>(ops), (size_t) n * 7, build);
+    if (!build) return submit(plan, cumIdx, cumPtr);
     if (!mfma || sw.mfmaWhole || sw.noDefer || pending.empty()) {
         // launch the queued transition-matrix jobs now: the kernel runs while the host compiles the list
         int mrc = flushMatrices();
-        if (mrc) return mrc;
+        if (mrc) return planBuilt(*plan, mrc);
     }
     std::vector<PartialsOp> dev(n);
     std::vector<int> dstIdx(n), c1Idx(n), c2Idx(n);
     std::vector<char> written(nBuffers, 0);
-    for (int o = 0; o < n; ++o) {
-        const BeagleOperation& b = ops[o];
-        PartialsOp& d = dev[o];
-        std::memset(&d, 0, sizeof d);
-        if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 ||
-            b.child1Partials >= nBuffers || b.child2Partials < 0 || b.child2Partials >= nBuffers)
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: partials index");
-        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices || b.child2TransitionMatrix < 0 ||
-            b.child2TransitionMatrix >= nMatrices)
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: matrix index");
-        int rc = ensurePartials(b.destinationPartials);
-        if (rc) return rc;
-        d.dst = partials[b.destinationPartials];
-        const int ci[2] = {b.child1Partials, b.child2Partials};
-        const void* cp[2];
-        uint8_t ck[2];
-        for (int s = 0; s < 2; ++s) {
-            if (tipStates[ci[s]] && !written[ci[s]]) {
-                cp[s] = tipStates[ci[s]];
-                ck[s] = CHILD_STATES;
-            } else {
-                if (!valid[ci[s]] && !written[ci[s]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: child buffer was never written");
-                cp[s] = partials[ci[s]];
-                ck[s] = CHILD_PARTIALS;
+    auto resolve = [&]() -> int {
+        for (int o = 0; o < n; ++o) {
+            const BeagleOperation& b = ops[o];
+            PartialsOp& d = dev[o];
+            std::memset(&d, 0, sizeof d);
+            const char* what;
+            int rc = checkOperation(b, written, what);
+            if (rc) return fail(rc, what);
+            rc = ensurePartials(b.destinationPartials);
+            if (rc) return rc;
+            d.dst = partials[b.destinationPartials];
+            const bool tip1 = tipStates[b.child1Partials] && !written[b.child1Partials], tip2 = tipStates[b.child2Partials] && !written[b.child2Partials];
+            d.c1 = tip1 ? (const void*) tipStates[b.child1Partials] : partials[b.child1Partials];
+            d.c2 = tip2 ? (const void*) tipStates[b.child2Partials] : partials[b.child2Partials];
+            d.c1_kind = tip1 ? CHILD_STATES : CHILD_PARTIALS;
+            d.c2_kind = tip2 ? CHILD_STATES : CHILD_PARTIALS;
+            d.m1 = matrixPtr(b.child1TransitionMatrix);
+            d.m2 = matrixPtr(b.child2TransitionMatrix);
+            d.c1_slot = d.c2_slot = d.dst_slot = MBAMD_NO_SLOT;
+            d.scale_mode = b.destinationScaleWrite != BEAGLE_OP_NONE ? SCALE_WRITE : (b.destinationScaleRead != BEAGLE_OP_NONE ? SCALE_READ : SCALE_NONE);
+            if (d.scale_mode != SCALE_NONE) {
+                const int si = d.scale_mode == SCALE_WRITE ? b.destinationScaleWrite : b.destinationScaleRead;
+                rc = ensureScale(si);
+                if (rc) return rc;
+                d.scale = scale[si];
             }
+            dstIdx[o] = b.destinationPartials;
+            c1Idx[o] = b.child1Partials;
+            c2Idx[o] = b.child2Partials;
+            written[b.destinationPartials] = 1;
         }
-        d.c1 = cp[0]; d.c1_kind = ck[0];
-        d.c2 = cp[1]; d.c2_kind = ck[1];
-        d.m1 = matrixPtr(b.child1TransitionMatrix);
-        d.m2 = matrixPtr(b.child2TransitionMatrix);
-        d.c1_slot = d.c2_slot = d.dst_slot = MBAMD_NO_SLOT;
-        d.scale_mode = SCALE_NONE;
-        if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
-            if (b.destinationScaleWrite < 0 || b.destinationScaleWrite >= nScale)
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: scale write index");
-            rc = ensureScale(b.destinationScaleWrite);
-            if (rc) return rc;
-            d.scale = scale[b.destinationScaleWrite];
-            d.scale_mode = SCALE_WRITE;
-        } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-            if (b.destinationScaleRead < 0 || b.destinationScaleRead >= nScale)
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: scale read index");
-            rc = ensureScale(b.destinationScaleRead);
-            if (rc) return rc;
-            d.scale = scale[b.destinationScaleRead];
-            d.scale_mode = SCALE_READ;
-        }
-        dstIdx[o] = b.destinationPartials;
-        c1Idx[o] = b.child1Partials;
-        c2Idx[o] = b.child2Partials;
-        written[b.destinationPartials] = 1;
-    }
+        return BEAGLE_SUCCESS;
+    };
+    int rc = resolve();
+    if (rc) return planBuilt(*plan, rc);
     for (int o = 0; o < n; ++o) valid[dstIdx[o]] = 1;
-    // ---- compile the list into a plan (evicting the least recently used one) ----------------------
-    Plan* plan;
-    const size_t maxPlans = 24;
-    if (plans.size() < maxPlans) {
-        plan = new Plan();
-        plans.push_back(plan);
-    } else {
-        plan = plans[0];
-        for (Plan* pl : plans) if (pl->lastUse < plan->lastUse) plan = pl;
-        for (auto& pp : pending)
-            if (pp.first == plan) { int frc = flushPending(); if (frc) return frc; break; }
-    }
-    plan->key.assign(raw, raw + nints);
-    plan->key.push_back(layoutEpoch);
-    plan->hash = h;
-    plan->lastUse = ++planClock;
-    int rc;
+    // ---- compile the list into the plan (which may be an evicted one that is still queued: that queue runs first) -----------
+    for (auto& pp : pending)
+        if (pp.first == plan) { int frc = flushPending(); if (frc) return planBuilt(*plan, frc); break; }
     {
         StatTimer st_(ST_PLAN);
         rc = buildGeneric(*plan, dev, dstIdx, c1Idx, c2Idx);
     }
-    if (rc) { plan->hash = 0; plan->key.clear(); return rc; }
+    if (rc) return planBuilt(*plan, rc);
     plan->bufsRead.assign(c1Idx.begin(), c1Idx.end());
     plan->bufsRead.insert(plan->bufsRead.end(), c2Idx.begin(), c2Idx.end());
     plan->bufsWritten.assign(dstIdx.begin(), dstIdx.end());
@@ -1320,12 +1400,7 @@ int Instance::flushPending(bool keepPath)
         return BEAGLE_SUCCESS;
     }
     hipEvent_t ev0{}, ev1{};
-    { int src = spanBegin(); if (src) return src; }
-    if (timing) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
+    { int brc = launchesBegin(ev0, ev1); if (brc) return brc; }
     size_t maxLevels = 0;
     bool allNarrow = true;
     for (auto& w : work) {
@@ -1423,17 +1498,12 @@ int Instance::flushPending(bool keepPath)
         }
     }
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        events.emplace_back(ev0, ev1);
-    }
-    return BEAGLE_SUCCESS;
+    return launchesEnd(ev0, ev1);
 }
 
-// upload a freshly built table into the plan's own device buffer
-int Instance::planTable(Plan& plan, const std::vector<PartialsOp>& table)
+// upload a freshly built table (level kernels: PartialsOp; tree walks: Walk4Entry programs) into the plan's own device buffer
+int Instance::planTable(Plan& plan, const void* table, size_t bytes)
 {
-    const size_t bytes = table.size() * sizeof(PartialsOp);
     const bool inFlight = plan.lastLaunch > syncedClock;     // the old table may still be read by a running kernel
     if (bytes > plan.cap) {
         if (inFlight) { HIP_TRY(hipStreamSynchronize(stream)); syncedClock = launchClock; }
@@ -1446,34 +1516,21 @@ int Instance::planTable(Plan& plan, const std::vector<PartialsOp>& table)
         HIP_TRY(hipStreamSynchronize(stream));
         syncedClock = launchClock;
     }
-    return upload(plan.d_table, table.data(), bytes);
+    return upload(plan.d_table, table, bytes);
 }
 
 int Instance::timedRun(const Plan& plan, int32_t* cum)
 {
     const_cast<Plan&>(plan).lastLaunch = ++launchClock;
     hipEvent_t ev0{}, ev1{};
-    { int src = spanBegin(); if (src) return src; }
-    if (timing) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
+    { int brc = launchesBegin(ev0, ev1); if (brc) return brc; }
     const int rc = s4 ? runWalk(plan, cum) : (wg ? runWalkG(plan) : runGeneric(plan, cum));
-    if (timing) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        events.emplace_back(ev0, ev1);
-        if (events.size() > 4096) {               // a client that never asks: fold the finished ones into the running total
-            HIP_TRY(hipStreamSynchronize(stream));
-            spanFold();
-            for (auto& ev : events) {
-                float t = 0.0f;
-                if (hipEventElapsedTime(&t, ev.first, ev.second) == hipSuccess) timedMs += t;
-                (void) hipEventDestroy(ev.first);
-                (void) hipEventDestroy(ev.second);
-            }
-            events.clear();
-        }
+    { int erc = launchesEnd(ev0, ev1); if (erc) return erc; }
+    if (events.size() > 4096) {                   // a client that never asks: fold the finished ones into the running total
+        HIP_TRY(hipStreamSynchronize(stream));
+        spanFold();
+        int frc = eventsFold();
+        if (frc) return frc;
     }
     return rc;
 }
@@ -1498,61 +1555,38 @@ int Instance::ensureWide(int idx)
     return BEAGLE_SUCCESS;
 }
 
+// A cumulative buffer a kernel is about to add to.  One that was never written (freshly reset: the rescale-everything pass, or
+// MrBayes-style Reset + Accumulate of every node) is only allocated and marked cumulative -- `fresh`: the kernel STORES its sums,
+// no zero-fill launch; any other is brought into the wide form.
+int Instance::prepareCumulative(int idx, bool& fresh)
+{
+    fresh = scaleState[idx] == 0;
+    if (!fresh) return ensureWide(idx);
+    if (!wideScale[idx]) HIP_TRY(hipMalloc(&wideScale[idx], (size_t) K * Ppad * sizeof(int32_t)));
+    scaleState[idx] = 2;
+    return BEAGLE_SUCCESS;
+}
+
 int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumIdx)
 {
     if (heldPath) { int prc = runHeldPath(); if (prc) return prc; }      // (a list behind a held path: the path runs first)
     int32_t* cumPtr = nullptr;
     walkCumFresh = false;
     if (cumIdx != BEAGLE_OP_NONE) {
-        if (scaleState[cumIdx] == 0) {
-            // a freshly reset cumulative buffer (the rescale-everything pass): the kernel STORES its sums, no zero-fill launch
-            if (!wideScale[cumIdx]) HIP_TRY(hipMalloc(&wideScale[cumIdx], (size_t) K * Ppad * sizeof(int32_t)));
-            scaleState[cumIdx] = 2;
-            walkCumFresh = true;
-        } else {
-            int rc = ensureWide(cumIdx);
-            if (rc) return rc;
-        }
+        int rc = prepareCumulative(cumIdx, walkCumFresh);
+        if (rc) return rc;
         cumPtr = wideScale[cumIdx];
     }
-    // ---- plan cache ------------------------------------------------------------------------
-    const int* raw = reinterpret_cast<const int*>(ops);
-    const size_t nints = (size_t) n * 7;
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < nints; ++i) h = (h ^ (uint64_t) (uint32_t) raw[i]) * 1099511628211ull;
-    h = (h ^ (uint64_t) (uint32_t) layoutEpoch) * 1099511628211ull;
-    Plan* plan = nullptr;
-    for (Plan* pl : plans)
-        if (pl->hash == h && pl->key.size() == nints + 1 && pl->key[nints] == layoutEpoch &&
-            std::memcmp(pl->key.data(), raw, nints * sizeof(int)) == 0) {
-            pl->lastUse = ++planClock;
-            planHits++;
-            plan = pl;
-            break;
-        }
-    if (!plan) {
-        planMisses++;
-        int mrc = flushMatrices();               // the matrix kernel runs while the host compiles the list
-        if (mrc) return mrc;
-        const size_t maxPlans = 24;
-        if (plans.size() < maxPlans) {
-            plan = new Plan();
-            plans.push_back(plan);
-        } else {
-            plan = plans[0];
-            for (Plan* pl : plans) if (pl->lastUse < plan->lastUse) plan = pl;
-        }
-        plan->key.assign(raw, raw + nints);
-        plan->key.push_back(layoutEpoch);
-        plan->hash = h;
-        plan->lastUse = ++planClock;
-        int rc;
-        {
+    bool build;
+    Plan* plan = cachedPlan(reinterpret_cast<const int*>(ops), (size_t) n * 7, build);
+    if (build) {
+        int rc = flushMatrices();                // the matrix kernel runs while the host compiles the list
+        if (rc == BEAGLE_SUCCESS) {
             StatTimer st_(ST_PLAN);
             plan->path = plan->forked = false;
             rc = buildPath4(*plan, ops, n) ? BEAGLE_SUCCESS : buildWalk(*plan, ops, n);
         }
-        if (rc) { plan->hash = 0; plan->key.clear(); return rc; }
+        if (planBuilt(*plan, rc)) return rc;
     }
     // bookkeeping the list implies, whether compiled now or before: destinations valid, exponent buffers in node form
     for (int o = 0; o < n; ++o) {
@@ -1613,8 +1647,7 @@ int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int
             }
             for (size_t o = 0; o < seg.size(); ++o) writer[seg[o].dst] = -1;
         }
-        uint64_t kh = 1469598103934665603ull;
-        for (int v : key) kh = (kh ^ (uint64_t) (uint32_t) v) * 1099511628211ull;
+        const uint64_t kh = fnv1a(key.data(), key.size());
         auto it = w4templates.find(kh);
         if (it == w4templates.end() || it->second.key != key) {
             scheduleMisses++;
@@ -1728,32 +1761,18 @@ int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int
     };
     for (int o = 0; o < n; ++o) {
         const BeagleOperation& b = ops[o];
-        if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 ||
-            b.child1Partials >= nBuffers || b.child2Partials < 0 || b.child2Partials >= nBuffers)
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: partials index");
-        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices || b.child2TransitionMatrix < 0 ||
-            b.child2TransitionMatrix >= nMatrices)
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: matrix index");
+        const char* what;
+        if (const int crc = checkOperation(b, written, what)) return fail(crc, what);
         Walk4Op w;
         w.dst = b.destinationPartials;
         w.c1 = b.child1Partials; w.c2 = b.child2Partials;
         w.m1 = b.child1TransitionMatrix; w.m2 = b.child2TransitionMatrix;
-        const int ci[2] = {w.c1, w.c2};
-        uint8_t tip[2];
-        for (int c = 0; c < 2; ++c) {
-            tip[c] = (tipStates[ci[c]] && !written[ci[c]]) ? 1 : 0;
-            if (!tip[c] && !valid[ci[c]] && !written[ci[c]])
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: child buffer was never written");
-        }
+        const uint8_t tip[2] = {(uint8_t) (tipStates[w.c1] && !written[w.c1]), (uint8_t) (tipStates[w.c2] && !written[w.c2])};
         w.tip1 = tip[0]; w.tip2 = tip[1];
         w.scaleWrite = w.scaleRead = -1;
         if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
-            if (b.destinationScaleWrite < 0 || b.destinationScaleWrite >= nScale)
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: scale write index");
             w.scaleWrite = b.destinationScaleWrite;
         } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-            if (b.destinationScaleRead < 0 || b.destinationScaleRead >= nScale)
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartials: scale read index");
             if (scaleState[b.destinationScaleRead] == 2 && !segScale[b.destinationScaleRead])
                 return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePartials: destinationScaleRead names a cumulative buffer");
             w.scaleRead = b.destinationScaleRead;
@@ -1788,20 +1807,7 @@ int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int
         plan.inlineProg = w4table;
         return BEAGLE_SUCCESS;
     }
-    // upload the programs into the plan's device buffer
-    const size_t bytes = w4table.size() * sizeof(Walk4Entry);
-    const bool inFlight = plan.lastLaunch > syncedClock;
-    if (bytes > plan.cap || inFlight) {
-        if (inFlight) { HIP_TRY(hipStreamSynchronize(stream)); syncedClock = launchClock; }
-        if (bytes > plan.cap) {
-            if (plan.d_table) HIP_TRY(hipFree(plan.d_table));
-            plan.d_table = nullptr;
-            plan.cap = 0;
-            HIP_TRY(hipMalloc(&plan.d_table, bytes + bytes / 2));
-            plan.cap = bytes + bytes / 2;
-        }
-    }
-    return upload(plan.d_table, w4table.data(), bytes);
+    return planTable(plan, w4table.data(), w4table.size() * sizeof(Walk4Entry));
 }
 
 // host data -> the pinned ring -> a device buffer, by a launch of ours on the instance's stream
@@ -1821,98 +1827,145 @@ int Instance::ringCopy(void* dst, const void* src, size_t bytes)
     return BEAGLE_SUCCESS;
 }
 
-// A root-ward path (the list of a move that dirtied one branch) as k_path4's entries: operation i has the result of operation i - 1
-// as one child; its other child -- and both children of operation 0 -- are compact tips or buffers the list does not write; no buffer
-// or exponent buffer is written twice or read after it is written.  Round 6: also FORKED paths (the list of a topology move: root-ward
-// paths that join, in post-order) -- an operation that does not read its predecessor's result begins a new ARM (the predecessor's
-// result is saved), an operation whose other child is the saved result JOINS the arms; one saved result at a time.  Anything else
-// (false) is compiled by buildWalk.
+// A root-ward path (the list of a move that dirtied one branch): operation i has the result of operation i - 1 as one child; its
+// other child -- and both children of operation 0 -- are compact tips or buffers the list does not write; no buffer or exponent
+// buffer is written twice or read after it is written.  Round 6: also FORKED paths (the list of a topology move: root-ward paths
+// that join, in post-order) -- an operation that does not read its predecessor's result begins a new ARM (the predecessor's
+// result is saved), an operation whose other child is the saved result JOINS the arms; one saved result at a time.
+// ops[0, n) are n / L lists of L operations (one list; or the mutually independent lists of the eigen-system parts of a codon
+// model), every one such a path, and the hazard rules hold over all of them.  true: pathSteps describes the operations.  Anything
+// else (false) is compiled by buildWalk, which also reports what is wrong with an operation.
+bool Instance::recognisePath(const BeagleOperation* ops, int n, int L, bool& forked)
+{
+    std::vector<char>& written = w4written;          // buffers earlier operations write; after this loop: any operation
+    written.assign((size_t) nBuffers, 0);
+    std::vector<char>& named = w4segScale;           // how many scale fields of the operations name an exponent buffer (3 = more)
+    named.assign(scale.size() + 1, 0);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        const char* what;
+        if (checkOperation(b, written, what) != BEAGLE_SUCCESS) return false;
+        if (tipStates[b.destinationPartials] || written[b.destinationPartials]) return false;
+        written[b.destinationPartials] = 1;
+        for (int f : {b.destinationScaleWrite, b.destinationScaleRead})
+            if (f >= 0 && f < nScale && named[f] < 3) ++named[f];
+    }
+    pathSteps.resize((size_t) n);
+    forked = false;
+    int saved = -1;                              // buffer of the saved result (an arm that waits for its join), or -1
+    int armStart = 0, arms = 0;
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        PathStep& p = pathSteps[(size_t) o];
+        const bool first = o % L == 0;
+        const int prev = first ? -1 : ops[o - 1].destinationPartials;
+        const bool one = !first && b.child1Partials == prev, two = !first && b.child2Partials == prev;
+        if (one && two) return false;
+        p.start = !one && !two;
+        p.join = false;
+        p.arm = 0;
+        p.dst = b.destinationPartials;
+        p.chain = two ? b.child2Partials : b.child1Partials; p.sib = two ? b.child1Partials : b.child2Partials;
+        p.mchain = two ? b.child2TransitionMatrix : b.child1TransitionMatrix; p.msib = two ? b.child1TransitionMatrix : b.child2TransitionMatrix;
+        if (p.start) {
+            if (!first) {
+                if (saved >= 0) return false;                                 // (two results waiting: not the path kernels' shape)
+                saved = prev;
+                pathSteps[(size_t) armStart].arm = o - armStart;
+            }
+            armStart = o;
+            ++arms;
+        } else if (saved >= 0 && p.sib == saved) {
+            p.join = true;
+            saved = -1;
+        }
+        // what comes from outside must not be written anywhere in the lists (before: a second dependency; after: a hazard)
+        if ((!p.join && written[p.sib]) || (p.start && written[p.chain])) return false;
+        p.chainTip = p.start && tipStates[p.chain] != nullptr;
+        p.sibTip = !p.join && tipStates[p.sib] != nullptr;
+        p.scaleMode = SCALE_NONE;
+        p.scaleIdx = -1;
+        if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
+            // the operation's own: nobody else's scale fields name it
+            if (named[b.destinationScaleWrite] != 1 + (b.destinationScaleRead == b.destinationScaleWrite ? 1 : 0)) return false;
+            p.scaleMode = SCALE_WRITE;
+            p.scaleIdx = b.destinationScaleWrite;
+        } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
+            if (scaleState[b.destinationScaleRead] == 2) return false;
+            p.scaleMode = SCALE_READ;
+            p.scaleIdx = b.destinationScaleRead;
+        }
+        if (o % L == L - 1) {                    // the end of a list
+            if (saved >= 0) return false;        // (an arm nobody joins: two trees in one list)
+            pathSteps[(size_t) armStart].arm = o + 1 - armStart;
+            forked = forked || arms > 1;
+            arms = 0;
+        }
+    }
+    return true;
+}
+
+// A step as an entry of k_path4 / k_pathg, offsets in the caller's units: a partials buffer, a compact tip, a matrix buffer, and
+// the scratch exponent row an operation that records no exponents stores to.
+Walk4Entry Instance::pathEntry(const PathStep& p, uint32_t pbuf, uint32_t tipb, uint32_t mbuf, int scratchRow) const
+{
+    const uint32_t ebuf = (uint32_t) K * 64u;
+    Walk4Entry e;
+    std::memset(&e, 0, sizeof e);
+    uint32_t flags = 0;
+    e.dst = (uint32_t) p.dst * pbuf;
+    if (p.start) {
+        flags |= MBAMD_P4_START;
+        if (p.chainTip) { e.c1 = (uint32_t) p.chain * tipb; flags |= MBAMD_W4_TIP1; }
+        else e.c1 = (uint32_t) p.chain * pbuf;
+    }
+    if (p.join) flags |= MBAMD_P4_JOIN;
+    else if (p.sibTip) { e.c2 = (uint32_t) p.sib * tipb; flags |= MBAMD_W4_TIP2; }
+    else e.c2 = (uint32_t) p.sib * pbuf;
+    e.m1 = (uint32_t) p.mchain * mbuf;
+    e.m2 = (uint32_t) p.msib * mbuf;
+    e.ewrite = (uint32_t) scratchRow * ebuf;
+    e.eread = (uint32_t) scale.size() * ebuf;
+    if (p.scaleMode == SCALE_WRITE) e.ewrite = (uint32_t) p.scaleIdx * ebuf;
+    else if (p.scaleMode == SCALE_READ) e.eread = (uint32_t) p.scaleIdx * ebuf;
+    e.ctl = flags | ((uint32_t) p.scaleMode << 8);
+    return e;
+}
+
+// a path plan's geometry: one single-wave program of `entries` per list, no LDS slots, no read-ahead tail
+void Instance::pathPlan(Plan& plan, int entries, bool forked)
+{
+    plan.forked = forked;
+    plan.segments.clear();
+    Plan::Segment sg;
+    sg.first = 0; sg.W = 1; sg.entries = entries; sg.nslots = 0; sg.tail = 0;
+    plan.segments.push_back(sg);
+    lastWalkW = 1; lastWalkSlots = 0; lastWalkEntries = entries; lastWalkPhases = 1;
+}
+
+// One list as k_path4's entries (mbamd_walk4.h): partials buffers in KiB of the buffer-major arena, 32 bytes of state bitplanes
+// per tip, matrices [K][4][4]; the first entry of an arm carries the arm's length.
 bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
 {
     if (sw.noPath4 || n < 1 || n > MBAMD_W4_INLINE) return false;
-    const int scratchScale = (int) scale.size();
-    const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
-    std::vector<Walk4Entry>& prog = plan.inlineProg;
-    prog.assign((size_t) n, Walk4Entry());
-    auto inList = [&](int buf, int upto) { for (int q = 0; q < upto; ++q) if (ops[q].destinationPartials == buf) return true; return false; };
-    int saved = -1;                              // buffer of the saved result (an arm that waits for its join), or -1
-    int armStart = 0, arms = 0;
+    bool forked;
+    if (!recognisePath(ops, n, n, forked) || (forked && sw.noForkPath)) return false;
+    const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), mbuf = (uint32_t) K * 64u;
+    plan.inlineProg.resize((size_t) n);
     for (int i = 0; i < n; ++i) {
-        const BeagleOperation& b = ops[i];
-        if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 || b.child1Partials >= nBuffers ||
-            b.child2Partials < 0 || b.child2Partials >= nBuffers || b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
-            b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices) return false;      // (buildWalk reports it)
-        if (tipStates[b.destinationPartials] || inList(b.destinationPartials, i)) return false;
-        int chain, sib, mchain, msib;
-        const int prev = i == 0 ? -1 : ops[i - 1].destinationPartials;
-        const bool one = i > 0 && b.child1Partials == prev, two = i > 0 && b.child2Partials == prev;
-        if (one && two) return false;
-        const bool start = !one && !two;
-        bool join = false;
-        if (start) {
-            if (i > 0) {
-                if (sw.noForkPath || saved >= 0) return false;                // (two results waiting: not this kernel's shape)
-                saved = prev;
-                prog[(size_t) armStart].ctl |= (uint32_t) (i - armStart) << 16;
-                armStart = i;
-            }
-            ++arms;
-            chain = b.child1Partials; sib = b.child2Partials; mchain = b.child1TransitionMatrix; msib = b.child2TransitionMatrix;
-        } else {
-            chain = one ? b.child1Partials : b.child2Partials; sib = one ? b.child2Partials : b.child1Partials;
-            mchain = one ? b.child1TransitionMatrix : b.child2TransitionMatrix; msib = one ? b.child2TransitionMatrix : b.child1TransitionMatrix;
-            if (saved >= 0 && sib == saved) { join = true; saved = -1; }
-        }
-        // what comes from outside must not be written anywhere in the list (before: a second dependency; after: a hazard)
-        for (int ext : {join ? -1 : sib, start ? chain : -1})
-            if (ext >= 0) {
-                if (inList(ext, n)) return false;
-                if (!tipStates[ext] && !valid[ext]) return false;
-            }
-        Walk4Entry& e = prog[(size_t) i];
-        std::memset(&e, 0, sizeof e);
-        uint32_t flags = 0, mode = SCALE_NONE;
-        e.dst = (uint32_t) b.destinationPartials * pbuf;
-        if (start) {
-            flags |= MBAMD_P4_START;
-            if (tipStates[chain]) { e.c1 = (uint32_t) chain * 32u; flags |= MBAMD_W4_TIP1; }
-            else e.c1 = (uint32_t) chain * pbuf;
-        }
-        if (join) flags |= MBAMD_P4_JOIN;
-        else if (tipStates[sib]) { e.c2 = (uint32_t) sib * 32u; flags |= MBAMD_W4_TIP2; }
-        else e.c2 = (uint32_t) sib * pbuf;
-        e.m1 = (uint32_t) mchain * mbuf;
-        e.m2 = (uint32_t) msib * mbuf;
-        e.ewrite = e.eread = (uint32_t) scratchScale * ebuf;
-        if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
-            if (b.destinationScaleWrite < 0 || b.destinationScaleWrite >= nScale) return false;
-            for (int q = 0; q < n; ++q)
-                if (q != i && (ops[q].destinationScaleWrite == b.destinationScaleWrite || ops[q].destinationScaleRead == b.destinationScaleWrite)) return false;
-            mode = SCALE_WRITE;
-            e.ewrite = (uint32_t) b.destinationScaleWrite * ebuf;
-        } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-            if (b.destinationScaleRead < 0 || b.destinationScaleRead >= nScale || scaleState[b.destinationScaleRead] == 2) return false;
-            mode = SCALE_READ;
-            e.eread = (uint32_t) b.destinationScaleRead * ebuf;
-        }
-        e.ctl = flags | (mode << 8);
+        const PathStep& p = pathSteps[(size_t) i];
+        plan.inlineProg[(size_t) i] = pathEntry(p, pbuf, 32u, mbuf, (int) scale.size());
+        plan.inlineProg[(size_t) i].ctl |= (uint32_t) p.arm << 16;
     }
-    if (saved >= 0) return false;                // (an arm nobody joins: two trees in one list)
-    prog[(size_t) armStart].ctl |= (uint32_t) (n - armStart) << 16;
-    plan.forked = arms > 1;
     plan.path = true;
-    plan.segments.clear();
-    Plan::Segment sg;
-    sg.first = 0; sg.W = 1; sg.entries = n; sg.nslots = 0; sg.tail = 0;
-    plan.segments.push_back(sg);
-    lastWalkW = 1; lastWalkSlots = 0; lastWalkEntries = n; lastWalkPhases = 1;
+    pathPlan(plan, n, forked);
     return true;
 }
 
 // The same for the 20/61-state walk (k_pathg, mbamd_pathg_kernel.h): `nl` mutually independent lists (the eigen-system parts of a
-// codon model; one for a protein model), each a root-ward path -- or root-ward paths that join, arms as in buildPath4, at the same
-// positions in every list --, all of the same length.  Entries [list][operation] in the tile
-// arena's units (byte offsets of a buffer inside a tile, tip states at 32 bytes per buffer, matrix buffers in bytes).
+// codon model; one for a protein model), each a root-ward path -- or root-ward paths that join, at the same positions in every
+// list --, all of the same length.  Entries [list][operation] in the tile arena's units (byte offsets of a buffer inside a tile,
+// tip states at 32 bytes per buffer, matrix buffers in bytes); an entry carries its list's index.
 static inline bool pathg_compiled(int S) { return S == 20 || (S >= 60 && S <= 63); }
 bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl)
 {
@@ -1920,114 +1973,52 @@ bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, const s
     const int L = n / nl;
     if (L < 2 || (size_t) n > (size_t) MBAMD_W4_INLINE) return false;      // (a single operation gains nothing; the program travels in the kernel arguments)
     for (int q = 0; q < nl; ++q) if (starts[(size_t) q] != q * L) return false;
-    const int scratchScale = (int) scale.size();
-    const uint32_t slotb = wg_block_bytes(S), pbuf = (uint32_t) K * slotb, ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) (matrixFloats * 4);
-    auto writtenIn = [&](int buf, int lo, int hi) { for (int o = lo; o < hi; ++o) if (ops[o].destinationPartials == buf) return true; return false; };
-    std::vector<Walk4Entry>& prog = plan.inlineProg;
-    prog.assign((size_t) n, Walk4Entry());
-    int arms = 1;
-    for (int q = 0; q < nl; ++q) {
-        const int lo = q * L;
-        int saved = -1, armsHere = 0;                // buffer of the saved result (an arm that waits for its join), or -1
-        for (int i = 0; i < L; ++i) {
-            const BeagleOperation& b = ops[lo + i];
-            if (b.destinationPartials < 0 || b.destinationPartials >= nBuffers || b.child1Partials < 0 || b.child1Partials >= nBuffers ||
-                b.child2Partials < 0 || b.child2Partials >= nBuffers || b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
-                b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices) return false;      // (buildWalk reports it)
-            if (tipStates[b.destinationPartials] || writtenIn(b.destinationPartials, 0, lo + i)) return false;
-            int chain, sib, mchain, msib;
-            const int prev = i == 0 ? -1 : ops[lo + i - 1].destinationPartials;
-            const bool one = i > 0 && b.child1Partials == prev, two = i > 0 && b.child2Partials == prev;
-            if (one && two) return false;
-            const bool start = !one && !two;
-            bool join = false;
-            if (start) {
-                // FORKED paths, as buildPath4's: an operation that does not read its predecessor's result begins a new arm and the
-                // predecessor's result is saved; one saved result at a time
-                if (i > 0) {
-                    if (sw.noForkPath || saved >= 0) return false;
-                    saved = prev;
-                }
-                ++armsHere;
-                chain = b.child1Partials; sib = b.child2Partials; mchain = b.child1TransitionMatrix; msib = b.child2TransitionMatrix;
-            } else {
-                chain = one ? b.child1Partials : b.child2Partials; sib = one ? b.child2Partials : b.child1Partials;
-                mchain = one ? b.child1TransitionMatrix : b.child2TransitionMatrix; msib = one ? b.child2TransitionMatrix : b.child1TransitionMatrix;
-                if (saved >= 0 && sib == saved) { join = true; saved = -1; }              // ... an operation whose other child it is joins the arms
-            }
-            for (int ext : {join ? -1 : sib, start ? chain : -1})
-                if (ext >= 0) {
-                    if (writtenIn(ext, 0, n)) return false;                // (nothing any of the lists writes)
-                    if (!tipStates[ext] && !valid[ext]) return false;
-                }
-            Walk4Entry& e = prog[(size_t) (lo + i)];
-            std::memset(&e, 0, sizeof e);
-            uint32_t flags = 0, mode = SCALE_NONE;
-            e.dst = (uint32_t) b.destinationPartials * pbuf;
-            if (start) {
-                flags |= MBAMD_P4_START;
-                if (tipStates[chain]) { e.c1 = (uint32_t) chain * (uint32_t) MBAMD_WG_TW; flags |= MBAMD_W4_TIP1; }
-                else e.c1 = (uint32_t) chain * pbuf;
-            }
-            if (join) flags |= MBAMD_P4_JOIN;
-            else if (tipStates[sib]) { e.c2 = (uint32_t) sib * (uint32_t) MBAMD_WG_TW; flags |= MBAMD_W4_TIP2; }
-            else e.c2 = (uint32_t) sib * pbuf;
-            // every list the same arms: the workgroups of one launch run the same program shape
-            if (q > 0 && ((prog[(size_t) i].ctl ^ flags) & (MBAMD_P4_START | MBAMD_P4_JOIN)) != 0) return false;
-            e.m1 = (uint32_t) mchain * mbuf;
-            e.m2 = (uint32_t) msib * mbuf;
-            e.ewrite = e.eread = (uint32_t) scratchScale * ebuf;
-            e.ewrite = (uint32_t) (scratchScale + i % MBAMD_WG_SCRATCH_ROWS) * ebuf;      // (a different scratch row for neighbouring entries, see the arena)
-            if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
-                if (b.destinationScaleWrite < 0 || b.destinationScaleWrite >= nScale) return false;
-                for (int o = 0; o < n; ++o)
-                    if (o != lo + i && (ops[o].destinationScaleWrite == b.destinationScaleWrite || ops[o].destinationScaleRead == b.destinationScaleWrite)) return false;
-                mode = SCALE_WRITE;
-                e.ewrite = (uint32_t) b.destinationScaleWrite * ebuf;
-            } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-                if (b.destinationScaleRead < 0 || b.destinationScaleRead >= nScale || scaleState[b.destinationScaleRead] == 2) return false;
-                mode = SCALE_READ;
-                e.eread = (uint32_t) b.destinationScaleRead * ebuf;
-            }
-            e.ctl = flags | (mode << 8) | ((uint32_t) q << 10);
-        }
-        if (saved >= 0) return false;                // (an arm nobody joins: two trees in one list)
-        arms = armsHere;
+    bool forked;
+    if (!recognisePath(ops, n, L, forked) || (forked && sw.noForkPath)) return false;
+    // every list the same arms: the workgroups of one launch run the same program shape
+    for (int o = L; o < n; ++o)
+        if (pathSteps[(size_t) o].start != pathSteps[(size_t) (o % L)].start || pathSteps[(size_t) o].join != pathSteps[(size_t) (o % L)].join) return false;
+    const uint32_t pbuf = (uint32_t) K * wg_block_bytes(S), mbuf = (uint32_t) (matrixFloats * 4);
+    plan.inlineProg.resize((size_t) n);
+    for (int o = 0; o < n; ++o) {
+        // (a different scratch row for neighbouring entries, see the arena)
+        plan.inlineProg[(size_t) o] = pathEntry(pathSteps[(size_t) o], pbuf, (uint32_t) MBAMD_WG_TW, mbuf, (int) scale.size() + (o % L) % MBAMD_WG_SCRATCH_ROWS);
+        plan.inlineProg[(size_t) o].ctl |= (uint32_t) (o / L) << 10;
     }
-    if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths%s (k_pathg)\n", nl, L, arms > 1 ? " that join" : "");
+    if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths%s (k_pathg)\n", nl, L, forked ? " that join" : "");
     plan.pathG = true;
-    plan.forked = arms > 1;
     plan.lists = nl;
-    plan.segments.clear();
-    Plan::Segment sg;
-    sg.first = 0; sg.W = 1; sg.entries = L; sg.nslots = 0; sg.tail = 0;
-    plan.segments.push_back(sg);
-    lastWalkW = 1; lastWalkSlots = 0; lastWalkEntries = L; lastWalkPhases = 1;
+    pathPlan(plan, L, forked);
     return true;
+}
+
+// the instance's side of a 4-state kernel's arguments; the call site adds program, geometry and cumulative buffer
+Walk4Args Instance::walk4Args() const
+{
+    Walk4Args a{};
+    a.partials = reinterpret_cast<f4*>(arenaPartials);
+    a.pstride = geom.pstride;
+    a.tips = arenaTips;
+    a.tstride = geom.tstride;
+    a.exps = arenaExp;
+    a.estride = estride;
+    a.matrices = matrices;
+    a.K = K;
+    a.Ppad = Ppad;
+    a.nblocks = Ppad / 64;
+    return a;
 }
 
 int Instance::runWalk(const Plan& plan, int32_t* cum)
 {
+    Walk4ArgsInline ai;
+    Walk4Args& a = ai.a;
+    a = walk4Args();
+    a.cum = cum;
+    if (!plan.inlineProg.empty()) std::memcpy(ai.inl, plan.inlineProg.data(), plan.inlineProg.size() * sizeof(Walk4Entry));
     if (plan.path) {
-        Walk4ArgsInline ai;
-        Walk4Args& a = ai.a;
-        a.prog = nullptr;
         a.entries = (int) plan.inlineProg.size();
-        a.nslots = 0;
-        a.partials = reinterpret_cast<f4*>(arenaPartials);
-        a.pstride = geom.pstride;
-        a.tips = arenaTips;
-        a.tstride = geom.tstride;
-        a.exps = arenaExp;
-        a.estride = estride;
-        a.matrices = matrices;
-        a.cum = cum;
         a.cumFresh = walkCumFresh ? 1 : 0;
-        a.K = K;
-        a.Ppad = Ppad;
-        a.nblocks = Ppad / 64;
-        a.tail = 0;
-        std::memcpy(ai.inl, plan.inlineProg.data(), plan.inlineProg.size() * sizeof(Walk4Entry));
         auto kernel = k_path4<Walk4ArgsInline>;
         MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, path4_lds_bytes((int) plan.inlineProg.size()), stream, ai);    // (lanes exchange through LDS: the emulation runs them as fibers)
         HIP_TRY(hipGetLastError());
@@ -2035,31 +2026,15 @@ int Instance::runWalk(const Plan& plan, int32_t* cum)
         return BEAGLE_SUCCESS;
     }
     for (const Plan::Segment& sg : plan.segments) {
-        Walk4Args a;
-        a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
         a.entries = sg.entries;
         a.nslots = sg.nslots;
-        a.partials = reinterpret_cast<f4*>(arenaPartials);
-        a.pstride = geom.pstride;
-        a.tips = arenaTips;
-        a.tstride = geom.tstride;
-        a.exps = arenaExp;
-        a.estride = estride;
-        a.matrices = matrices;
-        a.cum = cum;
         a.cumFresh = (walkCumFresh && &sg == &plan.segments.front()) ? 1 : 0;
-        a.K = K;
-        a.Ppad = Ppad;
-        a.nblocks = Ppad / 64;
         a.tail = sg.tail;
         if (!plan.inlineProg.empty()) {
-            Walk4ArgsInline ai;
-            ai.a = a;
-            ai.a.prog = nullptr;
-            std::memcpy(ai.inl, plan.inlineProg.data(), plan.inlineProg.size() * sizeof(Walk4Entry));
             auto kernel = k_walk4_t<Walk4ArgsInline>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_lds_bytes(sg.W, sg.nslots), stream, ai);
         } else {
+            a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
             auto kernel = k_walk4_t<Walk4Args>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_lds_bytes(sg.W, sg.nslots), stream, a);
         }
@@ -2117,10 +2092,9 @@ int Instance::flushWalkG()
     std::vector<int> listOf(n, 0);
     for (int q = 0; q < nl; ++q)
         for (int o = starts[q]; o < (q + 1 < nl ? starts[q + 1] : n); ++o) listOf[o] = q;
-    // ---- plan cache key: the operations as submitted, the list boundaries, the layout epoch ------------------------------
+    // ---- plan cache key: the operations as submitted and the list boundaries ---------------------------------------------
     std::vector<int> key(reinterpret_cast<const int*>(ops.data()), reinterpret_cast<const int*>(ops.data()) + (size_t) n * 7);
     for (int q = 0; q < nl; ++q) key.push_back(starts[q]);
-    key.push_back(layoutEpoch);
     // One list that does not rescale may hold several independent trees: without a cumulative buffer MrBayes submits the
     // operations of all eigen-system parts as ONE list (reference src/mbbeagle.c:1029-1104, No_Rescale), and a move dirties
     // the same root-ward path in each part.  Its connected components are treated like lists of their own.
@@ -2171,40 +2145,15 @@ int Instance::flushWalkG()
     for (int q = 0; q < nl; ++q) {
         const int ci = cums[q];
         if (ci == BEAGLE_OP_NONE) continue;
-        if (scaleState[ci] == 0) {
-            // a freshly reset cumulative buffer (the rescale-everything pass): the kernel STORES its sums, no zero-fill launch
-            if (!wideScale[ci]) HIP_TRY(hipMalloc(&wideScale[ci], (size_t) K * Ppad * sizeof(int32_t)));
-            scaleState[ci] = 2;
-            wgFresh |= 1 << q;
-        } else {
-            int rc = ensureWide(ci);
-            if (rc) return rc;
-        }
+        bool fresh;
+        int rc = prepareCumulative(ci, fresh);
+        if (rc) return rc;
+        if (fresh) wgFresh |= 1 << q;
         wgCum[q] = wideScale[ci];
     }
-    uint64_t h = 1469598103934665603ull;
-    for (int v : key) h = (h ^ (uint64_t) (uint32_t) v) * 1099511628211ull;
-    Plan* plan = nullptr;
-    for (Plan* pl : plans)
-        if (pl->hash == h && pl->key == key) {
-            pl->lastUse = ++planClock;
-            planHits++;
-            plan = pl;
-            break;
-        }
-    if (!plan) {
-        planMisses++;
-        const size_t maxPlans = 24;
-        if (plans.size() < maxPlans) {
-            plan = new Plan();
-            plans.push_back(plan);
-        } else {
-            plan = plans[0];
-            for (Plan* pl : plans) if (pl->lastUse < plan->lastUse) plan = pl;
-        }
-        plan->key = key;
-        plan->hash = h;
-        plan->lastUse = ++planClock;
+    bool build;
+    Plan* plan = cachedPlan(key.data(), key.size(), build);
+    if (build) {
         // Mutually independent lists (the eigen-system parts of a codon model) run as separate workgroups of ONE launch --
         // three times the workgroups for a grid that does not fill the chip otherwise -- if they compile to the same geometry;
         // anything else is one merged forest.
@@ -2261,7 +2210,7 @@ int Instance::flushWalkG()
             }
             if (!done) rc = buildWalk(*plan, ops.data(), n, listOf.data(), false);
         }
-        if (rc) { plan->hash = 0; plan->key.clear(); return rc; }
+        if (planBuilt(*plan, rc)) return rc;
     }
     // what updatePartials4 counts; one flush = one list event, however many eigen-system parts it carries
     listsTotal++;
@@ -2306,26 +2255,33 @@ static void launch_pathg_t(Instance& in, const WalkGArgs& a, const std::vector<W
     MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S), in.stream, ai);
 }
 
+// the instance's side of a general-state walk's arguments, with the cumulative buffers of the lists being flushed; the call
+// site adds program, geometry and which of those buffers are fresh
+WalkGArgs Instance::walkGArgs() const
+{
+    WalkGArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.partials = arenaPartials;
+    a.tileBytes = wgTileBytes;
+    a.tips = arenaTipStates;
+    a.tipTileBytes = wgTipTileBytes;
+    a.exps = arenaExp;
+    a.estride = estride;
+    a.matrices = matrices;
+    a.tabOff = (unsigned) (wgTabFloats * 4);
+    a.tabBytes = (unsigned) (wg_table_floats(S) * 4);
+    for (int q = 0; q < MBAMD_WG_MAXLISTS; ++q) a.cum[q] = wgCum[q];
+    a.K = K; a.Ppad = Ppad; a.ntiles = Ppad / MBAMD_WG_TW; a.S = S; a.SP = SP;
+    return a;
+}
+
 int Instance::runWalkG(const Plan& plan)
 {
+    WalkGArgs a = walkGArgs();
+    a.lists = plan.lists;
     if (plan.pathG) {
-        const Plan::Segment& sg = plan.segments.front();
-        WalkGArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.entries = sg.entries;
-        a.partials = arenaPartials;
-        a.tileBytes = wgTileBytes;
-        a.tips = arenaTipStates;
-        a.tipTileBytes = wgTipTileBytes;
-        a.exps = arenaExp;
-        a.estride = estride;
-        a.matrices = matrices;
-        a.tabOff = (unsigned) (wgTabFloats * 4);
-        a.tabBytes = (unsigned) (wg_table_floats(S) * 4);
-        for (int q = 0; q < MBAMD_WG_MAXLISTS; ++q) a.cum[q] = wgCum[q];
+        a.entries = plan.segments.front().entries;
         a.cumFresh = wgFresh;
-        a.K = K; a.Ppad = Ppad; a.ntiles = Ppad / MBAMD_WG_TW; a.S = S; a.SP = SP;
-        a.lists = plan.lists;
         switch (S) {
             case 20: launch_pathg_t<20>(*this, a, plan.inlineProg, plan.forked); break;
             case 60: launch_pathg_t<60>(*this, a, plan.inlineProg, plan.forked); break;
@@ -2339,24 +2295,10 @@ int Instance::runWalkG(const Plan& plan)
     }
     for (const Plan::Segment& sg : plan.segments) {
         if (plan.lists > 1 && &sg != &plan.segments.front()) break;     // (independent lists: one launch covers all segments)
-        WalkGArgs a;
-        std::memset(&a, 0, sizeof a);
         a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
         a.entries = sg.entries;
         a.nslots = sg.nslots;
-        a.partials = arenaPartials;
-        a.tileBytes = wgTileBytes;
-        a.tips = arenaTipStates;
-        a.tipTileBytes = wgTipTileBytes;
-        a.exps = arenaExp;
-        a.estride = estride;
-        a.matrices = matrices;
-        a.tabOff = (unsigned) (wgTabFloats * 4);
-        a.tabBytes = (unsigned) (wg_table_floats(S) * 4);
-        for (int q = 0; q < MBAMD_WG_MAXLISTS; ++q) a.cum[q] = wgCum[q];
         a.cumFresh = (&sg == &plan.segments.front()) ? wgFresh : 0;
-        a.K = K; a.Ppad = Ppad; a.ntiles = Ppad / MBAMD_WG_TW; a.S = S; a.SP = SP;
-        a.lists = plan.lists;
         a.spread = sg.W == 2 ? 1 : 0;     // two-wave workgroups are launched as four (see k_walkg)
         MBAMD_WG_DISPATCH(S, launch_walkg_t, *this, a, sg.W, sg.nslots, &plan.inlineProg);
         HIP_TRY(hipGetLastError());
@@ -2631,7 +2573,7 @@ int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, const std::
             }
         }
     }
-    return planTable(plan, sorted);
+    return planTable(plan, sorted.data(), sorted.size() * sizeof(PartialsOp));
 }
 
 int Instance::runGeneric(const Plan& plan, int32_t* cum)
@@ -2775,17 +2717,10 @@ int Instance::accumulate4(const int* idx, int n, int cumIdx, int sign)
     }
     // (arena buffers in front of the wide ones: the kernel sums them without a branch; the order of an integer sum is free)
     const int nNarrow = (int) (std::stable_partition(src.begin(), src.end(), [](const ExpSource& e) { return e.wide == nullptr; }) - src.begin());
-    // a freshly reset cumulative buffer (MrBayes-style rescaling: Reset + Accumulate of every node): the kernel STORES, no zero fill
-    const bool fresh = scaleState[cumIdx] == 0 && !src.empty();
-    int rc = BEAGLE_SUCCESS;
-    if (fresh) {
-        if (!wideScale[cumIdx]) HIP_TRY(hipMalloc(&wideScale[cumIdx], (size_t) K * Ppad * sizeof(int32_t)));
-        scaleState[cumIdx] = 2;
-    } else {
-        rc = ensureWide(cumIdx);
-        if (rc) return rc;
-    }
-    if (src.empty()) return BEAGLE_SUCCESS;
+    if (src.empty()) return ensureWide(cumIdx);                      // (nothing to add: the buffer is cumulative from here on)
+    bool fresh;
+    int rc = prepareCumulative(cumIdx, fresh);
+    if (rc) return rc;
     const ExpSource* dsrc = nullptr;
     rc = stageDirect(src.data(), sizeof(ExpSource) * src.size(), (const void**) &dsrc);
     if (rc) return rc;
@@ -2795,53 +2730,76 @@ int Instance::accumulate4(const int* idx, int n, int cumIdx, int sign)
     return BEAGLE_SUCCESS;
 }
 
-int Instance::integrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
-                        const int* cumIdx, int count, double* out)
+// The arguments of a log-likelihood call (child == nullptr: at the root), whichever kernel serves it.
+int Instance::checkIntegrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx, int count)
 {
-    if (count < 1 || count > MBAMD_MAX_SUBSETS) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "log-likelihood: subset count");
-    armSums();
-    if (arena()) {
-        int rc;
-        if (heldPath && count == 1 && parent[0] == heldPathDst && !(child && tipStates[child[0]] == nullptr && child[0] == heldPathDst)) {
-            rc = integratePath4(parent, child, prob, wIdx, fIdx, cumIdx);      // the held path and this integration: one launch
-        } else {
-            if (heldPath) { rc = runHeldPath(); if (rc) return rc; }
-            rc = integrate4(parent, child, prob, wIdx, fIdx, cumIdx, count);
-        }
-        if (rc) return rc;
-        rc = spanEnd();
-        if (rc) return rc;
-        postResultFlag();
-        haveSite = true;
-        pendingResult = true;
-        if (deferred) {
-            if (out) *out = 0.0;
-            return BEAGLE_SUCCESS;
-        }
-        return fetchResult(out);
-    }
-    IntegrateArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.count = count;
     for (int n = 0; n < count; ++n) {
-        if (parent[n] < 0 || parent[n] >= nBuffers || !valid[parent[n]])
+        // (arena layouts: a buffer that holds compact tip states has no partials to integrate over)
+        if (parent[n] < 0 || parent[n] >= nBuffers || !valid[parent[n]] || (arena() && tipStates[parent[n]]))
             return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: parent buffer");
-        a.parent[n] = partials[parent[n]];
         if (child) {
             const int ci = child[n];
             if (ci < 0 || ci >= nBuffers || prob[n] < 0 || prob[n] >= nMatrices)
                 return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge log-likelihood: child buffer / matrix");
-            if (tipStates[ci]) { a.child[n] = tipStates[ci]; a.child_kind[n] = CHILD_STATES; }
-            else if (valid[ci]) { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
-            else return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge log-likelihood: child buffer was never written");
-            a.matrix[n] = matrixPtr(prob[n]);
+            if (!tipStates[ci] && !valid[ci]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge log-likelihood: child buffer was never written");
         }
         if (wIdx[n] < 0 || wIdx[n] >= nEigen || fIdx[n] < 0 || fIdx[n] >= nEigen)
             return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: weights / frequencies index");
+        if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE && (cumIdx[n] < 0 || cumIdx[n] >= nScale))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: cumulative scale index");
+    }
+    return BEAGLE_SUCCESS;
+}
+
+int Instance::integrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
+                        const int* cumIdx, int count, double* out)
+{
+    if (count < 1 || count > MBAMD_MAX_SUBSETS) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "log-likelihood: subset count");
+    int rc = checkIntegrate(parent, child, prob, wIdx, fIdx, cumIdx, count);
+    if (rc) {                                    // (a held path is not lost to a bad call: it runs, then the error is the caller's)
+        if (heldPath) { int prc = runHeldPath(); if (prc) return prc; }
+        return rc;
+    }
+    armSums();
+    if (!arena()) {
+        rc = integrateLevels(parent, child, prob, wIdx, fIdx, cumIdx, count);
+    } else if (heldPath && count == 1 && parent[0] == heldPathDst && !(child && tipStates[child[0]] == nullptr && child[0] == heldPathDst)) {
+        rc = integratePath4(child, prob, wIdx, fIdx, cumIdx);                  // the held path and this integration: one launch
+    } else {
+        if (heldPath) { rc = runHeldPath(); if (rc) return rc; }
+        rc = integrate4(parent, child, prob, wIdx, fIdx, cumIdx, count);
+    }
+    if (rc) return rc;
+    rc = spanEnd();
+    if (rc) return rc;
+    postResultFlag();
+    haveSite = true;
+    pendingResult = true;
+    if (deferred) {
+        if (out) *out = 0.0;
+        return BEAGLE_SUCCESS;
+    }
+    return fetchResult(out);
+}
+
+// the level kernels' integration (arguments checked by integrate)
+int Instance::integrateLevels(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
+                              const int* cumIdx, int count)
+{
+    IntegrateArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.count = count;
+    for (int n = 0; n < count; ++n) {
+        a.parent[n] = partials[parent[n]];
+        if (child) {
+            const int ci = child[n];
+            if (tipStates[ci]) { a.child[n] = tipStates[ci]; a.child_kind[n] = CHILD_STATES; }
+            else { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
+            a.matrix[n] = matrixPtr(prob[n]);
+        }
         a.weights[n] = d_weights + (size_t) wIdx[n] * K;
         a.freqs[n] = d_freqs + (size_t) fIdx[n] * S;
         if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE) {
-            if (cumIdx[n] < 0 || cumIdx[n] >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: cumulative scale index");
             int rc = ensureScale(cumIdx[n]);
             if (rc) return rc;
             a.cum[n] = scale[cumIdx[n]];
@@ -2853,45 +2811,28 @@ int Instance::integrate(const int* parent, const int* child, const int* prob, co
     else
         MBAMD_LAUNCH(k_integrate_lnl, (unsigned) nblocks, 64, 0, stream, a, S, SP, K, P, Ppad, (const double*) d_pweights, siteOut, h_sums_dev);
     HIP_TRY(hipGetLastError());
-    { int src = spanEnd(); if (src) return src; }
-    postResultFlag();
-    haveSite = true;
-    pendingResult = true;
-    if (deferred) {
-        if (out) *out = 0.0;
-        return BEAGLE_SUCCESS;
-    }
-    return fetchResult(out);
+    return BEAGLE_SUCCESS;
 }
 
-// the held root-ward path (k_path4 plan) and the log-likelihood over its last result as ONE launch (k_path4_lnl, mbamd_walk4.h)
-int Instance::integratePath4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx)
+// the held root-ward path (k_path4 plan) and the log-likelihood over its last result as ONE launch (k_path4_lnl, mbamd_walk4.h;
+// arguments checked by integrate).  The path stays held until that launch is in the stream: whatever fails before, the path
+// still runs on its own and the error is returned.
+int Instance::integratePath4(const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx)
 {
     Plan* plan = heldPath;
     PathLnl4 t;
     std::memset(&t, 0, sizeof t);
-    bool ok = parent[0] >= 0 && parent[0] < nBuffers && valid[parent[0]] && !tipStates[parent[0]];
-    if (ok && child) {
+    if (child) {
         const int ci = child[0];
-        ok = ci >= 0 && ci < nBuffers && prob[0] >= 0 && prob[0] < nMatrices && (tipStates[ci] || valid[ci]);
-        if (ok) {
-            if (tipStates[ci]) { t.child = tipStates[ci]; t.child_kind = CHILD_STATES; }
-            else { t.child = partials[ci]; t.child_kind = CHILD_PARTIALS; }
-            t.matrix = matrixPtr(prob[0]);
-        }
-    }
-    ok = ok && wIdx[0] >= 0 && wIdx[0] < nEigen && fIdx[0] >= 0 && fIdx[0] < nEigen;
-    if (ok && cumIdx && cumIdx[0] != BEAGLE_OP_NONE) ok = cumIdx[0] >= 0 && cumIdx[0] < nScale;
-    if (!ok) {                                   // (let the separate kernels report what is wrong, in their own words)
-        int rc = runHeldPath();
-        if (rc) return rc;
-        return integrate4(parent, child, prob, wIdx, fIdx, cumIdx, 1);
+        if (tipStates[ci]) { t.child = tipStates[ci]; t.child_kind = CHILD_STATES; }
+        else { t.child = partials[ci]; t.child_kind = CHILD_PARTIALS; }
+        t.matrix = matrixPtr(prob[0]);
     }
     t.weights = d_weights + (size_t) wIdx[0] * K;
     t.freqs = d_freqs + (size_t) fIdx[0] * S;
+    int rc = BEAGLE_SUCCESS;
     if (cumIdx && cumIdx[0] != BEAGLE_OP_NONE && scaleState[cumIdx[0]] != 0) {
-        int rc = ensureWide(cumIdx[0]);
-        if (rc) return rc;
+        rc = ensureWide(cumIdx[0]);
         t.cum = wideScale[cumIdx[0]];
     }
     double* const siteOut = (siteToHost && h_site_dev) ? h_site_dev : d_site;
@@ -2900,46 +2841,32 @@ int Instance::integratePath4(const int* parent, const int* child, const int* pro
     t.site = siteOut;
     t.wsite = h_sums_dev;
     t.P = P;
+    hipEvent_t ev0{}, ev1{};
+    if (rc == BEAGLE_SUCCESS) rc = launchesBegin(ev0, ev1);
+    if (rc == BEAGLE_SUCCESS) {
+        plan->lastLaunch = ++launchClock;
+        Walk4ArgsInline ai;
+        ai.a = walk4Args();
+        ai.a.entries = (int) plan->inlineProg.size();
+        ai.a.cum = heldPathCum;
+        ai.a.cumFresh = heldPathFresh ? 1 : 0;
+        std::memcpy(ai.inl, plan->inlineProg.data(), plan->inlineProg.size() * sizeof(Walk4Entry));
+        auto kernel = k_path4_lnl<Walk4ArgsInline>;
+        MBAMD_LAUNCH_BARRIER(kernel, 8u * (unsigned) ((Ppad / 64 + 7) / 8), 64 * K, path4_lnl_lds_bytes(ai.a.entries, K), stream, ai, t);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) rc = hip_fail(le, "k_path4_lnl");
+    }
+    if (rc) {
+        (void) runHeldPath();
+        return rc;
+    }
     heldPath = nullptr;
     fusedPaths++;
-    plan->lastLaunch = ++launchClock;
-    { int src = spanBegin(); if (src) return src; }
-    Walk4ArgsInline ai;
-    Walk4Args& a = ai.a;
-    a.prog = nullptr;
-    a.entries = (int) plan->inlineProg.size();
-    a.nslots = 0;
-    a.partials = reinterpret_cast<f4*>(arenaPartials);
-    a.pstride = geom.pstride;
-    a.tips = arenaTips;
-    a.tstride = geom.tstride;
-    a.exps = arenaExp;
-    a.estride = estride;
-    a.matrices = matrices;
-    a.cum = heldPathCum;
-    a.cumFresh = heldPathFresh ? 1 : 0;
-    a.K = K;
-    a.Ppad = Ppad;
-    a.nblocks = Ppad / 64;
-    a.tail = 0;
-    std::memcpy(ai.inl, plan->inlineProg.data(), plan->inlineProg.size() * sizeof(Walk4Entry));
-    hipEvent_t ev0{}, ev1{};
-    if (timing) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
-    auto kernel = k_path4_lnl<Walk4ArgsInline>;
-    MBAMD_LAUNCH_BARRIER(kernel, 8u * (unsigned) ((Ppad / 64 + 7) / 8), 64 * K, path4_lnl_lds_bytes(a.entries, K), stream, ai, t);
-    HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        events.emplace_back(ev0, ev1);
-    }
     pendingLaunches += 1;
-    return BEAGLE_SUCCESS;
+    return launchesEnd(ev0, ev1);
 }
 
+// the arena layouts' integration (arguments checked by integrate)
 int Instance::integrate4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
                          const int* cumIdx, int count)
 {
@@ -2947,29 +2874,19 @@ int Instance::integrate4(const int* parent, const int* child, const int* prob, c
     std::memset(&a, 0, sizeof a);
     a.count = count;
     for (int n = 0; n < count; ++n) {
-        if (parent[n] < 0 || parent[n] >= nBuffers || !valid[parent[n]] || tipStates[parent[n]])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: parent buffer");
         a.parent[n] = reinterpret_cast<const f4*>(partials[parent[n]]);
         if (child) {
             const int ci = child[n];
-            if (ci < 0 || ci >= nBuffers || prob[n] < 0 || prob[n] >= nMatrices)
-                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge log-likelihood: child buffer / matrix");
             if (tipStates[ci]) { a.child[n] = tipStates[ci]; a.child_kind[n] = CHILD_STATES; }
-            else if (valid[ci]) { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
-            else return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge log-likelihood: child buffer was never written");
+            else { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
             a.matrix[n] = matrixPtr(prob[n]);
         }
-        if (wIdx[n] < 0 || wIdx[n] >= nEigen || fIdx[n] < 0 || fIdx[n] >= nEigen)
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: weights / frequencies index");
         a.weights[n] = d_weights + (size_t) wIdx[n] * K;
         a.freqs[n] = d_freqs + (size_t) fIdx[n] * S;
-        if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE) {
-            if (cumIdx[n] < 0 || cumIdx[n] >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "log-likelihood: cumulative scale index");
-            if (scaleState[cumIdx[n]] != 0) {
-                int rc = ensureWide(cumIdx[n]);
-                if (rc) return rc;
-                a.cum[n] = wideScale[cumIdx[n]];
-            }
+        if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE && scaleState[cumIdx[n]] != 0) {
+            int rc = ensureWide(cumIdx[n]);
+            if (rc) return rc;
+            a.cum[n] = wideScale[cumIdx[n]];
         }
     }
     double* const siteOut = (siteToHost && h_site_dev) ? h_site_dev : d_site;
@@ -3308,7 +3225,7 @@ using namespace mbamd;
 // every entry point except beagleUpdatePartials first runs the lists deferred so far
 #define GET_INSTANCE(id)                                                                             \
     GET_INSTANCE_NOFLUSH(id);                                                                        \
-    if (in->hasPending() || !in->pendingJobs.empty()) {                                          \
+    if (in->hasWork()) {                                                                             \
         int frc_ = in->flushPending();                                                               \
         if (frc_ != BEAGLE_SUCCESS) return frc_;                                                     \
     }
@@ -3316,26 +3233,35 @@ using namespace mbamd;
 // log-likelihood calls themselves leave a held 4-state path where it is (Instance::heldPath)
 #define GET_INSTANCE_KEEPING_PATH(id)                                                                \
     GET_INSTANCE_NOFLUSH(id);                                                                        \
-    if (!in->pending.empty() || !in->wgListCum.empty() || !in->pendingJobs.empty()) {                \
+    if (in->hasWork(false)) {                                                                        \
         int frc_ = in->flushPending(true);                                                           \
         if (frc_ != BEAGLE_SUCCESS) return frc_;                                                     \
     }
+// a facade's call on every child, in order: its device made current, its deferred work run first (`flush`); the first error ends it
+template <class F>
+static int each_child(Instance* in, bool flush, F&& call)
+{
+    for (Instance::Child& ch : in->children) {
+        (void) hipSetDevice(ch.in->device);
+        if (flush && ch.in->hasWork()) {
+            int frc = ch.in->flushPending();
+            if (frc != BEAGLE_SUCCESS) return frc;
+        }
+        int crc = call(ch);
+        if (crc != BEAGLE_SUCCESS) return crc;
+    }
+    return BEAGLE_SUCCESS;
+}
+// K rows of n values each between a child's [K][count][width] block and its pattern range of a client's [K][P][width] array
+template <class T>
+static void copy_rows(T* dst, size_t dstRow, const T* src, size_t srcRow, int K, size_t n)
+{
+    for (int k = 0; k < K; ++k) std::memcpy(dst + (size_t) k * dstRow, src + (size_t) k * srcRow, n * sizeof(T));
+}
 // a facade forwards the call to every child (`c`, its pattern range in `ch`) and returns
 #define FACADE_EACH(FLUSH, ...)                                                                      \
-    if (in->facade()) {                                                                              \
-        for (Instance::Child& ch : in->children) {                                                   \
-            Instance* c = ch.in;                                                                     \
-            (void) ch;                                                                               \
-            (void) hipSetDevice(c->device);                                                          \
-            if (FLUSH && (c->hasPending() || !c->pendingJobs.empty())) {                         \
-                int frc_ = c->flushPending();                                                        \
-                if (frc_ != BEAGLE_SUCCESS) return frc_;                                             \
-            }                                                                                        \
-            int crc_ = (__VA_ARGS__);                                                                \
-            if (crc_ != BEAGLE_SUCCESS) return crc_;                                                 \
-        }                                                                                            \
-        return BEAGLE_SUCCESS;                                                                       \
-    }
+    if (in->facade())                                                                                \
+        return each_child(in, FLUSH, [&](Instance::Child& ch) { Instance* c = ch.in; (void) c; return (int) (__VA_ARGS__); })
 #define FACADE_ALL(...) FACADE_EACH(true, __VA_ARGS__)
 
 // the engine proper for one log-likelihood call; facade: per-child sums, FLOATING_POINT if any child says so
@@ -3364,7 +3290,7 @@ static int integrate_any(Instance* in, const int* parent, const int* child, cons
         }
         Instance* c = ch.in;
         (void) hipSetDevice(c->device);
-        if (c->hasPending() || !c->pendingJobs.empty()) { int frc = c->flushPending(); if (frc) return frc; }
+        if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
         const bool was = c->deferred;
         c->deferred = true;                             // launch everywhere first, collect afterwards
         const int rc = c->integrate(pa.data(), child ? ca.data() : nullptr, child ? pr.data() : nullptr, wa.data(), fa.data(),
@@ -3606,7 +3532,6 @@ int beagleSetCPUThreadCount(int instance, int threadCount)
 {
     (void) threadCount;
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return BEAGLE_SUCCESS;
     return BEAGLE_SUCCESS;
 }
 
@@ -3660,19 +3585,14 @@ int beagleSetPartials(int instance, int bufferIndex, const double* inPartials)
 {
     GET_INSTANCE(instance);
     if (in->f64) return in->f64->setPartials(bufferIndex, inPartials, true);
-    if (in->facade()) {
-        std::vector<double> part;
-        for (Instance::Child& ch : in->children) {
-            part.resize((size_t) in->K * ch.count * in->S);
-            for (int k = 0; k < in->K; ++k)
-                std::memcpy(part.data() + (size_t) k * ch.count * in->S, inPartials + ((size_t) k * in->P + ch.start) * in->S,
-                            sizeof(double) * ch.count * in->S);
-            (void) hipSetDevice(ch.in->device);
-            const int rc = ch.in->importPartials(bufferIndex, part.data(), true);
-            if (rc) return rc;
-        }
-        return BEAGLE_SUCCESS;
-    }
+    std::vector<double> part;
+    const size_t S = (size_t) in->S;
+    if (in->facade())
+        return each_child(in, false, [&](Instance::Child& ch) {
+            part.resize((size_t) in->K * ch.count * S);
+            copy_rows(part.data(), ch.count * S, inPartials + ch.start * S, in->P * S, in->K, ch.count * S);
+            return ch.in->importPartials(bufferIndex, part.data(), true);
+        });
     return in->importPartials(bufferIndex, inPartials, true);
 }
 int beagleGetPartials(int instance, int bufferIndex, int scaleIndex, double* outPartials)
@@ -3680,20 +3600,15 @@ int beagleGetPartials(int instance, int bufferIndex, int scaleIndex, double* out
     GET_INSTANCE(instance);
     if (in->f64) return in->f64->getPartials(bufferIndex, outPartials);
     if (scaleIndex != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleGetPartials: scaleIndex must be BEAGLE_OP_NONE");
-    if (in->facade()) {
-        std::vector<double> part;
-        for (Instance::Child& ch : in->children) {
-            part.resize((size_t) in->K * ch.count * in->S);
-            (void) hipSetDevice(ch.in->device);
-            if (ch.in->hasPending() || !ch.in->pendingJobs.empty()) { int frc = ch.in->flushPending(); if (frc) return frc; }
+    std::vector<double> part;
+    const size_t S = (size_t) in->S;
+    if (in->facade())
+        return each_child(in, true, [&](Instance::Child& ch) {
+            part.resize((size_t) in->K * ch.count * S);
             const int rc = ch.in->getPartials(bufferIndex, part.data());
-            if (rc) return rc;
-            for (int k = 0; k < in->K; ++k)
-                std::memcpy(outPartials + ((size_t) k * in->P + ch.start) * in->S, part.data() + (size_t) k * ch.count * in->S,
-                            sizeof(double) * ch.count * in->S);
-        }
-        return BEAGLE_SUCCESS;
-    }
+            if (rc == BEAGLE_SUCCESS) copy_rows(outPartials + ch.start * S, in->P * S, part.data(), ch.count * S, in->K, ch.count * S);
+            return rc;
+        });
     return in->getPartials(bufferIndex, outPartials);
 }
 int beagleSetEigenDecomposition(int instance, int eigenIndex, const double* inEigenVectors,
@@ -3836,7 +3751,7 @@ int beagleGetTransitionMatrix(int instance, int matrixIndex, double* outMatrix)
     if (in->facade()) {
         Instance* c = in->children[0].in;
         (void) hipSetDevice(c->device);
-        if (c->hasPending() || !c->pendingJobs.empty()) { int frc = c->flushPending(); if (frc) return frc; }
+        if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
         return c->getMatrix(matrixIndex, outMatrix);
     }
     return in->getMatrix(matrixIndex, outMatrix);
@@ -4055,19 +3970,14 @@ int mbamdGetScaleExponents(int instance, int srcScalingIndex, int* out)
 {
     GET_INSTANCE(instance);
     if (in->f64) return in->f64->getScaleExponents(srcScalingIndex, out);
-    if (in->facade()) {
-        std::vector<int> part;
-        for (Instance::Child& ch : in->children) {
+    std::vector<int> part;
+    if (in->facade())
+        return each_child(in, true, [&](Instance::Child& ch) {
             part.resize((size_t) in->K * ch.count);
-            (void) hipSetDevice(ch.in->device);
-            if (ch.in->hasPending() || !ch.in->pendingJobs.empty()) { int frc = ch.in->flushPending(); if (frc) return frc; }
             const int rc = ch.in->getScaleExponents(srcScalingIndex, part.data());
-            if (rc) return rc;
-            for (int k = 0; k < in->K; ++k)
-                std::memcpy(out + (size_t) k * in->P + ch.start, part.data() + (size_t) k * ch.count, sizeof(int) * ch.count);
-        }
-        return BEAGLE_SUCCESS;
-    }
+            if (rc == BEAGLE_SUCCESS) copy_rows(out + ch.start, (size_t) in->P, part.data(), (size_t) ch.count, in->K, (size_t) ch.count);
+            return rc;
+        });
     return in->getScaleExponents(srcScalingIndex, out);
 }
 // BEAGLE's scale factors are one log value per pattern.  The 4-state path keeps an exponent per (pattern, category):
@@ -4111,9 +4021,9 @@ int beagleCalculateEdgeLogLikelihoods(int instance, const int* parentBufferIndic
 {
     StatTimer st_(ST_LNL);
     GET_INSTANCE_KEEPING_PATH(instance);
-    if (in->f64) return (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivative || outSumSecondDerivative) ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoods: derivatives") : in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
     if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivative || outSumSecondDerivative)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoods: derivatives");
+    if (in->f64) return in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
     const int rc_ = integrate_any(in, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
                                   stateFrequenciesIndices, cumulativeScaleIndices, count, nullptr, 1, nullptr, outSumLogLikelihood);
     API_TRACE("beagleCalculateEdgeLogLikelihoods(parents=%s, children=%s, matrices=%s, weights=%s, freqs=%s, cumulative=%s) -> %d, lnL %.6f",
@@ -4153,14 +4063,12 @@ int beagleCalculateEdgeLogLikelihoodsByPartition(int instance, const int* parent
 {
     StatTimer st_(ST_LNL);
     GET_INSTANCE(instance);
-    if (in->f64)
-        return (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivativeByPartition || outSumFirstDerivative || outSumSecondDerivativeByPartition || outSumSecondDerivative)
-                   ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoodsByPartition: derivatives")
-                   : in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices,
-                                             cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
     if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivativeByPartition || outSumFirstDerivative ||
         outSumSecondDerivativeByPartition || outSumSecondDerivative)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoodsByPartition: derivatives");
+    if (in->f64)
+        return in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices,
+                                       cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
     if (!in->facade() && (partitionCount != 1 || partitionIndices[0] != 0))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeLogLikelihoodsByPartition: no partitions were set");
     double total = 0.0;
@@ -4202,14 +4110,7 @@ static int kernel_timing_of(Instance* in, double* ms, long* launches, int reset)
 {
     (void) hipSetDevice(in->device);
     HIP_TRY(hipStreamSynchronize(in->stream));
-    for (auto& ev : in->events) {
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, ev.first, ev.second));
-        in->timedMs += t;
-        (void) hipEventDestroy(ev.first);
-        (void) hipEventDestroy(ev.second);
-    }
-    in->events.clear();
+    { int frc = in->eventsFold(); if (frc) return frc; }
     in->timedLaunches += in->pendingLaunches;
     in->pendingLaunches = 0;
     *ms += in->timedMs;
@@ -4296,8 +4197,7 @@ int mbamdSetKernelPath(int instance, int path)
     GET_INSTANCE(instance);
     if (in->f64) return BEAGLE_SUCCESS;
     if (path < 0 || path > 3) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdSetKernelPath");
-    in->path = path;
-    return BEAGLE_SUCCESS;
+    return BEAGLE_SUCCESS;                       // (accepted and ignored: every instance picks its kernels from its dimensions)
 }
 int mbamdWalkTrace(int instance, long long* out, int maxSteps, int* outSteps, int* outWaves)
 {
@@ -4387,21 +4287,18 @@ int mbamdGetScaledPartials(int instance, int bufferIndex, int cumulativeScaleInd
     if (!in->facade()) return in->getScaledPartials(bufferIndex, cumulativeScaleIndex, outPartials, outLnScale);
     if (in->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetScaledPartials: not on a multi-partition instance");
     // pattern shards: each child's [K][count][S] block goes to its pattern range of the caller's [K][P][S] array
-    const int S = in->createArgs[3], P = in->createArgs[4], K = in->createArgs[7];
+    const size_t S = (size_t) in->createArgs[3], P = (size_t) in->createArgs[4];
+    const int K = in->createArgs[7];
     std::vector<float> part, ln;
-    for (Instance::Child& ch : in->children) {
-        Instance* c = ch.in;
-        (void) hipSetDevice(c->device);
-        if (c->hasPending() || !c->pendingJobs.empty()) { int frc = c->flushPending(); if (frc) return frc; }
+    return each_child(in, true, [&](Instance::Child& ch) {
         part.resize((size_t) K * ch.count * S);
         ln.resize((size_t) ch.count);
-        int rc = c->getScaledPartials(bufferIndex, cumulativeScaleIndex, part.data(), ln.data());
+        const int rc = ch.in->getScaledPartials(bufferIndex, cumulativeScaleIndex, part.data(), ln.data());
         if (rc) return rc;
-        for (int k = 0; k < K; ++k)
-            std::memcpy(outPartials + ((size_t) k * P + ch.start) * S, part.data() + (size_t) k * ch.count * S, (size_t) ch.count * S * sizeof(float));
-        std::memcpy(outLnScale + ch.start, ln.data(), (size_t) ch.count * sizeof(float));
-    }
-    return BEAGLE_SUCCESS;
+        copy_rows(outPartials + ch.start * S, P * S, part.data(), ch.count * S, K, ch.count * S);
+        copy_rows(outLnScale + ch.start, P, ln.data(), (size_t) ch.count, 1, (size_t) ch.count);
+        return (int) BEAGLE_SUCCESS;
+    });
 }
 
 

@@ -143,7 +143,7 @@ def test_lds_stack_eviction(emu, oracle, monkeypatch):
     assert abs(lnl - want) / abs(want) < ec.REL_FP64
 
 
-def test_error_codes(emu):
+def test_error_codes(emu, monkeypatch):
     inst = bg.BeagleInstance(emu, 2, 4, 2, 4, 10, 1, 2, 4, 2)
     with pytest.raises(bg.BeagleError) as e:
         inst.update_partials(np.array([[9, -1, -1, 0, 0, 1, 1]], dtype=np.int32))
@@ -154,6 +154,41 @@ def test_error_codes(emu):
     with pytest.raises(bg.BeagleError):
         bg.BeagleInstance(emu, 2, 4, 2, 65, 10, 1, 2, 4, 2)                         # > 64 states
     inst.finalize()
+
+    # A bad log-likelihood call behind a HELD root-ward path (four states: the list of a branch move waits for the call that
+    # follows it): the child index one past the last buffer is refused before anything is read with it, and the path is not
+    # lost -- it runs, so that the next, valid call sees its result, as it does where paths are never held.
+    def root_after_refused_edge():
+        div = synthetic_division("gtr", 20, 130, seed=51, tree_seed=52)
+        t = div.tree
+        bd = lk.BeagleDivision(div, emu, scaling=lk.MB_BEAGLE_SCALE_DYNAMIC)
+        try:
+            bd.LogLike(0)
+            bd.AcceptMove(0)
+            node = t.int_down_pass[0]
+            t.length[node] *= 1.9
+            bd.TouchBranch(0, node)
+            bd.TreeTiProbs_Beagle(0)
+            bd.TreeCondLikes_Beagle_No_Rescale(0)                                    # the path's list
+            top = bd.condLikeIndex[0][t.root_left]
+            eig, cum = [bd.cijkIndex[0]], [bd.siteScalerIndex[0]]
+            past_the_end = bd.numCondLikes * bd.step + sum(s is not None for s in div.tip_states)
+            with pytest.raises(bg.BeagleError) as err:
+                bd.inst.calculate_edge_log_likelihoods([top], [past_the_end], [bd.tiProbsIndex[0][t.root_left]], eig, eig, cum)
+            assert err.value.code == bg.BEAGLE_ERROR_OUT_OF_RANGE
+            rc, lnl = bd.inst.calculate_root_log_likelihoods([top], eig, eig, cum)
+            assert rc == bg.BEAGLE_SUCCESS
+            counts = bd.inst.get_list_counts()
+            return lnl, counts
+        finally:
+            bd.finalize()
+
+    monkeypatch.delenv("MBAMD_NO_FUSE_PATH", raising=False)
+    held, counts = root_after_refused_edge()
+    assert counts[1] == 1 and counts[3] == 0           # the list was a path; it ran on its own, not with a log-likelihood
+    monkeypatch.setenv("MBAMD_NO_FUSE_PATH", "1")
+    plain, _ = root_after_refused_edge()
+    assert np.isfinite(plain) and held == plain
 
 
 @pytest.mark.parametrize("waves", [2, 3, 4, 8])
