@@ -1,5 +1,5 @@
 // mbamd_engine.cpp -- host side of the MI355X conditional-likelihood engine and its C ABI
-// (include/libhmsbeagle/beagle.h).  One Instance = one MrBayes data division: it owns every
+// (include/libhmsbeagle/beagle.h).  One instance = one MrBayes data division: its engine owns every
 // partials / transition-matrix / scale buffer of all local chains in HBM (the reference's
 // condLikes/tiProbs/scalers arrays, src/mcmc.c:5703-6510) and turns each BEAGLE call coming from
 // src/mbbeagle.c into HIP kernel launches on a private stream.
@@ -183,39 +183,24 @@ struct PathStep {
     int scaleMode, scaleIdx;         // SCALE_NONE / SCALE_WRITE / SCALE_READ and its exponent buffer
 };
 
+// the dimensions an instance was created with (beagleCreateInstance)
+struct Dims {
+    int tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount, categoryCount,
+        scaleBufferCount;
+};
+
+// The single-precision engine of one device: arenas, stream, plan cache, schedulers.  Created by new_engine() only; the
+// destructor hands everything back.  What the C ABI calls an instance is a Handle (further down), which owns one of these,
+// several (pattern shards, v3 partitions), or the double-precision engine instead.
 struct Instance {
-    // ---- facade: an instance whose site patterns are split over child instances -- one per pattern PARTITION
-    // (BEAGLE v3 multi-partition mode, reference src/mbbeagle.c:1500-3010) and/or per SHARD (pattern blocks of one
-    // partition on different GPUs).  Site patterns are independent through the whole recursion, so every
-    // call fans out to the children (each with its own stream, possibly its own device) and only the log-likelihood
-    // sums meet again on the host.  A facade owns no device memory itself.
-    struct Child { Instance* in; int start, count, partition; };
-    std::vector<Child> children;
-    bool facade() const { return !children.empty(); }
-    int createArgs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<int> shardDevices;   // devices the patterns of every partition are spread over (size 1: no sharding)
-    int partitionCount = 1;
-    bool released = false;           // device buffers handed back (became a facade)
-    // tip data and pattern weights as the client gave them, kept until the first computation: a v3 client sets them
-    // BEFORE it declares the partitions (reference src/mbbeagle.c:1655-1700 then src/mcmc.c:6461-6466)
-    bool logOpen = true;
-    std::vector<std::pair<int, std::vector<int>>> logTipStates;
-    std::vector<std::pair<int, std::vector<double>>> logTipPartials;
-    std::vector<double> logWeights;
-    int makeChildren(const std::vector<std::pair<int, int>>& partitionRanges);
-    void destroyChildren();
+    Instance() = default;
+    Instance(const Instance&) = delete;
+    Instance& operator=(const Instance&) = delete;
+    ~Instance();
     int getSites(double* out);
     int getScaleExponents(int idx, int* out);
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
-    void closeLog()                  // the first computation: the set-up data is where it belongs, drop the host copies
-    {
-        if (!logOpen) return;
-        logOpen = false;
-        std::vector<std::pair<int, std::vector<int>>>().swap(logTipStates);
-        std::vector<std::pair<int, std::vector<double>>>().swap(logTipPartials);
-        std::vector<double>().swap(logWeights);
-    }
 
     int device = 0;
     hipStream_t stream{};
@@ -286,8 +271,6 @@ struct Instance {
     long long* d_trace = nullptr;    // MBAMD_WALK_TRACE: per-step clock stamps of workgroup 0 (timing experiments)
 
     int NT = 0, T = 0;               // MFMA packing: i-tiles of 32 rows, j-pairs
-    long flags = 0;
-    class Engine64* f64 = nullptr;        // BEAGLE_FLAG_PRECISION_DOUBLE: this object is only the handle, the engine is mbamd_f64.h
     size_t partialsFloats = 0, matrixFloats = 0, eigenDoubles = 0;
 
     std::vector<float*> partials;      // general path: allocated on first use; 4-state path: slices of the arena
@@ -515,7 +498,6 @@ struct Instance {
 
     int create(int tipCount_, int partialsBufferCount, int compactBufferCount, int stateCount, int patternCount,
                int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev, const Switches& switches);
-    void destroy();
 
     int configureWalk();
     void wgGeometry(int lists, int& W, int& slots) const;
@@ -570,35 +552,24 @@ static bool launch_mfma_serial(Instance& in, const OpTables& tabs, int ntables);
 static bool launch_tips(Instance& in, const OpTables& tabs, int count);
 
 static std::mutex g_mutex;
-static std::vector<Instance*> g_instances;
 
-// A new engine for one device.  The 20/61-state tree walk allocates every buffer up front (arenas); if that does not fit,
-// the same instance is set up once more on the level kernels, which allocate a buffer when it is first written.
-static int new_engine(Instance*& out, long flags, int tipCount, int partialsBufferCount, int compactBufferCount, int stateCount,
-                      int patternCount, int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev,
-                      const Switches& sw)
+// A new engine for `patternCount` of an instance's patterns on one device -- the only place one is made.  The 20/61-state tree
+// walk allocates every buffer up front (arenas); if that does not fit, the engine is set up once more on the level kernels,
+// which allocate a buffer when it is first written.
+static int new_engine(std::unique_ptr<Instance>& out, const Dims& d, int patternCount, int dev, const Switches& sw)
 {
     for (int attempt = 0; attempt < 2; ++attempt) {
-        Instance* c = new Instance();
-        c->flags = flags;
+        std::unique_ptr<Instance> c(new Instance());
         c->noWalkG = attempt == 1;
-        const int rc = c->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                                 matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
-        if (rc == BEAGLE_SUCCESS) { out = c; return rc; }
+        const int rc = c->create(d.tipCount, d.partialsBufferCount, d.compactBufferCount, d.stateCount, patternCount, d.eigenBufferCount,
+                                 d.matrixBufferCount, d.categoryCount, d.scaleBufferCount, dev, sw);
+        if (rc == BEAGLE_SUCCESS) { out = std::move(c); return rc; }
         const bool retry = rc == BEAGLE_ERROR_OUT_OF_MEMORY && c->wg && attempt == 0;
-        c->destroy();
-        delete c;
+        c.reset();
         (void) hipGetLastError();
         if (!retry) return rc;
     }
     return BEAGLE_ERROR_OUT_OF_MEMORY;
-}
-
-static Instance* lookup(int id)
-{
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (id < 0 || id >= (int) g_instances.size()) return nullptr;
-    return g_instances[id];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -758,7 +729,8 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
     return BEAGLE_SUCCESS;
 }
 
-void Instance::destroy()
+// synchronise, free the device memory, destroy the stream
+Instance::~Instance()
 {
     (void) hipSetDevice(device);
     (void) hipStreamSynchronize(stream);
@@ -3015,7 +2987,7 @@ static void buildResources()
 }  // namespace mbamd
 
 // ---------------------------------------------------------------------------------------------
-// per-pattern read-outs as Instance methods (the facade gathers them from its children)
+// per-pattern read-outs as Instance methods (a handle of children gathers them)
 // ---------------------------------------------------------------------------------------------
 namespace mbamd {
 
@@ -3158,48 +3130,6 @@ int Instance::getScaledPartials(int idx, int cumIdx, float* out, float* outLn)
     return BEAGLE_SUCCESS;
 }
 
-
-void Instance::destroyChildren()
-{
-    for (Child& ch : children) { ch.in->destroy(); delete ch.in; }
-    children.clear();
-}
-
-// Split the patterns into child instances: every partition range (start, count) is cut into one shard per device of
-// shardDevices (whole 64-pattern blocks, the last shard takes the remainder), then the recorded tip data and pattern
-// weights are replayed into the children.
-int Instance::makeChildren(const std::vector<std::pair<int, int>>& ranges)
-{
-    destroyChildren();
-    const int G = std::max<int>(1, (int) shardDevices.size());
-    for (size_t p = 0; p < ranges.size(); ++p) {
-        const int start = ranges[p].first, count = ranges[p].second;
-        const int blocks = (count + 63) / 64;
-        const int g = std::max(1, std::min(G, blocks));
-        int done = 0;
-        for (int i = 0; i < g; ++i) {
-            const int b0 = (int) ((long) blocks * i / g), b1 = (int) ((long) blocks * (i + 1) / g);
-            const int n = (i == g - 1) ? count - done : (b1 - b0) * 64;
-            if (n <= 0) continue;
-            Instance* c = nullptr;
-            const int dev = shardDevices.empty() ? device : shardDevices[i % shardDevices.size()];
-            int rc = new_engine(c, flags, createArgs[0], createArgs[1], createArgs[2], createArgs[3], n, createArgs[5], createArgs[6],
-                                createArgs[7], createArgs[8], dev, sw);
-            if (rc) { destroyChildren(); return rc; }
-            c->logOpen = false;
-            children.push_back(Child{c, start + done, n, (int) p});
-            done += n;
-        }
-    }
-    for (Child& ch : children) {
-        (void) hipSetDevice(ch.in->device);
-        for (auto& ts : logTipStates) { int rc = ch.in->setTipStates(ts.first, ts.second.data() + ch.start); if (rc) return rc; }
-        for (auto& tp : logTipPartials) { int rc = ch.in->importPartials(tp.first, tp.second.data() + (size_t) ch.start * S, false); if (rc) return rc; }
-        if (!logWeights.empty()) { int rc = ch.in->upload(ch.in->d_pweights, logWeights.data() + ch.start, sizeof(double) * ch.count); if (rc) return rc; }
-    }
-    return BEAGLE_SUCCESS;
-}
-
 }  // namespace mbamd
 
 // =============================================================================================
@@ -3211,21 +3141,105 @@ int Instance::makeChildren(const std::vector<std::pair<int, int>>& ranges)
 
 using namespace mbamd;
 
+// What an instance number of the C ABI stands for.  It owns exactly one of: one single-precision engine ("plain"); a list of
+// child engines, one per pattern PARTITION (BEAGLE v3 multi-partition mode, reference src/mbbeagle.c:1500-3010) and / or per
+// SHARD (pattern blocks of one partition on different GPUs); the double-precision engine (mbamd_f64.h).  Site
+// patterns are independent through the whole recursion, so a call fans out to the children (each with its own stream,
+// possibly its own device) and only the log-likelihood sums meet again on the host.  The handle itself holds what belongs to
+// the API object and not to a device; tear-down is its destructor.
+struct Handle {
+    struct Span { int start, count, partition; };          // the patterns [start, start + count) of the instance, and their partition
+    struct Child { std::unique_ptr<Instance> in; Span span; };
+    std::unique_ptr<Instance> engine;
+    std::vector<Child> children;
+    std::unique_ptr<Engine64> f64;
+
+    Dims dim{};
+    long flags = 0;                  // as reported to the client
+    Switches sw;                     // the environment switches, read when the instance was created: children are created from them
+    int device = 0;                  // the first (or only) device
+    std::vector<int> shardDevices;   // devices the patterns of every partition are spread over (size 1: no sharding)
+    int partitionCount = 1;
+    // tip data and pattern weights as the client gave them, kept until the first computation: a v3 client sets them
+    // BEFORE it declares the partitions (reference src/mbbeagle.c:1655-1700 then src/mcmc.c:6461-6466)
+    bool logOpen = true;
+    std::vector<std::pair<int, std::vector<int>>> logTipStates;
+    std::vector<std::pair<int, std::vector<double>>> logTipPartials;
+    std::vector<double> logWeights;
+    void closeLog()                  // the first computation: the set-up data is where it belongs, drop the host copies
+    {
+        if (!logOpen) return;
+        logOpen = false;
+        std::vector<std::pair<int, std::vector<int>>>().swap(logTipStates);
+        std::vector<std::pair<int, std::vector<double>>>().swap(logTipPartials);
+        std::vector<double>().swap(logWeights);
+    }
+    int makeChildren(const std::vector<std::pair<int, int>>& partitionRanges);
+    // the engine whose kernels and matrices speak for the instance: the only one, or the first child
+    Instance* first() const { return engine ? engine.get() : children.empty() ? nullptr : children[0].in.get(); }
+};
+
+// (plain pointers: instances a client never finalised are not torn down behind the runtime's back when the process ends)
+static std::vector<Handle*> g_instances;
+
+static Handle* lookup(int id)
+{
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (id < 0 || id >= (int) g_instances.size()) return nullptr;
+    return g_instances[id];
+}
+
+// Split the patterns into child engines: every partition range (start, count) is cut into one shard per device of
+// shardDevices (whole 64-pattern blocks, the last shard takes the remainder), then the recorded tip data and pattern
+// weights are replayed into the children.
+int Handle::makeChildren(const std::vector<std::pair<int, int>>& ranges)
+{
+    children.clear();
+    const int G = (int) shardDevices.size();
+    for (size_t p = 0; p < ranges.size(); ++p) {
+        const int start = ranges[p].first, count = ranges[p].second;
+        const int blocks = (count + 63) / 64;
+        const int g = std::max(1, std::min(G, blocks));
+        int done = 0;
+        for (int i = 0; i < g; ++i) {
+            const int b0 = (int) ((long) blocks * i / g), b1 = (int) ((long) blocks * (i + 1) / g);
+            const int n = (i == g - 1) ? count - done : (b1 - b0) * 64;
+            if (n <= 0) continue;
+            std::unique_ptr<Instance> c;
+            int rc = new_engine(c, dim, n, shardDevices[i % G], sw);
+            if (rc) { children.clear(); return rc; }
+            children.push_back(Child{std::move(c), Span{start + done, n, (int) p}});
+            done += n;
+        }
+    }
+    for (Child& ch : children) {
+        (void) hipSetDevice(ch.in->device);
+        for (auto& ts : logTipStates) { int rc = ch.in->setTipStates(ts.first, ts.second.data() + ch.span.start); if (rc) return rc; }
+        for (auto& tp : logTipPartials) { int rc = ch.in->importPartials(tp.first, tp.second.data() + (size_t) ch.span.start * dim.stateCount, false); if (rc) return rc; }
+        if (!logWeights.empty()) { int rc = ch.in->upload(ch.in->d_pweights, logWeights.data() + ch.span.start, sizeof(double) * ch.span.count); if (rc) return rc; }
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// Entry: the handle `h`, its first device made current, and `in`, the one single-precision engine behind it (null behind a
+// handle of children or of the double-precision engine: the bookkeeping below is that engine's)
 #define GET_INSTANCE_RAW(id)                                                                         \
-    Instance* in = lookup(id);                                                                       \
-    if (!in) return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "no such instance");                   \
-    (void) hipSetDevice(in->device)
+    Handle* h = lookup(id);                                                                          \
+    if (!h) return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "no such instance");                    \
+    (void) hipSetDevice(h->device);                                                                  \
+    Instance* const in = h->engine.get();                                                            \
+    (void) in
 // (a beagleResetScaleFactors that is still waiting for its beagleAccumulateScaleFactors -- see there -- runs before anything else)
 #define GET_INSTANCE_NOFLUSH(id)                                                                     \
     GET_INSTANCE_RAW(id);                                                                            \
-    if (in->deferredReset >= 0) {                                                                    \
+    if (in && in->deferredReset >= 0) {                                                              \
         int drc_ = in->runDeferredReset();                                                           \
         if (drc_ != BEAGLE_SUCCESS) return drc_;                                                     \
     }
 // every entry point except beagleUpdatePartials first runs the lists deferred so far
 #define GET_INSTANCE(id)                                                                             \
     GET_INSTANCE_NOFLUSH(id);                                                                        \
-    if (in->hasWork()) {                                                                             \
+    if (in && in->hasWork()) {                                                                       \
         int frc_ = in->flushPending();                                                               \
         if (frc_ != BEAGLE_SUCCESS) return frc_;                                                     \
     }
@@ -3233,53 +3247,55 @@ using namespace mbamd;
 // log-likelihood calls themselves leave a held 4-state path where it is (Instance::heldPath)
 #define GET_INSTANCE_KEEPING_PATH(id)                                                                \
     GET_INSTANCE_NOFLUSH(id);                                                                        \
-    if (in->hasWork(false)) {                                                                        \
+    if (in && in->hasWork(false)) {                                                                  \
         int frc_ = in->flushPending(true);                                                           \
         if (frc_ != BEAGLE_SUCCESS) return frc_;                                                     \
     }
-// a facade's call on every child, in order: its device made current, its deferred work run first (`flush`); the first error ends it
+// A call on the single-precision engines behind a handle, each with the patterns it holds: the one engine (the entry macro has
+// made its device current and run its deferred work), or every child in order -- its device made current, its deferred work
+// run first (`flush`); the first error ends it
 template <class F>
-static int each_child(Instance* in, bool flush, F&& call)
+static int each_engine(Handle* h, bool flush, F&& call)
 {
-    for (Instance::Child& ch : in->children) {
-        (void) hipSetDevice(ch.in->device);
-        if (flush && ch.in->hasWork()) {
-            int frc = ch.in->flushPending();
+    if (h->engine) return call(h->engine.get(), Handle::Span{0, h->dim.patternCount, 0});
+    for (Handle::Child& child : h->children) {
+        Instance* c = child.in.get();
+        (void) hipSetDevice(c->device);
+        if (flush && c->hasWork()) {
+            int frc = c->flushPending();
             if (frc != BEAGLE_SUCCESS) return frc;
         }
-        int crc = call(ch);
+        int crc = call(c, child.span);
         if (crc != BEAGLE_SUCCESS) return crc;
     }
     return BEAGLE_SUCCESS;
 }
+// ... as an expression of the engine `c` and its patterns `ch`, returned from the entry point
+#define EACH_ENGINE(FLUSH, ...)                                                                      \
+    return each_engine(h, FLUSH, [&](Instance* c, const Handle::Span& ch) { (void) c; (void) ch; return (int) (__VA_ARGS__); })
 // K rows of n values each between a child's [K][count][width] block and its pattern range of a client's [K][P][width] array
 template <class T>
 static void copy_rows(T* dst, size_t dstRow, const T* src, size_t srcRow, int K, size_t n)
 {
     for (int k = 0; k < K; ++k) std::memcpy(dst + (size_t) k * dstRow, src + (size_t) k * srcRow, n * sizeof(T));
 }
-// a facade forwards the call to every child (`c`, its pattern range in `ch`) and returns
-#define FACADE_EACH(FLUSH, ...)                                                                      \
-    if (in->facade())                                                                                \
-        return each_child(in, FLUSH, [&](Instance::Child& ch) { Instance* c = ch.in; (void) c; return (int) (__VA_ARGS__); })
-#define FACADE_ALL(...) FACADE_EACH(true, __VA_ARGS__)
 
-// the engine proper for one log-likelihood call; facade: per-child sums, FLOATING_POINT if any child says so
-static int integrate_any(Instance* in, const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
+// the engine proper for one log-likelihood call; children: per-child sums, FLOATING_POINT if any child says so
+static int integrate_any(Handle* h, const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
                          const int* cumIdx, int count, const int* partitionIndices, int partitionCount, double* outByPartition,
                          double* outSum)
 {
-    if (!in->facade()) return in->integrate(parent, child, prob, wIdx, fIdx, cumIdx, count, outSum);
+    if (h->engine) return h->engine->integrate(parent, child, prob, wIdx, fIdx, cumIdx, count, outSum);
     // arrays are laid out [count][partitionCount] when partitionIndices is given (reference src/mbbeagle.c:2781-2800)
     const int pc = partitionIndices ? partitionCount : 1;
     std::vector<int> pa(count), ca(count), pr(count), wa(count), fa(count), cu(count);
     std::vector<Instance*> launched;
     std::vector<int> slotOf;
-    for (Instance::Child& ch : in->children) {
+    for (Handle::Child& ch : h->children) {
         int dpos = 0;
         if (partitionIndices) {
             dpos = -1;
-            for (int d = 0; d < pc; ++d) if (partitionIndices[d] == ch.partition) dpos = d;
+            for (int d = 0; d < pc; ++d) if (partitionIndices[d] == ch.span.partition) dpos = d;
             if (dpos < 0) continue;                     // this partition is not part of the call
         }
         for (int i = 0; i < count; ++i) {
@@ -3288,7 +3304,7 @@ static int integrate_any(Instance* in, const int* parent, const int* child, cons
             cu[i] = cumIdx ? cumIdx[j] : BEAGLE_OP_NONE;
             if (child) { ca[i] = child[j]; pr[i] = prob[j]; }
         }
-        Instance* c = ch.in;
+        Instance* c = ch.in.get();
         (void) hipSetDevice(c->device);
         if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
         const bool was = c->deferred;
@@ -3313,7 +3329,6 @@ static int integrate_any(Instance* in, const int* parent, const int* child, cons
         if (outByPartition) outByPartition[slotOf[i]] += v;
     }
     if (outSum) *outSum = total;
-    in->haveSite = true;
     return result;
 }
 
@@ -3410,57 +3425,27 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         for (int i = 0; i < g; ++i) devices.push_back((first + i) % ndev);
     }
     const int dev = devices[0];
-    Instance* in = new Instance();
-    in->sw = sw;                                   // (a handle or facade keeps them too: its children are created from them)
-    in->flags = kSupport | (requirementFlags & (BEAGLE_FLAG_SCALING_ALWAYS | BEAGLE_FLAG_SCALING_DYNAMIC));
-    const int args[9] = {tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                         matrixBufferCount, categoryCount, scaleBufferCount};
-    std::memcpy(in->createArgs, args, sizeof args);
-    in->shardDevices = devices;
+    std::unique_ptr<Handle> h(new Handle());       // (a create that fails below takes whatever was made with it)
+    h->dim = Dims{tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount,
+                  categoryCount, scaleBufferCount};
+    h->flags = kSupport | (requirementFlags & (BEAGLE_FLAG_SCALING_ALWAYS | BEAGLE_FLAG_SCALING_DYNAMIC));
+    h->sw = sw;
+    h->device = dev;
+    h->shardDevices = devices;
     int rc;
     if (wantDouble) {
-        // the handle only: every entry point forwards to the fp64 engine (mbamd_f64.h); one device, no shards
-        in->device = dev;
-        in->S = stateCount; in->P = patternCount; in->K = categoryCount; in->nEigen = eigenBufferCount;
-        in->released = true;
-        in->flags = (in->flags & ~BEAGLE_FLAG_PRECISION_SINGLE) | BEAGLE_FLAG_PRECISION_DOUBLE;
-        in->f64 = new Engine64();
-        rc = in->f64->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                             matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
-    } else if (devices.size() > 1 && patternCount > 64) {
-        // facade from the start: dimensions only, the children own the device memory
-        in->device = dev;
-        in->tipCount = tipCount; in->nBuffers = partialsBufferCount + compactBufferCount; in->S = stateCount; in->P = patternCount;
-        in->Ppad = round_up(patternCount, 64); in->K = categoryCount; in->nEigen = eigenBufferCount; in->nMatrices = matrixBufferCount;
-        in->nScale = scaleBufferCount;
-        in->released = true;
-        rc = in->makeChildren(std::vector<std::pair<int, int>>(1, std::make_pair(0, patternCount)));
-    } else {
-        in->shardDevices.assign(1, dev);
-        rc = in->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                        matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
-        if (rc == BEAGLE_ERROR_OUT_OF_MEMORY && in->wg) {
-            // the arenas of the 20/61-state tree walk did not fit: once more on the level kernels (buffers allocated on first use)
-            const long fl = in->flags;
-            in->destroy();
-            delete in;
-            (void) hipGetLastError();
-            in = new Instance();
-            in->flags = fl;
-            in->noWalkG = true;
-            std::memcpy(in->createArgs, args, sizeof args);
-            in->shardDevices.assign(1, dev);
-            rc = in->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
+        // every entry point forwards to the fp64 engine (mbamd_f64.h); one device, no shards
+        h->flags = (h->flags & ~BEAGLE_FLAG_PRECISION_SINGLE) | BEAGLE_FLAG_PRECISION_DOUBLE;
+        h->f64.reset(new Engine64());
+        rc = h->f64->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
                             matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
-        }
+    } else if (devices.size() > 1 && patternCount > 64) {
+        rc = h->makeChildren(std::vector<std::pair<int, int>>(1, std::make_pair(0, patternCount)));      // pattern shards from the start
+    } else {
+        h->shardDevices.assign(1, dev);
+        rc = new_engine(h->engine, h->dim, patternCount, dev, sw);
     }
-    if (rc != BEAGLE_SUCCESS) {
-        in->destroyChildren();
-        if (!in->released) in->destroy();
-        delete in->f64;
-        delete in;
-        return rc;
-    }
+    if (rc != BEAGLE_SUCCESS) return rc;
     int id;
     {
         std::lock_guard<std::mutex> lk(g_mutex);
@@ -3469,60 +3454,58 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         for (size_t i = 0; i < g_instances.size(); ++i)
             if (!g_instances[i]) { id = (int) i; break; }
         if (id < 0) { id = (int) g_instances.size(); g_instances.push_back(nullptr); }
-        g_instances[id] = in;
+        g_instances[id] = h.get();
     }
     if (returnInfo) {
-        const Instance* first = in->facade() ? in->children[0].in : in;
+        const Instance* first = h->first();
         returnInfo->resourceNumber = dev;
         returnInfo->resourceName = (dev < g_resources.length) ? g_resources.list[dev].name : const_cast<char*>("HIP device");
-        returnInfo->implName = const_cast<char*>(first->f64 ? (first->S == 4 ? MBAMD_IMPL_NAME ": double-precision kernels (four states: tree walk)" : MBAMD_IMPL_NAME ": double-precision level kernels")
+        returnInfo->implName = const_cast<char*>(h->f64 ? (stateCount == 4 ? MBAMD_IMPL_NAME ": double-precision kernels (four states: tree walk)" : MBAMD_IMPL_NAME ": double-precision level kernels")
                                                  : first->s4 ? MBAMD_IMPL_NAME ": 4-state tree-walk kernels"
                                                  : first->wg ? (wg_bf16(first->S) ? MBAMD_IMPL_NAME ": general-state tree-walk kernels (fp32 arithmetic as three exact bf16 pieces on v_mfma_f32_32x32x16_bf16)"
                                                                                   : MBAMD_IMPL_NAME ": general-state tree-walk kernels (v_mfma_f32_32x32x2_f32)")
                                                  : first->mfma ? MBAMD_IMPL_NAME ": general-state MFMA (v_mfma_f32_32x32x2_f32) kernels"
                                                                : MBAMD_IMPL_NAME ": general-state vector kernels");
         returnInfo->implDescription = const_cast<char*>("hand-written HIP kernels for AMD CDNA4 (MI355X)");
-        returnInfo->flags = in->flags;
+        returnInfo->flags = h->flags;
     }
+    h.release();                                   // (now g_instances')
     return id;
 }
 
 int beagleFinalizeInstance(int instance)
 {
-    Instance* in;
+    std::unique_ptr<Handle> h;
     {
         std::lock_guard<std::mutex> lk(g_mutex);
         if (instance < 0 || instance >= (int) g_instances.size() || !g_instances[instance])
             return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "beagleFinalizeInstance: no such instance");
-        in = g_instances[instance];
+        h.reset(g_instances[instance]);
         g_instances[instance] = nullptr;
     }
     if (g_loadSwitches.stats) {
-        std::fprintf(stderr, "[mbamd] instance %d: plan cache %ld hits / %ld misses; tree-walk schedules re-used %llu / built %llu; root-ward paths held %ld, run with their log-likelihood as one launch %ld\n", instance,
-                     in->planHits, in->planMisses, (unsigned long long) in->scheduleHits, (unsigned long long) in->scheduleMisses, in->heldPaths, in->fusedPaths);
-        if (in->listsTotal)
-            std::fprintf(stderr, "[mbamd] instance %d: %d-state lists %ld: root-ward paths %ld (of them forked %ld), tree walks %ld (%.1f operations each)\n", instance,
-                         in->S, in->listsTotal, in->listsPath, in->forkedPaths, in->listsWalked, in->listsWalked ? (double) in->opsWalked / in->listsWalked : 0.0);
+        if (const Instance* in = h->engine.get()) {
+            std::fprintf(stderr, "[mbamd] instance %d: plan cache %ld hits / %ld misses; tree-walk schedules re-used %llu / built %llu; root-ward paths held %ld, run with their log-likelihood as one launch %ld\n", instance,
+                         in->planHits, in->planMisses, (unsigned long long) in->scheduleHits, (unsigned long long) in->scheduleMisses, in->heldPaths, in->fusedPaths);
+            if (in->listsTotal)
+                std::fprintf(stderr, "[mbamd] instance %d: %d-state lists %ld: root-ward paths %ld (of them forked %ld), tree walks %ld (%.1f operations each)\n", instance,
+                             in->S, in->listsTotal, in->listsPath, in->forkedPaths, in->listsWalked, in->listsWalked ? (double) in->opsWalked / in->listsWalked : 0.0);
+        }
         for (const ApiStats& a : g_stats)
             std::fprintf(stderr, "[mbamd]   %-34s %9ld calls %10.3f ms total %9.2f us/call\n", a.name, a.calls,
                          a.seconds * 1e3, a.calls ? a.seconds * 1e6 / a.calls : 0.0);
     }
-    in->destroyChildren();
-    if (!in->released) in->destroy();
-    delete in->f64;
-    delete in;
     return BEAGLE_SUCCESS;
 }
 
 int beagleFinalize(void)
 {
-    std::vector<Instance*> all;
+    std::vector<Handle*> all;
     {
         std::lock_guard<std::mutex> lk(g_mutex);
         all.swap(g_instances);
     }
-    for (Instance* in : all)
-        if (in) { in->destroyChildren(); if (!in->released) in->destroy(); delete in->f64; delete in; }
+    for (Handle* h : all) delete h;
     return BEAGLE_SUCCESS;
 }
 
@@ -3536,17 +3519,17 @@ int beagleSetCPUThreadCount(int instance, int threadCount)
 }
 
 // v3 multi-partition mode (reference src/mcmc.c:6464): patternPartitions[c] = partition of pattern c, partitions are
-// contiguous pattern ranges (MrBayes lists its divisions one after the other).  From here on the instance is a facade over
-// one child per partition (times the shards); tip data and pattern weights set so far are replayed into the children.
+// contiguous pattern ranges (MrBayes lists its divisions one after the other).  From here on the handle owns one child engine
+// per partition (times the shards); tip data and pattern weights set so far are replayed into the children.
 int beagleSetPatternPartitions(int instance, int partitionCount, const int* inPatternPartitions)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return (partitionCount < 1 || !inPatternPartitions) ? fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: arguments") : in->f64->setPartitions(partitionCount, inPatternPartitions);
+    if (h->f64) return (partitionCount < 1 || !inPatternPartitions) ? fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: arguments") : h->f64->setPartitions(partitionCount, inPatternPartitions);
     API_TRACE("beagleSetPatternPartitions(%d partitions)", partitionCount);
     if (partitionCount < 1 || !inPatternPartitions) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: arguments");
-    if (!in->logOpen) return fail(BEAGLE_ERROR_GENERAL, "beagleSetPatternPartitions: call it before the first matrix / partials update");
+    if (!h->logOpen) return fail(BEAGLE_ERROR_GENERAL, "beagleSetPatternPartitions: call it before the first matrix / partials update");
     std::vector<std::pair<int, int>> ranges;
-    for (int c = 0; c < in->P; ++c) {
+    for (int c = 0; c < h->dim.patternCount; ++c) {
         const int p = inPatternPartitions[c];
         if (p < 0 || p >= partitionCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: partition index");
         if ((int) ranges.size() == p) ranges.emplace_back(c, 1);
@@ -3554,72 +3537,69 @@ int beagleSetPatternPartitions(int instance, int partitionCount, const int* inPa
         else return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleSetPatternPartitions: partitions must be contiguous, increasing pattern ranges");
     }
     if ((int) ranges.size() != partitionCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: empty partition");
-    in->partitionCount = partitionCount;
-    if (partitionCount == 1 && !in->facade()) return BEAGLE_SUCCESS;
-    if (!in->released) {                          // hand the single-partition buffers back
-        in->destroy();
-        in->released = true;
-    }
-    return in->makeChildren(ranges);
+    h->partitionCount = partitionCount;
+    if (partitionCount == 1 && in) return BEAGLE_SUCCESS;
+    h->engine.reset();                            // hand the single-partition buffers back
+    return h->makeChildren(ranges);
 }
 
 int beagleSetTipStates(int instance, int tipIndex, const int* inStates)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setTipStates(tipIndex, inStates);
-    API_TRACE("beagleSetTipStates(tip=%d, states=%s...)", tipIndex, trace_ints(inStates, std::min(8, in->P)).c_str());
-    if (in->logOpen) in->logTipStates.emplace_back(tipIndex, std::vector<int>(inStates, inStates + in->P));
-    FACADE_ALL(c->setTipStates(tipIndex, inStates + ch.start));
-    return in->setTipStates(tipIndex, inStates);
+    if (h->f64) return h->f64->setTipStates(tipIndex, inStates);
+    const int P = h->dim.patternCount;
+    API_TRACE("beagleSetTipStates(tip=%d, states=%s...)", tipIndex, trace_ints(inStates, std::min(8, P)).c_str());
+    if (h->logOpen) h->logTipStates.emplace_back(tipIndex, std::vector<int>(inStates, inStates + P));
+    EACH_ENGINE(true, c->setTipStates(tipIndex, inStates + ch.start));
 }
 int beagleSetTipPartials(int instance, int tipIndex, const double* inPartials)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setPartials(tipIndex, inPartials, false);
-    API_TRACE("beagleSetTipPartials(tip=%d, %s...)", tipIndex, trace_doubles(inPartials, std::min(8, in->S)).c_str());
-    if (in->logOpen) in->logTipPartials.emplace_back(tipIndex, std::vector<double>(inPartials, inPartials + (size_t) in->P * in->S));
-    FACADE_ALL(c->importPartials(tipIndex, inPartials + (size_t) ch.start * in->S, false));
-    return in->importPartials(tipIndex, inPartials, false);
+    if (h->f64) return h->f64->setPartials(tipIndex, inPartials, false);
+    const size_t S = (size_t) h->dim.stateCount;
+    API_TRACE("beagleSetTipPartials(tip=%d, %s...)", tipIndex, trace_doubles(inPartials, std::min(8, h->dim.stateCount)).c_str());
+    if (h->logOpen) h->logTipPartials.emplace_back(tipIndex, std::vector<double>(inPartials, inPartials + (size_t) h->dim.patternCount * S));
+    EACH_ENGINE(true, c->importPartials(tipIndex, inPartials + (size_t) ch.start * S, false));
 }
 int beagleSetPartials(int instance, int bufferIndex, const double* inPartials)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setPartials(bufferIndex, inPartials, true);
+    if (h->f64) return h->f64->setPartials(bufferIndex, inPartials, true);
+    if (in) return in->importPartials(bufferIndex, inPartials, true);
+    // children: each takes the [K][count][S] block of its pattern range
     std::vector<double> part;
-    const size_t S = (size_t) in->S;
-    if (in->facade())
-        return each_child(in, false, [&](Instance::Child& ch) {
-            part.resize((size_t) in->K * ch.count * S);
-            copy_rows(part.data(), ch.count * S, inPartials + ch.start * S, in->P * S, in->K, ch.count * S);
-            return ch.in->importPartials(bufferIndex, part.data(), true);
-        });
-    return in->importPartials(bufferIndex, inPartials, true);
+    const size_t S = (size_t) h->dim.stateCount, P = (size_t) h->dim.patternCount;
+    const int K = h->dim.categoryCount;
+    return each_engine(h, false, [&](Instance* c, const Handle::Span& ch) {
+        part.resize((size_t) K * ch.count * S);
+        copy_rows(part.data(), ch.count * S, inPartials + ch.start * S, P * S, K, ch.count * S);
+        return c->importPartials(bufferIndex, part.data(), true);
+    });
 }
 int beagleGetPartials(int instance, int bufferIndex, int scaleIndex, double* outPartials)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->getPartials(bufferIndex, outPartials);
+    if (h->f64) return h->f64->getPartials(bufferIndex, outPartials);
     if (scaleIndex != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleGetPartials: scaleIndex must be BEAGLE_OP_NONE");
+    if (in) return in->getPartials(bufferIndex, outPartials);
     std::vector<double> part;
-    const size_t S = (size_t) in->S;
-    if (in->facade())
-        return each_child(in, true, [&](Instance::Child& ch) {
-            part.resize((size_t) in->K * ch.count * S);
-            const int rc = ch.in->getPartials(bufferIndex, part.data());
-            if (rc == BEAGLE_SUCCESS) copy_rows(outPartials + ch.start * S, in->P * S, part.data(), ch.count * S, in->K, ch.count * S);
-            return rc;
-        });
-    return in->getPartials(bufferIndex, outPartials);
+    const size_t S = (size_t) h->dim.stateCount, P = (size_t) h->dim.patternCount;
+    const int K = h->dim.categoryCount;
+    return each_engine(h, true, [&](Instance* c, const Handle::Span& ch) {
+        part.resize((size_t) K * ch.count * S);
+        const int rc = c->getPartials(bufferIndex, part.data());
+        if (rc == BEAGLE_SUCCESS) copy_rows(outPartials + ch.start * S, P * S, part.data(), ch.count * S, K, ch.count * S);
+        return rc;
+    });
 }
 int beagleSetEigenDecomposition(int instance, int eigenIndex, const double* inEigenVectors,
                                 const double* inInverseEigenVectors, const double* inEigenValues)
 {
     StatTimer st_(ST_SET);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setEigen(eigenIndex, inEigenVectors, inInverseEigenVectors, inEigenValues);
-    API_TRACE("beagleSetEigenDecomposition(eigen=%d, values=%s...)", eigenIndex, trace_doubles(inEigenValues, std::min(6, in->S)).c_str());
-    FACADE_ALL(c->setEigen(eigenIndex, inEigenVectors, inInverseEigenVectors, inEigenValues));
-    return in->setEigen(eigenIndex, inEigenVectors, inInverseEigenVectors, inEigenValues);
+    if (h->f64) return h->f64->setEigen(eigenIndex, inEigenVectors, inInverseEigenVectors, inEigenValues);
+    API_TRACE("beagleSetEigenDecomposition(eigen=%d, values=%s...)", eigenIndex, trace_doubles(inEigenValues, std::min(6, h->dim.stateCount)).c_str());
+    EACH_ENGINE(true, c->setEigen(eigenIndex, inEigenVectors, inInverseEigenVectors, inEigenValues));
 }
 // extension: eigen-systems of `count` reversible rate matrices computed on the device and stored in the eigen
 // buffers firstEigenIndex ...; q: count x S x S row-major rates (mode 0) or exchangeabilities (mode 1: Q is built and
@@ -3628,65 +3608,58 @@ int beagleSetEigenDecomposition(int instance, int eigenIndex, const double* inEi
 int mbamdSetRateMatrices(int instance, int firstEigenIndex, int count, const double* q, const double* pi, int mode)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetRateMatrices: not on a double-precision instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetRateMatrices: not on a double-precision instance");
     if (!q || !pi || (mode != 0 && mode != 1)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdSetRateMatrices: arguments");
-    FACADE_ALL(c->setRateMatrices(firstEigenIndex, count, q, pi, mode));
-    return in->setRateMatrices(firstEigenIndex, count, q, pi, mode);
+    EACH_ENGINE(true, c->setRateMatrices(firstEigenIndex, count, q, pi, mode));
 }
 int mbamdSetRateMatricesFrom(int instance, int firstEigenIndex, int count, const double* q, const double* pi, int mode, int warmFirstEigenIndex)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetRateMatricesFrom: not on a double-precision instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetRateMatricesFrom: not on a double-precision instance");
     if (!q || !pi) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdSetRateMatricesFrom: null");
-    FACADE_ALL(c->setRateMatrices(firstEigenIndex, count, q, pi, mode, warmFirstEigenIndex));
-    return in->setRateMatrices(firstEigenIndex, count, q, pi, mode, warmFirstEigenIndex);
+    EACH_ENGINE(true, c->setRateMatrices(firstEigenIndex, count, q, pi, mode, warmFirstEigenIndex));
 }
 int beagleSetStateFrequencies(int instance, int idx, const double* f)
 {
     StatTimer st_(ST_SET);
     GET_INSTANCE_KEEPING_PATH(instance);
-    if (in->f64) return in->f64->setFreqs(idx, f);
-    API_TRACE("beagleSetStateFrequencies(%d, %s...)", idx, trace_doubles(f, std::min(6, in->S)).c_str());
-    if (idx < 0 || idx >= in->nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetStateFrequencies: index");
-    FACADE_ALL(c->uploadIfChanged(c->h_freqs, (size_t) idx * c->S, c->d_freqs, f, c->S));
-    return in->uploadIfChanged(in->h_freqs, (size_t) idx * in->S, in->d_freqs, f, in->S);
+    if (h->f64) return h->f64->setFreqs(idx, f);
+    API_TRACE("beagleSetStateFrequencies(%d, %s...)", idx, trace_doubles(f, std::min(6, h->dim.stateCount)).c_str());
+    if (idx < 0 || idx >= h->dim.eigenBufferCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetStateFrequencies: index");
+    EACH_ENGINE(true, c->uploadIfChanged(c->h_freqs, (size_t) idx * c->S, c->d_freqs, f, c->S));
 }
 int beagleSetCategoryWeights(int instance, int idx, const double* w)
 {
     StatTimer st_(ST_SET);
     GET_INSTANCE_KEEPING_PATH(instance);
-    if (in->f64) return in->f64->setWeights(idx, w);
-    API_TRACE("beagleSetCategoryWeights(%d, %s)", idx, trace_doubles(w, in->K).c_str());
-    if (idx < 0 || idx >= in->nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetCategoryWeights: index");
-    FACADE_ALL(c->uploadIfChanged(c->h_weights, (size_t) idx * c->K, c->d_weights, w, c->K));
-    return in->uploadIfChanged(in->h_weights, (size_t) idx * in->K, in->d_weights, w, in->K);
+    if (h->f64) return h->f64->setWeights(idx, w);
+    API_TRACE("beagleSetCategoryWeights(%d, %s)", idx, trace_doubles(w, h->dim.categoryCount).c_str());
+    if (idx < 0 || idx >= h->dim.eigenBufferCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetCategoryWeights: index");
+    EACH_ENGINE(true, c->uploadIfChanged(c->h_weights, (size_t) idx * c->K, c->d_weights, w, c->K));
 }
 int beagleSetCategoryRates(int instance, const double* r)
 {
     StatTimer st_(ST_SET);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setRates(0, r);
-    API_TRACE("beagleSetCategoryRates(%s)", trace_doubles(r, in->K).c_str());
-    FACADE_ALL(c->setRates(0, r));
-    return in->setRates(0, r);
+    if (h->f64) return h->f64->setRates(0, r);
+    API_TRACE("beagleSetCategoryRates(%s)", trace_doubles(r, h->dim.categoryCount).c_str());
+    EACH_ENGINE(true, c->setRates(0, r));
 }
 // v3 (reference src/mbbeagle.c:2055): one rate vector per partition, named by index in beagleUpdateTransitionMatricesWithMultipleModels
 int beagleSetCategoryRatesWithIndex(int instance, int categoryRatesIndex, const double* r)
 {
     StatTimer st_(ST_SET);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setRates(categoryRatesIndex, r);
-    API_TRACE("beagleSetCategoryRatesWithIndex(%d, %s)", categoryRatesIndex, trace_doubles(r, in->K).c_str());
-    FACADE_ALL(c->setRates(categoryRatesIndex, r));
-    return in->setRates(categoryRatesIndex, r);
+    if (h->f64) return h->f64->setRates(categoryRatesIndex, r);
+    API_TRACE("beagleSetCategoryRatesWithIndex(%d, %s)", categoryRatesIndex, trace_doubles(r, h->dim.categoryCount).c_str());
+    EACH_ENGINE(true, c->setRates(categoryRatesIndex, r));
 }
 int beagleSetPatternWeights(int instance, const double* w)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setPatternWeights(w);
-    if (in->logOpen) in->logWeights.assign(w, w + in->P);
-    FACADE_ALL(c->upload(c->d_pweights, w + ch.start, sizeof(double) * ch.count));
-    return in->upload(in->d_pweights, w, sizeof(double) * in->P);
+    if (h->f64) return h->f64->setPatternWeights(w);
+    if (h->logOpen) h->logWeights.assign(w, w + h->dim.patternCount);
+    EACH_ENGINE(true, c->upload(c->d_pweights, w + ch.start, sizeof(double) * ch.count));
 }
 int beagleUpdateTransitionMatrices(int instance, int eigenIndex, const int* probabilityIndices,
                                    const int* firstDerivativeIndices, const int* secondDerivativeIndices,
@@ -3694,19 +3667,19 @@ int beagleUpdateTransitionMatrices(int instance, int eigenIndex, const int* prob
 {
     StatTimer st_(ST_MATRICES);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return in->f64->updateMatrices(eigenIndex, 0, probabilityIndices, edgeLengths, count);
+    if (h->f64) return h->f64->updateMatrices(eigenIndex, 0, probabilityIndices, edgeLengths, count);
     API_TRACE("beagleUpdateTransitionMatrices(eigen=%d, count=%d, indices=%s..., lengths=%s...)", eigenIndex, count,
               trace_ints(probabilityIndices, std::min(6, count)).c_str(), trace_doubles(edgeLengths, std::min(6, count)).c_str());
     if (firstDerivativeIndices || secondDerivativeIndices)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatrices: derivatives");
-    in->closeLog();
-    FACADE_EACH(false, (!c->hasPending() ? BEAGLE_SUCCESS : c->flushPending()) != BEAGLE_SUCCESS
-                           ? BEAGLE_ERROR_GENERAL : c->updateMatrices(eigenIndex, probabilityIndices, edgeLengths, count));
-    if (in->hasPending()) {                      // deferred lists read the matrices about to be replaced
-        int frc_ = in->flushPending();
-        if (frc_ != BEAGLE_SUCCESS) return frc_;
-    }
-    return in->updateMatrices(eigenIndex, probabilityIndices, edgeLengths, count);
+    h->closeLog();
+    return each_engine(h, false, [&](Instance* c, const Handle::Span&) {
+        if (c->hasPending()) {                   // deferred lists read the matrices about to be replaced
+            int frc_ = c->flushPending();
+            if (frc_ != BEAGLE_SUCCESS) return in ? frc_ : (int) BEAGLE_ERROR_GENERAL;      // (a child's failed flush is reported as a general error)
+        }
+        return c->updateMatrices(eigenIndex, probabilityIndices, edgeLengths, count);
+    });
 }
 // v3 (reference src/mbbeagle.c:2140-2147): every matrix names its own eigen-system and category-rate vector
 int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* eigenIndices, const int* categoryRateIndices,
@@ -3715,13 +3688,13 @@ int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* ei
 {
     StatTimer st_(ST_MATRICES);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return (firstDerivativeIndices || secondDerivativeIndices) ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatricesWithMultipleModels: derivatives") : in->f64->updateMatricesMulti(eigenIndices, categoryRateIndices, probabilityIndices, edgeLengths, count);
+    if (h->f64) return (firstDerivativeIndices || secondDerivativeIndices) ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatricesWithMultipleModels: derivatives") : h->f64->updateMatricesMulti(eigenIndices, categoryRateIndices, probabilityIndices, edgeLengths, count);
     API_TRACE("beagleUpdateTransitionMatricesWithMultipleModels(count=%d, eigen=%s..., rates=%s...)", count,
               trace_ints(eigenIndices, std::min(6, count)).c_str(), trace_ints(categoryRateIndices, std::min(6, count)).c_str());
     if (firstDerivativeIndices || secondDerivativeIndices)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatricesWithMultipleModels: derivatives");
-    in->closeLog();
-    auto run = [&](Instance* c) {
+    h->closeLog();
+    return each_engine(h, false, [&](Instance* c, const Handle::Span&) {
         if (c->hasPending()) { int frc = c->flushPending(); if (frc) return frc; }
         int i = 0;
         while (i < count) {                      // runs of equal (eigen-system, rate vector)
@@ -3732,41 +3705,36 @@ int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* ei
             i = j;
         }
         return (int) BEAGLE_SUCCESS;
-    };
-    FACADE_EACH(false, run(c));
-    return run(in);
+    });
 }
 int beagleSetTransitionMatrix(int instance, int matrixIndex, const double* inMatrix, double paddedValue)
 {
     (void) paddedValue;
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->setMatrix(matrixIndex, inMatrix);
-    FACADE_ALL(c->setMatrix(matrixIndex, inMatrix));
-    return in->setMatrix(matrixIndex, inMatrix);
+    if (h->f64) return h->f64->setMatrix(matrixIndex, inMatrix);
+    EACH_ENGINE(true, c->setMatrix(matrixIndex, inMatrix));
 }
 int beagleGetTransitionMatrix(int instance, int matrixIndex, double* outMatrix)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->getMatrix(matrixIndex, outMatrix);
-    if (in->facade()) {
-        Instance* c = in->children[0].in;
-        (void) hipSetDevice(c->device);
-        if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
-        return c->getMatrix(matrixIndex, outMatrix);
-    }
-    return in->getMatrix(matrixIndex, outMatrix);
+    if (h->f64) return h->f64->getMatrix(matrixIndex, outMatrix);
+    if (in) return in->getMatrix(matrixIndex, outMatrix);
+    Instance* c = h->first();                    // every child holds the same matrices: the first one answers
+    if (!c) return fail(BEAGLE_ERROR_GENERAL, "beagleGetTransitionMatrix: the instance has no engine");
+    (void) hipSetDevice(c->device);
+    if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
+    return c->getMatrix(matrixIndex, outMatrix);
 }
 int beagleUpdatePartials(int instance, const BeagleOperation* operations, int operationCount, int cumulativeScaleIndex)
 {
     StatTimer st_(ST_PARTIALS);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return in->f64->updatePartials(operations, operationCount, cumulativeScaleIndex);
+    if (h->f64) return h->f64->updatePartials(operations, operationCount, cumulativeScaleIndex);
     API_TRACE("beagleUpdatePartials(count=%d, cumulative=%d, first=%s, last=%s)", operationCount, cumulativeScaleIndex,
               trace_ints(reinterpret_cast<const int*>(operations), operationCount > 0 ? 7 : 0).c_str(),
               trace_ints(reinterpret_cast<const int*>(operations + std::max(0, operationCount - 1)), operationCount > 0 ? 7 : 0).c_str());
-    in->closeLog();
-    FACADE_EACH(false, c->updatePartials(operations, operationCount, cumulativeScaleIndex));
-    return in->updatePartials(operations, operationCount, cumulativeScaleIndex);
+    h->closeLog();
+    EACH_ENGINE(false, c->updatePartials(operations, operationCount, cumulativeScaleIndex));
 }
 // v3 (reference src/mbbeagle.c:2292, 2440, 2616): operations of several partitions in one array; every operation names its
 // partition and its cumulative scale buffer.  Each partition's operations, in order, are one list for that partition's child.
@@ -3774,13 +3742,16 @@ int beagleUpdatePartialsByPartition(int instance, const BeagleOperationByPartiti
 {
     StatTimer st_(ST_PARTIALS);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) {
+    if (h->f64) {
         std::vector<int> part((size_t) std::max(operationCount, 0)), cum((size_t) std::max(operationCount, 0));
         for (int i = 0; i < operationCount; ++i) { part[i] = operations[i].partition; cum[i] = operations[i].cumulativeScaleIndex; }
-        return in->f64->updatePartialsEx(operations, sizeof(BeagleOperationByPartition), operationCount, part.data(), cum.data());
+        return h->f64->updatePartialsEx(operations, sizeof(BeagleOperationByPartition), operationCount, part.data(), cum.data());
     }
     API_TRACE("beagleUpdatePartialsByPartition(count=%d)", operationCount);
-    in->closeLog();
+    h->closeLog();
+    if (in)
+        for (int i = 0; i < operationCount; ++i)
+            if (operations[i].partition != 0) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartialsByPartition: partition index (no partitions were set)");
     std::vector<BeagleOperation> list;
     auto runFor = [&](Instance* c, int partition) {
         int i = 0;
@@ -3801,44 +3772,36 @@ int beagleUpdatePartialsByPartition(int instance, const BeagleOperationByPartiti
         }
         return (int) BEAGLE_SUCCESS;
     };
-    FACADE_EACH(false, runFor(c, in->partitionCount > 1 ? ch.partition : -1));
-    for (int i = 0; i < operationCount; ++i)
-        if (operations[i].partition != 0) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePartialsByPartition: partition index (no partitions were set)");
-    return runFor(in, -1);
+    EACH_ENGINE(false, runFor(c, h->partitionCount > 1 ? ch.partition : -1));
+}
+// everything queued so far has run (beagleWaitForPartials, mbamdSynchronize)
+static int synchronize(Handle* h)
+{
+    if (h->f64) return h->f64->synchronize();
+    if (h->engine) { HIP_TRY(hipStreamSynchronize(h->engine->stream)); return BEAGLE_SUCCESS; }       // (an error carries HIP's text)
+    EACH_ENGINE(true, hipStreamSynchronize(c->stream) == hipSuccess ? BEAGLE_SUCCESS : BEAGLE_ERROR_GENERAL);
 }
 int beagleWaitForPartials(int instance, const int* destinationPartials, int destinationPartialsCount)
 {
     (void) destinationPartials; (void) destinationPartialsCount;
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->synchronize();
-    FACADE_ALL(hipStreamSynchronize(c->stream) == hipSuccess ? BEAGLE_SUCCESS : BEAGLE_ERROR_GENERAL);
-    HIP_TRY(hipStreamSynchronize(in->stream));
-    return BEAGLE_SUCCESS;
+    return synchronize(h);
 }
 
 // scale-factor bookkeeping; `partition` < 0: all patterns
-static int scale_accumulate(Instance* in, const int* scaleIndices, int count, int cumulativeScaleIndex, int sign, int partition)
+static int scale_accumulate(Handle* h, const int* scaleIndices, int count, int cumulativeScaleIndex, int sign, int partition)
 {
-    // queued 20/61-state lists run first unless the call commutes with them (MrBayes removes the old node factors of
-    // eigen-system part j+1 between the lists of parts j and j+1: flushing there would undo the merge of the parts)
-    auto one = [&](Instance* c) -> int {
-        (void) hipSetDevice(c->device);
+    return each_engine(h, false, [&](Instance* c, const Handle::Span& ch) -> int {
+        if (partition >= 0 && h->partitionCount > 1 && ch.partition != partition) return BEAGLE_SUCCESS;
+        // queued 20/61-state lists run first unless the call commutes with them (MrBayes removes the old node factors of
+        // eigen-system part j+1 between the lists of parts j and j+1: flushing there would undo the merge of the parts)
         if (c->hasPending() && !(c->wg && c->scaleOpsIndependentOfPending(scaleIndices, count, cumulativeScaleIndex))) {
             int frc = c->flushPending();
             if (frc != BEAGLE_SUCCESS) return frc;
         }
         return c->arena() ? c->accumulate4(scaleIndices, count, cumulativeScaleIndex, sign)
                           : c->accumulate(scaleIndices, count, cumulativeScaleIndex, sign);
-    };
-    if (in->facade()) {
-        for (Instance::Child& ch : in->children) {
-            if (partition >= 0 && in->partitionCount > 1 && ch.partition != partition) continue;
-            const int rc = one(ch.in);
-            if (rc != BEAGLE_SUCCESS) return rc;
-        }
-        return BEAGLE_SUCCESS;
-    }
-    return one(in);
+    });
 }
 static int scale_reset(Instance* in, int idx)
 {
@@ -3894,7 +3857,7 @@ int beagleAccumulateScaleFactors(int instance, const int* scaleIndices, int coun
     GET_INSTANCE_RAW(instance);
     // Reset + Accumulate of one cumulative buffer, back to back (rescaling the MrBayes way, reference src/mbbeagle.c:1080-1098): the
     // reset was not launched -- this launch stores instead of adding
-    if (in->deferredReset >= 0) {
+    if (in && in->deferredReset >= 0) {
         bool fuse = in->deferredReset == cumulativeScaleIndex && count > 0;
         for (int i = 0; fuse && i < count; ++i)
             if (scaleIndices[i] == cumulativeScaleIndex) fuse = false;     // (the buffer among its own sources: reset-then-add, not a store)
@@ -3909,90 +3872,88 @@ int beagleAccumulateScaleFactors(int instance, const int* scaleIndices, int coun
         int drc = in->runDeferredReset();
         if (drc != BEAGLE_SUCCESS) return drc;
     }
-    if (in->f64) return in->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, +1);
-    return scale_accumulate(in, scaleIndices, count, cumulativeScaleIndex, +1, -1);
+    if (h->f64) return h->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, +1);
+    return scale_accumulate(h, scaleIndices, count, cumulativeScaleIndex, +1, -1);
 }
 int beagleRemoveScaleFactors(int instance, const int* scaleIndices, int count, int cumulativeScaleIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return in->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, -1);
-    return scale_accumulate(in, scaleIndices, count, cumulativeScaleIndex, -1, -1);
+    if (h->f64) return h->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, -1);
+    return scale_accumulate(h, scaleIndices, count, cumulativeScaleIndex, -1, -1);
 }
 int beagleResetScaleFactors(int instance, int cumulativeScaleIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->resetScale(cumulativeScaleIndex);
-    FACADE_ALL(scale_reset(c, cumulativeScaleIndex));
-    // the level-kernel path (int32 buffers): wait for the call that follows -- if it is beagleAccumulateScaleFactors into this buffer,
-    // one launch does both (any other entry point runs the reset first: GET_INSTANCE_NOFLUSH)
-    if (!in->arena() && cumulativeScaleIndex >= 0 && cumulativeScaleIndex < in->nScale && in->scale[cumulativeScaleIndex]) {
+    if (h->f64) return h->f64->resetScale(cumulativeScaleIndex);
+    // one engine on the level-kernel path (int32 buffers): wait for the call that follows -- if it is beagleAccumulateScaleFactors into
+    // this buffer, one launch does both (any other entry point runs the reset first: GET_INSTANCE_NOFLUSH).  Children reset at once.
+    if (in && !in->arena() && cumulativeScaleIndex >= 0 && cumulativeScaleIndex < in->nScale && in->scale[cumulativeScaleIndex]) {
         in->deferredReset = cumulativeScaleIndex;
         return BEAGLE_SUCCESS;
     }
-    return scale_reset(in, cumulativeScaleIndex);
+    EACH_ENGINE(true, scale_reset(c, cumulativeScaleIndex));
 }
 int beagleCopyScaleFactors(int instance, int destScalingIndex, int srcScalingIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->copyScale(destScalingIndex, srcScalingIndex);
-    FACADE_ALL(scale_copy(c, destScalingIndex, srcScalingIndex));
-    return scale_copy(in, destScalingIndex, srcScalingIndex);
+    if (h->f64) return h->f64->copyScale(destScalingIndex, srcScalingIndex);
+    EACH_ENGINE(true, scale_copy(c, destScalingIndex, srcScalingIndex));
 }
 // v3 (reference src/likelihood.c:8096-8103, src/mbbeagle.c:2566): the same on one partition's patterns
 int beagleAccumulateScaleFactorsByPartition(int instance, const int* scaleIndices, int count, int cumulativeScaleIndex, int partitionIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return in->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, +1, partitionIndex);
-    return scale_accumulate(in, scaleIndices, count, cumulativeScaleIndex, +1, partitionIndex);
+    if (h->f64) return h->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, +1, partitionIndex);
+    return scale_accumulate(h, scaleIndices, count, cumulativeScaleIndex, +1, partitionIndex);
 }
 int beagleRemoveScaleFactorsByPartition(int instance, const int* scaleIndices, int count, int cumulativeScaleIndex, int partitionIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return in->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, -1, partitionIndex);
-    return scale_accumulate(in, scaleIndices, count, cumulativeScaleIndex, -1, partitionIndex);
+    if (h->f64) return h->f64->accumulateScale(scaleIndices, count, cumulativeScaleIndex, -1, partitionIndex);
+    return scale_accumulate(h, scaleIndices, count, cumulativeScaleIndex, -1, partitionIndex);
 }
 int beagleResetScaleFactorsByPartition(int instance, int cumulativeScaleIndex, int partitionIndex)
 {
     StatTimer st_(ST_SCALE);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->resetScale(cumulativeScaleIndex, partitionIndex);
-    FACADE_ALL((in->partitionCount > 1 && ch.partition != partitionIndex) ? BEAGLE_SUCCESS : scale_reset(c, cumulativeScaleIndex));
-    return scale_reset(in, cumulativeScaleIndex);
+    if (h->f64) return h->f64->resetScale(cumulativeScaleIndex, partitionIndex);
+    EACH_ENGINE(true, (h->partitionCount > 1 && ch.partition != partitionIndex) ? BEAGLE_SUCCESS : scale_reset(c, cumulativeScaleIndex));
 }
 // engine extension: the binary exponents behind a scale buffer, out[k * patternCount + c] (the general-state
 // path keeps one exponent per pattern: every category row is the same)
 int mbamdGetScaleExponents(int instance, int srcScalingIndex, int* out)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->getScaleExponents(srcScalingIndex, out);
+    if (h->f64) return h->f64->getScaleExponents(srcScalingIndex, out);
+    if (in) return in->getScaleExponents(srcScalingIndex, out);
     std::vector<int> part;
-    if (in->facade())
-        return each_child(in, true, [&](Instance::Child& ch) {
-            part.resize((size_t) in->K * ch.count);
-            const int rc = ch.in->getScaleExponents(srcScalingIndex, part.data());
-            if (rc == BEAGLE_SUCCESS) copy_rows(out + ch.start, (size_t) in->P, part.data(), (size_t) ch.count, in->K, (size_t) ch.count);
-            return rc;
-        });
-    return in->getScaleExponents(srcScalingIndex, out);
+    const int K = h->dim.categoryCount;
+    return each_engine(h, true, [&](Instance* c, const Handle::Span& ch) {
+        part.resize((size_t) K * ch.count);
+        const int rc = c->getScaleExponents(srcScalingIndex, part.data());
+        if (rc == BEAGLE_SUCCESS) copy_rows(out + ch.start, (size_t) h->dim.patternCount, part.data(), (size_t) ch.count, K, (size_t) ch.count);
+        return rc;
+    });
 }
 // BEAGLE's scale factors are one log value per pattern.  The 4-state path keeps an exponent per (pattern, category):
 // reported here is the largest of a pattern's exponents (times ln 2), the factor a per-pattern scaler would have used.
 int beagleGetScaleFactors(int instance, int srcScalingIndex, double* outScaleFactors)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->getScaleFactors(srcScalingIndex, outScaleFactors);
-    if (srcScalingIndex < 0 || srcScalingIndex >= in->nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleGetScaleFactors: index");
-    std::vector<int> e((size_t) in->K * in->P);
+    if (h->f64) return h->f64->getScaleFactors(srcScalingIndex, outScaleFactors);
+    if (srcScalingIndex < 0 || srcScalingIndex >= h->dim.scaleBufferCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleGetScaleFactors: index");
+    const int K = h->dim.categoryCount, P = h->dim.patternCount;
+    std::vector<int> e((size_t) K * P);
     int rc = mbamdGetScaleExponents(instance, srcScalingIndex, e.data());
     if (rc) return rc;
-    for (int c = 0; c < in->P; ++c) {
+    for (int c = 0; c < P; ++c) {
         int m = e[c];
-        for (int k = 1; k < in->K; ++k) m = std::max(m, e[(size_t) k * in->P + c]);
+        for (int k = 1; k < K; ++k) m = std::max(m, e[(size_t) k * P + c]);
         outScaleFactors[c] = (double) m * 0.69314718055994530942;
     }
     return BEAGLE_SUCCESS;
@@ -4003,8 +3964,8 @@ int beagleCalculateRootLogLikelihoods(int instance, const int* bufferIndices, co
 {
     StatTimer st_(ST_LNL);
     GET_INSTANCE_KEEPING_PATH(instance);
-    if (in->f64) return in->f64->logLikelihoods(bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
-    const int rc_ = integrate_any(in, bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices,
+    if (h->f64) return h->f64->logLikelihoods(bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
+    const int rc_ = integrate_any(h, bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices,
                                   cumulativeScaleIndices, count, nullptr, 1, nullptr, outSumLogLikelihood);
     API_TRACE("beagleCalculateRootLogLikelihoods(buffers=%s, weights=%s, freqs=%s, cumulative=%s) -> %d, lnL %.6f",
               trace_ints(bufferIndices, count).c_str(), trace_ints(categoryWeightsIndices, count).c_str(),
@@ -4023,8 +3984,8 @@ int beagleCalculateEdgeLogLikelihoods(int instance, const int* parentBufferIndic
     GET_INSTANCE_KEEPING_PATH(instance);
     if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivative || outSumSecondDerivative)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoods: derivatives");
-    if (in->f64) return in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
-    const int rc_ = integrate_any(in, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
+    if (h->f64) return h->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
+    const int rc_ = integrate_any(h, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
                                   stateFrequenciesIndices, cumulativeScaleIndices, count, nullptr, 1, nullptr, outSumLogLikelihood);
     API_TRACE("beagleCalculateEdgeLogLikelihoods(parents=%s, children=%s, matrices=%s, weights=%s, freqs=%s, cumulative=%s) -> %d, lnL %.6f",
               trace_ints(parentBufferIndices, count).c_str(), trace_ints(childBufferIndices, count).c_str(),
@@ -4041,13 +4002,13 @@ int beagleCalculateRootLogLikelihoodsByPartition(int instance, const int* buffer
 {
     StatTimer st_(ST_LNL);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->logLikelihoods(bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
-    if (!in->facade() && (partitionCount != 1 || partitionIndices[0] != 0))
+    if (h->f64) return h->f64->logLikelihoods(bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
+    if (in && (partitionCount != 1 || partitionIndices[0] != 0))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateRootLogLikelihoodsByPartition: no partitions were set");
     double total = 0.0;
-    const int rc_ = integrate_any(in, bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices,
+    const int rc_ = integrate_any(h, bufferIndices, nullptr, nullptr, categoryWeightsIndices, stateFrequenciesIndices,
                                   cumulativeScaleIndices, count, partitionIndices, partitionCount, outSumLogLikelihoodByPartition, &total);
-    if (!in->facade() && outSumLogLikelihoodByPartition) outSumLogLikelihoodByPartition[0] = total;
+    if (in && outSumLogLikelihoodByPartition) outSumLogLikelihoodByPartition[0] = total;
     if (outSumLogLikelihood) *outSumLogLikelihood = total;
     API_TRACE("beagleCalculateRootLogLikelihoodsByPartition(%d partitions) -> %d, lnL %.6f", partitionCount, rc_, total);
     return rc_;
@@ -4066,16 +4027,16 @@ int beagleCalculateEdgeLogLikelihoodsByPartition(int instance, const int* parent
     if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivativeByPartition || outSumFirstDerivative ||
         outSumSecondDerivativeByPartition || outSumSecondDerivative)
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoodsByPartition: derivatives");
-    if (in->f64)
-        return in->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices,
+    if (h->f64)
+        return h->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices,
                                        cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
-    if (!in->facade() && (partitionCount != 1 || partitionIndices[0] != 0))
+    if (in && (partitionCount != 1 || partitionIndices[0] != 0))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeLogLikelihoodsByPartition: no partitions were set");
     double total = 0.0;
-    const int rc_ = integrate_any(in, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
+    const int rc_ = integrate_any(h, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
                                   stateFrequenciesIndices, cumulativeScaleIndices, count, partitionIndices, partitionCount,
                                   outSumLogLikelihoodByPartition, &total);
-    if (!in->facade() && outSumLogLikelihoodByPartition) outSumLogLikelihoodByPartition[0] = total;
+    if (in && outSumLogLikelihoodByPartition) outSumLogLikelihoodByPartition[0] = total;
     if (outSumLogLikelihood) *outSumLogLikelihood = total;
     API_TRACE("beagleCalculateEdgeLogLikelihoodsByPartition(%d partitions) -> %d, lnL %.6f", partitionCount, rc_, total);
     return rc_;
@@ -4084,31 +4045,26 @@ int beagleGetSiteLogLikelihoods(int instance, double* outLogLikelihoods)
 {
     StatTimer st_(ST_SITE);
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->getSites(outLogLikelihoods);
-    FACADE_ALL(c->haveSite ? c->getSites(outLogLikelihoods + ch.start) : BEAGLE_SUCCESS);
-    return in->getSites(outLogLikelihoods);
+    if (h->f64) return h->f64->getSites(outLogLikelihoods);
+    if (in) return in->getSites(outLogLikelihoods);                  // (an error before the first log-likelihood)
+    EACH_ENGINE(true, c->haveSite ? c->getSites(outLogLikelihoods + ch.start) : BEAGLE_SUCCESS);        // (children without a result are skipped)
 }
 
 // ---- engine extensions ---------------------------------------------------------------------
 int mbamdSynchronize(int instance)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return in->f64->synchronize();
-    FACADE_ALL(hipStreamSynchronize(c->stream) == hipSuccess ? BEAGLE_SUCCESS : BEAGLE_ERROR_GENERAL);
-    HIP_TRY(hipStreamSynchronize(in->stream));
-    return BEAGLE_SUCCESS;
+    return synchronize(h);
 }
 int mbamdKernelTiming(int instance, int enable)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return BEAGLE_SUCCESS;
-    if (in->facade()) { for (Instance::Child& ch : in->children) ch.in->timing = enable != 0; return BEAGLE_SUCCESS; }
-    in->timing = enable != 0;
-    return BEAGLE_SUCCESS;
+    if (h->f64) return BEAGLE_SUCCESS;
+    EACH_ENGINE(false, (c->timing = enable != 0, BEAGLE_SUCCESS));
 }
+// (each_engine has made the engine's device current)
 static int kernel_timing_of(Instance* in, double* ms, long* launches, int reset)
 {
-    (void) hipSetDevice(in->device);
     HIP_TRY(hipStreamSynchronize(in->stream));
     { int frc = in->eventsFold(); if (frc) return frc; }
     in->timedLaunches += in->pendingLaunches;
@@ -4120,7 +4076,6 @@ static int kernel_timing_of(Instance* in, double* ms, long* launches, int reset)
 }
 static int step_timing_of(Instance* in, double* ms, long* steps, int reset)
 {
-    (void) hipSetDevice(in->device);
     HIP_TRY(hipStreamSynchronize(in->stream));
     in->spanFold();
     *ms += in->spanMs;
@@ -4128,30 +4083,26 @@ static int step_timing_of(Instance* in, double* ms, long* steps, int reset)
     if (reset) { in->spanMs = 0.0; in->spanCount = 0; }
     return BEAGLE_SUCCESS;
 }
-// (a facade reports the LARGEST kernel time of its children -- they run side by side -- and the sum of the launches)
+// (children: the LARGEST kernel time among them -- they run side by side -- and the sum of the launches)
 int mbamdGetKernelTiming(int instance, double* outMilliseconds, long* outLaunches, int reset)
 {
     GET_INSTANCE(instance);
-    if (in->f64) {                               // (no device timing on a double-precision instance: the partials launches are counted)
-        { const int rcq = in->f64->flushQueue(); if (rcq) return rcq; }
+    if (Engine64* e = h->f64.get()) {            // (no device timing on a double-precision instance: the partials launches are counted)
+        { const int rcq = e->flushQueue(); if (rcq) return rcq; }
         if (outMilliseconds) *outMilliseconds = 0.0;
-        if (outLaunches) *outLaunches = (long) (in->f64->walkLaunches + in->f64->levelLaunches);
-        if (reset) in->f64->walkLaunches = in->f64->levelLaunches = 0;
+        if (outLaunches) *outLaunches = (long) (e->walkLaunches + e->levelLaunches);
+        if (reset) e->walkLaunches = e->levelLaunches = 0;
         return BEAGLE_SUCCESS;
     }
     double ms = 0.0;
     long launches = 0;
-    if (in->facade()) {
-        for (Instance::Child& ch : in->children) {
-            double m = 0.0;
-            int rc = kernel_timing_of(ch.in, &m, &launches, reset);
-            if (rc) return rc;
-            ms = std::max(ms, m);
-        }
-    } else {
-        int rc = kernel_timing_of(in, &ms, &launches, reset);
-        if (rc) return rc;
-    }
+    const int rc = each_engine(h, false, [&](Instance* c, const Handle::Span&) {
+        double m = 0.0;
+        const int trc = kernel_timing_of(c, &m, &launches, reset);
+        ms = std::max(ms, m);
+        return trc;
+    });
+    if (rc) return rc;
     if (outMilliseconds) *outMilliseconds = ms;
     if (outLaunches) *outLaunches = launches;
     return BEAGLE_SUCCESS;
@@ -4161,33 +4112,29 @@ int mbamdGetListCounts(int instance, long* out6)
     GET_INSTANCE(instance);
     if (!out6) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetListCounts: null output");
     for (int i = 0; i < 6; ++i) out6[i] = 0;
-    if (in->f64 || in->facade()) return BEAGLE_SUCCESS;
+    if (!in) return BEAGLE_SUCCESS;              // (counted by the one single-precision engine only)
     out6[0] = in->listsTotal; out6[1] = in->listsPath; out6[2] = in->forkedPaths; out6[3] = in->fusedPaths;
     out6[4] = in->listsWalked; out6[5] = in->opsWalked;
     return BEAGLE_SUCCESS;
 }
 // Device time of whole evaluations while mbamdKernelTiming is on: from the first kernel launched after a log-likelihood
 // call to the end of the next integration kernel -- every kernel of a step and the gaps between them (HIP events on the
-// engine's stream).  A facade reports the largest of its children.
+// engine's stream).  Children: the largest among them.
 int mbamdGetStepTiming(int instance, double* outMilliseconds, long* outSteps, int reset)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetStepTiming: not on a double-precision instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetStepTiming: not on a double-precision instance");
     double ms = 0.0;
     long steps = 0;
-    if (in->facade()) {
-        for (Instance::Child& ch : in->children) {
-            double m = 0.0;
-            long st = 0;
-            int rc = step_timing_of(ch.in, &m, &st, reset);
-            if (rc) return rc;
-            ms = std::max(ms, m);
-            steps = std::max(steps, st);
-        }
-    } else {
-        int rc = step_timing_of(in, &ms, &steps, reset);
-        if (rc) return rc;
-    }
+    const int rc = each_engine(h, false, [&](Instance* c, const Handle::Span&) {
+        double m = 0.0;
+        long st = 0;
+        const int trc = step_timing_of(c, &m, &st, reset);
+        ms = std::max(ms, m);
+        steps = std::max(steps, st);
+        return trc;
+    });
+    if (rc) return rc;
     if (outMilliseconds) *outMilliseconds = ms;
     if (outSteps) *outSteps = steps;
     return BEAGLE_SUCCESS;
@@ -4195,15 +4142,15 @@ int mbamdGetStepTiming(int instance, double* outMilliseconds, long* outSteps, in
 int mbamdSetKernelPath(int instance, int path)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return BEAGLE_SUCCESS;
+    if (h->f64) return BEAGLE_SUCCESS;
     if (path < 0 || path > 3) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdSetKernelPath");
     return BEAGLE_SUCCESS;                       // (accepted and ignored: every instance picks its kernels from its dimensions)
 }
 int mbamdWalkTrace(int instance, long long* out, int maxSteps, int* outSteps, int* outWaves)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdWalkTrace: not on a double-precision instance");
-    if (!in->d_trace) return fail(BEAGLE_ERROR_GENERAL, "set MBAMD_WALK_TRACE before creating the instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdWalkTrace: not on a double-precision instance");
+    if (!in || !in->d_trace) return fail(BEAGLE_ERROR_GENERAL, "set MBAMD_WALK_TRACE before creating the instance");
     HIP_TRY(hipStreamSynchronize(in->stream));
     const int n = std::min(maxSteps, std::min(4096, in->lastWalkSteps));
     HIP_TRY(hipMemcpy(out, in->d_trace, (size_t) n * 8 * 3 * sizeof(long long), hipMemcpyDeviceToHost));
@@ -4211,25 +4158,25 @@ int mbamdWalkTrace(int instance, long long* out, int maxSteps, int* outSteps, in
     if (outWaves) *outWaves = in->walkWaves + 1;
     return BEAGLE_SUCCESS;
 }
-// the number of child instances behind this instance (1: none) -- pattern partitions x shards
+// the number of child engines behind this instance (1: none) -- pattern partitions x shards
 int mbamdGetChildCount(int instance)
 {
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) return std::max<int>(1, (int) in->f64->parts.size());
-    return in->facade() ? (int) in->children.size() : 1;
+    if (h->f64) return std::max<int>(1, (int) h->f64->parts.size());
+    return h->children.empty() ? 1 : (int) h->children.size();
 }
 int mbamdSetDeferredResult(int instance, int enable)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return enable ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetDeferredResult: not on a double-precision instance") : BEAGLE_SUCCESS;
-    if (in->facade()) return enable ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetDeferredResult: not on a partitioned / sharded instance") : BEAGLE_SUCCESS;
+    if (h->f64) return enable ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetDeferredResult: not on a double-precision instance") : BEAGLE_SUCCESS;
+    if (!in) return enable ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdSetDeferredResult: not on a partitioned / sharded instance") : BEAGLE_SUCCESS;
     in->deferred = enable != 0;
     return BEAGLE_SUCCESS;
 }
 int mbamdReduceLogLikelihood(int instance, double* deviceOut, void* waitingStream)
 {
     GET_INSTANCE(instance);
-    if (in->f64 || in->facade()) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdReduceLogLikelihood: plain single-precision instances only");
+    if (!in) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdReduceLogLikelihood: plain single-precision instances only");
     if (!in->pendingResult) return fail(BEAGLE_ERROR_GENERAL, "no log-likelihood pending");
     if (deviceOut == nullptr) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdReduceLogLikelihood: null output");
     MBAMD_LAUNCH_BARRIER(k_sum_block_sums, 1u, 256, 256 * sizeof(double), in->stream, (const double*) in->h_sums_dev, in->nblocks, deviceOut);
@@ -4254,17 +4201,16 @@ int mbamdGetResourcePciBusId(int resource, char* out, int length)
 int mbamdGetInstanceDevices(int instance, int* outResources, int maxCount)
 {
     GET_INSTANCE_NOFLUSH(instance);
-    if (in->f64) { if (outResources && maxCount > 0) outResources[0] = in->device; return 1; }
-    if (!in->facade()) { if (outResources && maxCount > 0) outResources[0] = in->device; return 1; }
+    if (h->children.empty()) { if (outResources && maxCount > 0) outResources[0] = h->device; return 1; }
     int n = 0;
-    for (const Instance::Child& c : in->children) { if (outResources && n < maxCount) outResources[n] = c.in->device; ++n; }
+    for (const Handle::Child& c : h->children) { if (outResources && n < maxCount) outResources[n] = c.in->device; ++n; }
     return n;
 }
 int mbamdFetchLogLikelihood(int instance, double* outSumLogLikelihood)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdFetchLogLikelihood: not on a double-precision instance");
-    if (in->facade()) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdFetchLogLikelihood: not on a partitioned / sharded instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdFetchLogLikelihood: not on a double-precision instance");
+    if (!in) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdFetchLogLikelihood: not on a partitioned / sharded instance");
     return in->fetchResult(outSumLogLikelihood);
 }
 
@@ -4273,27 +4219,26 @@ int mbamdFetchLogLikelihood(int instance, double* outSumLogLikelihood)
 int mbamdUpdateFinalPartials(int instance, const MbamdFinalOperation* operations, int operationCount)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdUpdateFinalPartials: not on a double-precision instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdUpdateFinalPartials: not on a double-precision instance");
     if (operationCount <= 0) return BEAGLE_SUCCESS;
     if (!operations) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdUpdateFinalPartials: null");
-    FACADE_ALL(c->finalPass(operations, operationCount));          // (site patterns are independent: every child does its range)
-    return in->finalPass(operations, operationCount);
+    EACH_ENGINE(true, c->finalPass(operations, operationCount));     // (site patterns are independent: every child does its range)
 }
 int mbamdGetScaledPartials(int instance, int bufferIndex, int cumulativeScaleIndex, float* outPartials, float* outLnScale)
 {
     GET_INSTANCE(instance);
-    if (in->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetScaledPartials: not on a double-precision instance");
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetScaledPartials: not on a double-precision instance");
     if (!outPartials || !outLnScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetScaledPartials: null");
-    if (!in->facade()) return in->getScaledPartials(bufferIndex, cumulativeScaleIndex, outPartials, outLnScale);
-    if (in->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetScaledPartials: not on a multi-partition instance");
+    if (in) return in->getScaledPartials(bufferIndex, cumulativeScaleIndex, outPartials, outLnScale);
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetScaledPartials: not on a multi-partition instance");
     // pattern shards: each child's [K][count][S] block goes to its pattern range of the caller's [K][P][S] array
-    const size_t S = (size_t) in->createArgs[3], P = (size_t) in->createArgs[4];
-    const int K = in->createArgs[7];
+    const size_t S = (size_t) h->dim.stateCount, P = (size_t) h->dim.patternCount;
+    const int K = h->dim.categoryCount;
     std::vector<float> part, ln;
-    return each_child(in, true, [&](Instance::Child& ch) {
+    return each_engine(h, true, [&](Instance* c, const Handle::Span& ch) {
         part.resize((size_t) K * ch.count * S);
         ln.resize((size_t) ch.count);
-        const int rc = ch.in->getScaledPartials(bufferIndex, cumulativeScaleIndex, part.data(), ln.data());
+        const int rc = c->getScaledPartials(bufferIndex, cumulativeScaleIndex, part.data(), ln.data());
         if (rc) return rc;
         copy_rows(outPartials + ch.start * S, P * S, part.data(), ch.count * S, K, ch.count * S);
         copy_rows(outLnScale + ch.start, P, ln.data(), (size_t) ch.count, 1, (size_t) ch.count);
@@ -4318,9 +4263,9 @@ int mbamdParsCreateInstance(int setCount, int patternCount, int wordsPerSet, int
         return fail(BEAGLE_ERROR_NO_RESOURCE, "mbamdParsCreateInstance: no HIP device (this engine has no CPU path)");
     int dev = 0;
     if (likelihoodInstance >= 0) {
-        Instance* in = lookup(likelihoodInstance);
-        if (!in) return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "mbamdParsCreateInstance: no such likelihood instance");
-        dev = in->facade() ? in->children[0].in->device : in->device;
+        const Handle* h = lookup(likelihoodInstance);
+        if (!h) return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "mbamdParsCreateInstance: no such likelihood instance");
+        dev = h->device;                         // (the first device of a sharded instance)
     }
     ParsInstance* pi = new ParsInstance();
     int rc = pi->create(setCount, patternCount, wordsPerSet, setBits, dev, read_switches());

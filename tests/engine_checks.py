@@ -1354,3 +1354,199 @@ def check_parsimony_model_golden(lib, golden_dir):
             inst.finalize()
 
 
+
+
+# ------------------------------------------------------------------------------------------------
+def check_handle_roles(lib, monkeypatch):
+    """What is behind an instance number is one of three things -- one single-precision engine ("plain"), a list of child engines
+    (pattern shards and / or v3 partitions), or the double-precision engine -- and the entry points differ between them in return
+    codes and read-outs that no other check pins.  Smallest shapes that reach each role: 4 states, 2 categories, 130 patterns
+    (sharded under MBAMD_SHARD=3: children of 64, 64 and 2 patterns; two partitions: 70 + 60 patterns)."""
+    import ctypes as C
+    L = lib.lib
+    NOIMPL, GENERAL, RANGE = bg.BEAGLE_ERROR_NO_IMPLEMENTATION, bg.BEAGLE_ERROR_GENERAL, bg.BEAGLE_ERROR_OUT_OF_RANGE
+    monkeypatch.delenv("MBAMD_SHARD", raising=False)
+    monkeypatch.delenv("MBAMD_WALK_TRACE", raising=False)
+    P, Pa = 130, 70
+    div = synthetic_division("gtr", 8, P, seed=81, tree_seed=82, ncat=2)
+    t = div.tree
+    ndev = len(lib.resources())
+    two = np.concatenate([np.zeros(Pa, dtype=np.int32), np.ones(P - Pa, dtype=np.int32)])
+
+    def refused(call, *args):
+        with pytest.raises(bg.BeagleError) as e:
+            call(*args)
+        return e.value.code, str(e.value)
+
+    def walk_trace(inst):
+        out, n, w = (C.c_longlong * 24)(), C.c_int(0), C.c_int(0)
+        L.mbamdWalkTrace.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        return L.mbamdWalkTrace(inst.id, out, 1, C.byref(n), C.byref(w)), lib.last_error()
+
+    def likelihood_arguments(bd):
+        p = t.root_left
+        eig = [bd.cijkIndex[0]]
+        return [bd.condLikeIndex[0][p]], [bd.condLikeIndex[0][t.root]], [bd.tiProbsIndex[0][p]], eig, eig, [bd.siteScalerIndex[0]]
+
+    def plain_only_calls_refused(inst):
+        """the extensions of a plain single-precision instance: refused elsewhere, except switching the deferred result OFF"""
+        inst.set_deferred_result(False)
+        assert refused(inst.set_deferred_result, True)[0] == NOIMPL
+        assert refused(inst.fetch_log_likelihood)[0] == NOIMPL
+        assert refused(inst.reduce_log_likelihood, 0)[0] == NOIMPL
+        assert inst.get_list_counts() == (0, 0, 0, 0, 0, 0)
+
+    # ---- plain -----------------------------------------------------------------------------------
+    bd = lk.BeagleDivision(div, lib)
+    inst = bd.inst
+    try:
+        assert inst.details.flags & bg.BEAGLE_FLAG_PRECISION_SINGLE and not inst.details.flags & bg.BEAGLE_FLAG_PRECISION_DOUBLE
+        assert b"4-state tree-walk" in inst.details.implName
+        assert inst.child_count() == 1 and inst.devices() == [inst.details.resourceNumber] == [0]
+        code, text = refused(inst.get_site_log_likelihoods)
+        assert code == GENERAL and "no likelihood computed yet" in text
+        inst.set_pattern_partitions(1, np.zeros(P, dtype=np.int32))                      # one partition: nothing happens
+        assert inst.child_count() == 1
+        plain_first_id = inst.id
+        want = bd.LogLike(0)
+        want_sites = inst.get_site_log_likelihoods()
+        _, plain_launches = inst.get_kernel_timing()                                      # the partials launches of one full evaluation
+        assert plain_launches >= 1
+        assert refused(inst.set_pattern_partitions, 2, two)[0] == GENERAL                 # too late: matrices and partials were updated
+        assert refused(inst.set_pattern_partitions, 1, np.zeros(P, dtype=np.int32))[0] == GENERAL
+        assert inst.child_count() == 1
+        args = likelihood_arguments(bd)
+        rc, by, total = inst.calculate_edge_log_likelihoods_by_partition(*args, [0], 1)
+        assert rc == 0 and by[0] == total == want
+        rc, by, total = inst.calculate_root_log_likelihoods_by_partition(args[0], *args[3:], [0], 1)
+        assert rc == 0 and by[0] == total and math.isfinite(total)               # (the subtree below the root tip)
+        for partitions in ([1], [0, 0]):
+            code, text = refused(inst.calculate_edge_log_likelihoods_by_partition, *args, partitions, 1)
+            assert code == RANGE and "beagleCalculateEdgeLogLikelihoodsByPartition: no partitions were set" in text
+            code, text = refused(inst.calculate_root_log_likelihoods_by_partition, args[0], *args[3:], partitions, 1)
+            assert code == RANGE and "beagleCalculateRootLogLikelihoodsByPartition: no partitions were set" in text
+        p = t.int_down_pass[0]
+        op = [bd.condLikeIndex[0][p], -1, -1, bd.condLikeIndex[0][t.left[p]], bd.tiProbsIndex[0][t.left[p]],
+              bd.condLikeIndex[0][t.right[p]], bd.tiProbsIndex[0][t.right[p]], 1, -1]
+        code, text = refused(inst.update_partials_by_partition, np.array([op], dtype=np.int32))
+        assert code == RANGE and "beagleUpdatePartialsByPartition: partition index (no partitions were set)" in text
+        op[7] = 0
+        inst.update_partials_by_partition(np.array([op], dtype=np.int32))
+        code, text = refused(inst.set_state_frequencies, 2, div.pi)                       # (two eigen buffers: nchains + 1)
+        assert code == RANGE and "beagleSetStateFrequencies: index" in text
+        assert inst.get_list_counts()[0] >= 1
+        inst.set_deferred_result(True)
+        inst.set_deferred_result(False)
+        code, text = refused(inst.reduce_log_likelihood, 0)
+        assert code == GENERAL and "no log-likelihood pending" in text
+        rc, text = walk_trace(inst)
+        assert rc == GENERAL and "MBAMD_WALK_TRACE" in text
+        ms, steps = inst.get_step_timing()
+        assert ms == 0.0 and steps == 0                                                   # (timing was never switched on)
+        top = bd.condLikeIndex[0][t.root_left]
+        want_scaled, want_ln = inst.get_scaled_partials(top, bd.siteScalerIndex[0])
+        inst.set_transition_matrix(bd.tiProbsScratchIndex[0], np.full((2, 4, 4), 0.25))
+        assert np.array_equal(inst.get_transition_matrix(bd.tiProbsScratchIndex[0]), np.full((2, 4, 4), 0.25))
+    finally:
+        bd.finalize()
+    # finalised: the number is free, and the next instance takes it
+    assert L.beagleResetScaleFactors(plain_first_id, 0) == bg.BEAGLE_ERROR_UNINITIALIZED_INSTANCE
+    assert L.beagleFinalizeInstance(plain_first_id) == bg.BEAGLE_ERROR_UNINITIALIZED_INSTANCE
+    bd = lk.BeagleDivision(div, lib)
+    try:
+        assert bd.inst.id == plain_first_id and bd.LogLike(0) == want
+    finally:
+        bd.finalize()
+
+    # ---- a create that fails: more than 64 states with several resources named; nothing is left behind -----------
+    both = (C.c_int * 2)(0, 0)
+    assert L.beagleCreateInstance(2, 4, 2, 65, P, 1, 2, 2, 2, C.cast(both, C.POINTER(C.c_int)), 2, 0, 0, None) == NOIMPL
+    assert "more than 64 states" in lib.last_error()
+
+    # ---- pattern shards ----------------------------------------------------------------------------
+    monkeypatch.setenv("MBAMD_SHARD", "3")
+    bd = lk.BeagleDivision(div, lib)
+    inst = bd.inst
+    try:
+        assert inst.id == plain_first_id                                                  # (the failed create took no number)
+        assert inst.details.flags & bg.BEAGLE_FLAG_PRECISION_SINGLE and b"4-state tree-walk" in inst.details.implName
+        assert inst.child_count() == 3 and inst.devices() == [i % ndev for i in range(3)] and inst.details.resourceNumber == 0
+        inst.get_site_log_likelihoods()                                                   # before any likelihood: children without a result are skipped
+        got = bd.LogLike(0)
+        assert abs(got - want) <= 1e-10 * abs(want)
+        assert np.array_equal(inst.get_site_log_likelihoods(), want_sites)
+        plain_only_calls_refused(inst)
+        rc, text = walk_trace(inst)
+        assert rc == GENERAL and "MBAMD_WALK_TRACE" in text
+        ms, steps = inst.get_step_timing()
+        assert ms == 0.0 and steps == 0
+        ms, launches = inst.get_kernel_timing()
+        assert ms == 0.0 and launches == 3 * plain_launches                               # the sum over the children
+        code, text = refused(inst.set_state_frequencies, 2, div.pi)
+        assert code == RANGE and "beagleSetStateFrequencies: index" in text
+        scaled, ln = inst.get_scaled_partials(top, bd.siteScalerIndex[0])                 # gathered from the children's pattern ranges
+        assert np.array_equal(scaled, want_scaled) and np.array_equal(ln, want_ln)
+        inst.set_transition_matrix(bd.tiProbsScratchIndex[0], np.full((2, 4, 4), 0.25))
+        assert np.array_equal(inst.get_transition_matrix(bd.tiProbsScratchIndex[0]), np.full((2, 4, 4), 0.25))
+        assert refused(inst.set_pattern_partitions, 2, two)[0] == GENERAL
+    finally:
+        bd.finalize()
+
+    # ---- two partitions, without and with shards (70 patterns: blocks of 64 + 6; 60: one block) -------------------
+    for shard, children in ((None, 2), ("3", 3)):
+        if shard is None:
+            monkeypatch.delenv("MBAMD_SHARD")
+        else:
+            monkeypatch.setenv("MBAMD_SHARD", shard)
+        inst = bg.BeagleInstance(lib, 8, 14, 8, 4, P, 2, 28, 2, 8)
+        try:
+            for tip in range(8):
+                inst.set_tip_states(tip, div.tip_states[tip])
+            inst.set_pattern_weights(div.weights)
+            inst.set_pattern_partitions(2, two)
+            assert inst.child_count() == children
+            assert inst.devices() == ([0, 0] if shard is None else [0, 1 % ndev, 0])
+            inst.get_site_log_likelihoods()
+            plain_only_calls_refused(inst)
+            code, text = refused(inst.get_scaled_partials, 0)
+            assert code == NOIMPL and "multi-partition" in text
+            assert walk_trace(inst)[0] == GENERAL
+            assert inst.get_step_timing() == (0.0, 0) and inst.get_kernel_timing() == (0.0, 0)
+            inst.set_transition_matrix(3, np.full((2, 4, 4), 0.25))
+            assert np.array_equal(inst.get_transition_matrix(3), np.full((2, 4, 4), 0.25))
+            inst.set_pattern_partitions(1, np.zeros(P, dtype=np.int32))                   # back to one partition: the children are rebuilt
+            assert inst.child_count() == (1 if shard is None else 3)
+        finally:
+            inst.finalize()
+    monkeypatch.delenv("MBAMD_SHARD")
+
+    # ---- double precision, without and with partitions -------------------------------------------------------
+    bd = lk.BeagleDivision(div, lib, double_precision=True)
+    inst = bd.inst
+    try:
+        assert inst.details.flags & bg.BEAGLE_FLAG_PRECISION_DOUBLE and not inst.details.flags & bg.BEAGLE_FLAG_PRECISION_SINGLE
+        assert b"double-precision kernels (four states: tree walk)" in inst.details.implName
+        assert inst.child_count() == 1 and inst.devices() == [0]
+        got = bd.LogLike(0)
+        assert abs(got - want) <= REL_FP64 * abs(want)
+        plain_only_calls_refused(inst)
+        ms, launches = inst.get_kernel_timing()
+        assert ms == 0.0 and launches >= 1                                                # no device timing; the partials launches are counted
+        assert inst.get_kernel_timing() == (0.0, 0)
+        rc, text = walk_trace(inst)
+        assert rc == NOIMPL and "double-precision" in text
+        assert refused(inst.get_step_timing)[0] == NOIMPL
+        assert refused(inst.get_scaled_partials, top)[0] == NOIMPL
+        assert refused(inst.update_final_partials, np.array([[top, -1, top, 0, -1]], dtype=np.int32))[0] == NOIMPL
+    finally:
+        bd.finalize()
+    inst = bg.BeagleInstance(lib, 8, 14, 8, 4, P, 2, 28, 2, 8, preference_flags=bg.BEAGLE_FLAG_PRECISION_DOUBLE)
+    try:
+        for tip in range(8):
+            inst.set_tip_states(tip, div.tip_states[tip])
+        inst.set_pattern_partitions(2, two)
+        assert inst.child_count() == 2 and inst.devices() == [0]
+        plain_only_calls_refused(inst)
+        assert refused(inst.set_pattern_partitions, 0, two)[0] == RANGE
+    finally:
+        inst.finalize()

@@ -510,6 +510,10 @@ def test_lists_with_hazards_are_cut_into_segments(gpu, oracle):
     ec.check_hazard_lists(gpu, 20, 2, 40, double_precision=True)
 
 
+def test_handle_roles(gpu, monkeypatch):
+    ec.check_handle_roles(gpu, monkeypatch)
+
+
 def test_instances_created_and_destroyed_repeatedly(gpu):
     """Buffers land at different device addresses every time (address-dependent bugs, e.g. a pointer whose low
     half has bit 31 set, show up here); results must not move."""

@@ -191,6 +191,10 @@ def test_error_codes(emu, monkeypatch):
     assert np.isfinite(plain) and held == plain
 
 
+def test_handle_roles(emu, monkeypatch):
+    ec.check_handle_roles(emu, monkeypatch)
+
+
 @pytest.mark.parametrize("waves", [2, 3, 4, 8])
 @pytest.mark.parametrize("slots", [3, 4, 7, 16])
 @pytest.mark.parametrize("prefetch", [0, 4])
