@@ -6,102 +6,23 @@
 //
 // Built by hipcc for gfx950 (see mrbayes_amd/build.py).  There is no CPU code path in the product:
 // without a HIP device beagleCreateInstance fails with BEAGLE_ERROR_NO_RESOURCE.
-#include <mbamd_dev_runtime.h>   // the HIP runtime + launch macros (csrc/device/; tests/hostemu/ has the CPU stand-in for the test build)
-
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
-#include <string>
-#include <limits>
 #include <memory>
 #include <unordered_map>
-#include <vector>
 
-#include "libhmsbeagle/beagle.h"
+#include "mbamd_host.h"          // the HIP runtime, beagle.h, the switches, <algorithm> ... <vector>; diagnostics and the host runtime the engines share
 #include "mbamd_kernels.h"
 #include "mbamd_reports.h"
 #include "libhmsbeagle/mbamd_reports.h"
 #include "mbamd_walk4_host.h"
 #include "mbamd_kernels_mfma.h"
-#include "mbamd_switches.h"
-
-#include <chrono>
+#include "libhmsbeagle/mbamd_parsimony.h"
+#include "mbamd_parsimony.h"     // ParsInstance: the parsimony engine
+#include "mbamd_f64.h"           // Engine64: the double-precision engine
 
 namespace mbamd {
-
-// MBAMD_STATS=1: per-entry-point call counts and host wall time, printed when an instance is finalized
-struct ApiStats {
-    const char* name;
-    long calls = 0;
-    double seconds = 0.0;
-};
-static ApiStats g_stats[] = {{"beagleUpdateTransitionMatrices"}, {"beagleUpdatePartials"}, {"beagleCalculate*LogLikelihoods"},
-                             {"beagle*ScaleFactors"}, {"beagleSet*"}, {"beagleGetSiteLogLikelihoods"}, {"plan build"},
-                             {"mbamdParsDownPass/FinalPass"}, {"mbamdParsScore"},
-                             {"  (launching the deferred work)"}, {"  (waiting for the device)"},
-                             {"  (parsimony: compiling the queued passes)"}, {"  (parsimony: waiting for the device)"}};
-enum { ST_MATRICES = 0, ST_PARTIALS, ST_LNL, ST_SCALE, ST_SET, ST_SITE, ST_PLAN, ST_PARS_PASS, ST_PARS_SCORE, ST_FLUSH, ST_WAIT, ST_PARS_COMPILE, ST_PARS_WAIT };
-// the process-level diagnostics (MBAMD_STATS, MBAMD_API_TRACE, MBAMD_VERBOSE in fail()): read once, when the library loads
-static const Switches g_loadSwitches = read_switches();
-// MBAMD_API_TRACE=1: one stderr line per C-ABI call (integration debugging: what does the client really send?)
-#define API_TRACE(...) do { if (g_loadSwitches.apiTrace) { std::fprintf(stderr, "[mbamd api] " __VA_ARGS__); std::fputc('\n', stderr); } } while (0)
-static std::string trace_ints(const int* v, int n) {
-    std::string r = "[";
-    for (int i = 0; v && i < n; ++i) r += (i ? "," : "") + std::to_string(v[i]);
-    return r + "]";
-}
-static std::string trace_doubles(const double* v, int n) {
-    std::string r = "[";
-    char buf[32];
-    for (int i = 0; v && i < n; ++i) { std::snprintf(buf, sizeof buf, "%s%.6g", i ? "," : "", v[i]); r += buf; }
-    return r + "]";
-}
-struct StatTimer {
-    int id;
-    std::chrono::steady_clock::time_point t0;
-    explicit StatTimer(int i) : id(i) { if (g_loadSwitches.stats) t0 = std::chrono::steady_clock::now(); }
-    bool stopped = false;
-    void stop()                                      // (a span that ends before its scope does)
-    {
-        if (!g_loadSwitches.stats || stopped) return;
-        stopped = true;
-        g_stats[id].calls++;
-        g_stats[id].seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    ~StatTimer() { stop(); }
-};
-
-static thread_local std::string g_last_error;
-
-static int fail(int code, const char* what, const char* detail = "")
-{
-    g_last_error = std::string(what) + (detail[0] ? ": " : "") + detail;
-    if (g_loadSwitches.verbose) std::fprintf(stderr, "[mbamd] error %d: %s\n", code, g_last_error.c_str());
-    return code;
-}
-
-static int hip_fail(hipError_t e, const char* what)
-{
-    return fail(e == hipErrorOutOfMemory ? BEAGLE_ERROR_OUT_OF_MEMORY : BEAGLE_ERROR_GENERAL, what, hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);                                          \
-    } while (0)
-
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// FNV-1a over 32-bit words: the hash of the plan cache and of the tree-walk templates (`h`: continue an earlier hash)
-static inline uint64_t fnv1a(const int* v, size_t n, uint64_t h = 1469598103934665603ull)
-{
-    for (size_t i = 0; i < n; ++i) h = (h ^ (uint64_t) (uint32_t) v[i]) * 1099511628211ull;
-    return h;
-}
 
 // state counts the 20/61-state tree walk (mbamd_walkg.h) is instantiated for: amino acids, doublets, and the sense codons of
 // every genetic code MrBayes knows (60 vertebrate mitochondrial ... 63; reference src/model.c SetCode)
@@ -183,12 +104,6 @@ struct PathStep {
     int scaleMode, scaleIdx;         // SCALE_NONE / SCALE_WRITE / SCALE_READ and its exponent buffer
 };
 
-// the dimensions an instance was created with (beagleCreateInstance)
-struct Dims {
-    int tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount, categoryCount,
-        scaleBufferCount;
-};
-
 // The single-precision engine of one device: arenas, stream, plan cache, schedulers.  Created by new_engine() only; the
 // destructor hands everything back.  What the C ABI calls an instance is a Handle (further down), which owns one of these,
 // several (pattern shards, v3 partitions), or the double-precision engine instead.
@@ -267,7 +182,7 @@ struct Instance {
     uint64_t launchClock = 0, syncedClock = 0;   // launches issued / launches known complete (last stream synchronisation)
     uint64_t flagClock = 0;                      // launchClock when the polled result flag was queued (postResultFlag)
     uint32_t siteSeq = 0, seenSeq = 0;           // flag value behind the integration that wrote the latest site values / latest flag value fetched
-    std::vector<double> h_freqs, h_weights;      // host mirrors of d_freqs / d_weights (uploadIfChanged)
+    HostMirror h_freqs, h_weights;               // host mirrors of d_freqs / d_weights (setFreqs / setWeights)
     long long* d_trace = nullptr;    // MBAMD_WALK_TRACE: per-step clock stamps of workgroup 0 (timing experiments)
 
     int NT = 0, T = 0;               // MFMA packing: i-tiles of 32 rows, j-pairs
@@ -291,7 +206,7 @@ struct Instance {
     double* h_site_dev = nullptr;
     bool siteToHost = false, siteOnHost = false;   // mode / where the latest evaluation put its values
     int nblocks = 0;                  // partial sums of the weighted site log-likelihoods (one per integration workgroup)
-    std::vector<RatesArg> rateSets;   // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
+    RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
     bool haveSite = false;
 
@@ -299,27 +214,16 @@ struct Instance {
     double* d_ev = nullptr;           size_t evCap = 0;
     void* d_tmp = nullptr;            size_t tmpCap = 0;
 
-    // pinned staging ring for small asynchronous uploads / downloads
-    unsigned char* stage = nullptr;
-    size_t stageCap = 0, stageOff = 0;
+    PinnedRing stage;                 // pinned staging ring for small asynchronous uploads and small kernel inputs: 8 MiB, 64-byte slots
     double* h_sums = nullptr;         // pinned host memory the integration kernel writes its block sums to
     double* h_sums_dev = nullptr;     // the device-side address of h_sums
-    // The result is waited for by polling a word in pinned host memory that the STREAM writes behind the integration kernel
-    // (hipStreamWriteValue32): 7 us less per evaluation than hipStreamSynchronize on the same stream (MrBayes fixed-topology
-    // generation 83 -> 76 us, profiles/r04_mcmc_fixed_topology.txt).  A long wait falls back to the runtime's own wait.
-    uint32_t* h_flag = nullptr;       // sequence number of the last integration whose results have landed
-    uint32_t* h_flag_dev = nullptr;
-    uint32_t flagSeq = 0;             // ... of the last integration launched
-    bool pollResult = false;          // (off: MBAMD_NO_POLL, or the stream refused the write)
-    // Round 6: the block sums are their own completion signal.  Before an integration is launched the host fills h_sums with a
-    // bit pattern no sum can have; fetchResult then waits for every block sum to differ from it -- no gap + stream write behind the
-    // kernel (8.6 us of every evaluation, profiles/r06_walk61.txt), and no fence in the kernel (each sum is one 8-byte store to
-    // host-coherent memory).  Armed only when nothing else can still write h_sums (no unfetched result) and not in deferred mode
-    // (mbamdReduceLogLikelihood reads them on the device).
+    // The result is waited for by polling (CompletionWait, mbamd_host.h): the block sums are their own completion signal, armed
+    // only when nothing else can still write h_sums (no unfetched result) and not in deferred mode (mbamdReduceLogLikelihood reads
+    // them on the device); otherwise the stream writes the flag word behind the integration kernel (postResultFlag: wait.seq is the
+    // sequence number of the last integration launched).  A wait of more than a millisecond falls back to the runtime's own.
+    CompletionWait wait;
     bool sumsArmed = false, flagWritten = false;
-    static constexpr uint64_t kSumSentinel = 0x7FF4DEADBEEF0001ull;      // a signalling NaN with a payload no arithmetic produces
-    void armSums();
-    unsigned char* stage_dev = nullptr;   // the device-side address of the staging ring
+    void armSums() { sumsArmed = !pendingResult && !deferred && wait.arm(h_sums, (size_t) nblocks); }
 
     // timing of the partials kernels
     bool timing = false;
@@ -411,23 +315,13 @@ struct Instance {
     long planHits = 0, planMisses = 0, fusedPaths = 0, heldPaths = 0, forkedPaths = 0, listsTotal = 0, listsPath = 0, opsWalked = 0, listsWalked = 0;
 
     // ---- helpers ----------------------------------------------------------------------------
-    int grow(void** p, size_t* cap, size_t bytes)
-    {
-        if (bytes <= *cap) return BEAGLE_SUCCESS;
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (*p) HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        size_t n = std::max(bytes, *cap * 2);
-        HIP_TRY(hipMalloc(p, n));
-        *cap = n;
-        return BEAGLE_SUCCESS;
-    }
+    int grow(void** p, size_t* cap, size_t bytes) { return grow_device(stream, p, cap, bytes, std::max(bytes, *cap * 2)); }
 
     // copy host bytes to the device asynchronously through the pinned ring
     int upload(void* dst, const void* src, size_t bytes)
     {
         if (bytes == 0) return BEAGLE_SUCCESS;
-        if (bytes > stageCap / 2) {            // big one-off transfers (tip data): plain blocking copy
+        if (bytes > stage.capacity() / 2) {    // big one-off transfers (tip data): plain blocking copy
             HIP_TRY(hipStreamSynchronize(stream));
             HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
             return BEAGLE_SUCCESS;
@@ -436,41 +330,27 @@ struct Instance {
         //  kernel of ours: hipMemcpyAsync costs the host ~10 us a call and its blit kernel left the walk behind it 30 % slower,
         //  profiles/r06_ring_copy.txt)
         if (bytes <= ((size_t) 256 << 10) && bytes % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) return ringCopy(dst, src, bytes);
-        size_t need = (bytes + 63) & ~(size_t) 63;
-        if (stageOff + need > stageCap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            stageOff = 0;
-        }
-        std::memcpy(stage + stageOff, src, bytes);
-        HIP_TRY(hipMemcpyAsync(dst, stage + stageOff, bytes, hipMemcpyHostToDevice, stream));
-        stageOff += need;
+        size_t off = 0;
+        int rc = stage.put(src, bytes, stream, &off);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(dst, stage.host(off), bytes, hipMemcpyHostToDevice, stream));
         return BEAGLE_SUCCESS;
     }
     int ringCopy(void* dst, const void* src, size_t bytes);
 
-    // MrBayes re-sends state frequencies and category weights before every evaluation (reference
-    // src/mbbeagle.c:1179-1225); only a changed vector costs a stream operation.  `shadow` mirrors the device array.
-    int uploadIfChanged(std::vector<double>& shadow, size_t off, double* devBase, const double* src, int n)
-    {
-        if (shadow.size() < off + n) shadow.resize(off + n, std::numeric_limits<double>::quiet_NaN());
-        if (std::memcmp(shadow.data() + off, src, sizeof(double) * n) == 0) return BEAGLE_SUCCESS;
-        std::memcpy(shadow.data() + off, src, sizeof(double) * n);
-        return upload(devBase + off, src, sizeof(double) * n);
-    }
+    // (idx < nEigen: checked by the C ABI)
+    int setFreqs(int idx, const double* f) { return h_freqs.send((size_t) nEigen * S, (size_t) idx * S, f, (size_t) S, [&] { return upload(d_freqs + (size_t) idx * S, f, sizeof(double) * S); }); }
+    int setWeights(int idx, const double* w) { return h_weights.send((size_t) nEigen * K, (size_t) idx * K, w, (size_t) K, [&] { return upload(d_weights + (size_t) idx * K, w, sizeof(double) * K); }); }
 
     // small kernel inputs (job lists, pointer lists): placed in the pinned ring and read by the kernel
     // directly over the host link -- no copy engine, no extra stream operation
     int stageDirect(const void* src, size_t bytes, const void** devPtr)
     {
-        size_t need = (bytes + 63) & ~(size_t) 63;
-        if (need > stageCap / 2) return fail(BEAGLE_ERROR_OUT_OF_MEMORY, "staging ring too small");
-        if (stageOff + need > stageCap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            stageOff = 0;
-        }
-        std::memcpy(stage + stageOff, src, bytes);
-        *devPtr = stage_dev + stageOff;
-        stageOff += need;
+        if (((bytes + 63) & ~(size_t) 63) > stage.capacity() / 2) return fail(BEAGLE_ERROR_OUT_OF_MEMORY, "staging ring too small");
+        size_t off = 0;
+        int rc = stage.put(src, bytes, stream, &off);
+        if (rc) return rc;
+        *devPtr = stage.dev(off);
         return BEAGLE_SUCCESS;
     }
 
@@ -496,8 +376,7 @@ struct Instance {
     }
     float* matrixPtr(int idx) const { return matrices + (size_t) idx * matrixFloats; }
 
-    int create(int tipCount_, int partialsBufferCount, int compactBufferCount, int stateCount, int patternCount,
-               int eigenBufferCount, int matrixBufferCount, int categoryCount, int scaleBufferCount, int dev, const Switches& switches);
+    int create(const Dims& dim, int patternCount, int dev, const Switches& switches);   // patternCount: this engine's (a shard's differ from dim.patternCount)
 
     int configureWalk();
     void wgGeometry(int lists, int& W, int& slots) const;
@@ -561,8 +440,7 @@ static int new_engine(std::unique_ptr<Instance>& out, const Dims& d, int pattern
     for (int attempt = 0; attempt < 2; ++attempt) {
         std::unique_ptr<Instance> c(new Instance());
         c->noWalkG = attempt == 1;
-        const int rc = c->create(d.tipCount, d.partialsBufferCount, d.compactBufferCount, d.stateCount, patternCount, d.eigenBufferCount,
-                                 d.matrixBufferCount, d.categoryCount, d.scaleBufferCount, dev, sw);
+        const int rc = c->create(d, patternCount, dev, sw);
         if (rc == BEAGLE_SUCCESS) { out = std::move(c); return rc; }
         const bool retry = rc == BEAGLE_ERROR_OUT_OF_MEMORY && c->wg && attempt == 0;
         c.reset();
@@ -573,23 +451,21 @@ static int new_engine(std::unique_ptr<Instance>& out, const Dims& d, int pattern
 }
 
 // ---------------------------------------------------------------------------------------------
-int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCount, int stateCount,
-                     int patternCount, int eigenBufferCount, int matrixBufferCount, int categoryCount,
-                     int scaleBufferCount, int dev, const Switches& switches)
+int Instance::create(const Dims& dim, int patternCount, int dev, const Switches& switches)
 {
     sw = switches;
     device = dev;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    tipCount = tipCount_;
-    nBuffers = partialsBufferCount + compactBufferCount;
-    S = stateCount;
+    tipCount = dim.tipCount;
+    nBuffers = dim.partialsBufferCount + dim.compactBufferCount;
+    S = dim.stateCount;
     P = patternCount;
     Ppad = round_up(P, 64);
-    K = categoryCount;
-    nEigen = eigenBufferCount;
-    nMatrices = matrixBufferCount;
-    nScale = scaleBufferCount;
+    K = dim.categoryCount;
+    nEigen = dim.eigenBufferCount;
+    nMatrices = dim.matrixBufferCount;
+    nScale = dim.scaleBufferCount;
     // the 4-state tree walk addresses buffers with 32-bit byte offsets inside a (block, category) column set (Walk4Entry)
     s4 = (S == 4 && !sw.forceGeneric && (size_t) nBuffers * K * 1024 < ((size_t) 1 << 32) && (size_t) nMatrices * K * 64 < ((size_t) 1 << 32) &&
           (size_t) (nScale + MBAMD_W4_SCRATCH_ROWS) * K * 64 < ((size_t) 1 << 32));
@@ -703,23 +579,12 @@ int Instance::create(int tipCount_, int partialsBufferCount, int compactBufferCo
     if (wg) nblocks = Ppad / MBAMD_INTEGRATE_WG_PATTERNS;      // the tree-walk layout's integration kernel, whatever the state count
     HIP_TRY(hipHostMalloc(&h_sums, (size_t) nblocks * sizeof(double), hipHostMallocDefault));
     HIP_TRY(hipHostGetDevicePointer((void**) &h_sums_dev, h_sums, 0));
-    if (!sw.noPoll) {
-        if (hipHostMalloc((void**) &h_flag, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer((void**) &h_flag_dev, h_flag, 0) == hipSuccess) {
-            *h_flag = 0;
-            pollResult = true;
-        } else {
-            (void) hipGetLastError();
-        }
-    }
-    stageCap = (size_t) 8 << 20;
-    HIP_TRY(hipHostMalloc(&stage, stageCap, hipHostMallocDefault));
-    HIP_TRY(hipHostGetDevicePointer((void**) &stage_dev, stage, 0));
+    wait.create(!sw.noPoll);
+    { int rc = stage.create((size_t) 8 << 20, 64); if (rc) return rc; }
 
     // defaults: unit rates, uniform category weights, unit pattern weights (BEAGLE clients normally set them)
     std::vector<double> ones(std::max(Ppad, K), 1.0);
     HIP_TRY(hipMemcpy(d_rates, ones.data(), (size_t) K * sizeof(double), hipMemcpyHostToDevice));
-    rateSets.assign(1, RatesArg{});
-    for (int k = 0; k < MBAMD_MAX_RATES; ++k) rateSets[0].r[k] = 1.0;
     std::vector<double> pw(Ppad, 0.0);
     std::fill(pw.begin(), pw.begin() + P, 1.0);
     HIP_TRY(hipMemcpy(d_pweights, pw.data(), (size_t) Ppad * sizeof(double), hipMemcpyHostToDevice));
@@ -751,9 +616,9 @@ Instance::~Instance()
                     d_ev, d_tmp, d_trace};
     for (void* b : bufs) if (b) (void) hipFree(b);
     if (h_sums) (void) hipHostFree(h_sums);
-    if (h_flag) (void) hipHostFree(h_flag);
+    wait.destroy();
     if (h_site) (void) hipHostFree(h_site);
-    if (stage) (void) hipHostFree(stage);
+    stage.destroy();
     for (auto& ev : events) { (void) hipEventDestroy(ev.first); (void) hipEventDestroy(ev.second); }
     for (auto& ev : spans) { (void) hipEventDestroy(ev.first); (void) hipEventDestroy(ev.second); }
     if (spanOpen) (void) hipEventDestroy(spanEv0);
@@ -956,7 +821,7 @@ int Instance::setRateMatrices(int first, int count, const double* q, const doubl
     std::memcpy(h.data(), q, qd * sizeof(double));
     std::memcpy(h.data() + qd, pi, (size_t) S * sizeof(double));
     int rc;
-    if (bytes + 64 <= stageCap / 2) {
+    if (bytes + 64 <= stage.capacity() / 2) {
         rc = stageDirect(h.data(), bytes, (const void**) &dq);
         if (rc) return rc;
     } else {                                                       // (many large matrices at once: a device copy)
@@ -1020,18 +885,11 @@ int Instance::setEigen(int idx, const double* U, const double* Ui, const double*
 
 // beagleUpdateTransitionMatrices only queues its jobs: MrBayes calls it once per eigen-system part (reference
 // src/mbbeagle.c:1475-1486), and all parts of an evaluation go out as ONE launch when the next other call arrives.
-int Instance::setRates(int index, const double* r)
-{
-    if (index < 0 || index > 65535) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "category rates: index");
-    if (K > MBAMD_MAX_RATES) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "more than 16 rate categories");
-    if ((size_t) index >= rateSets.size()) rateSets.resize((size_t) index + 1, rateSets[0]);
-    for (int k = 0; k < K; ++k) rateSets[index].r[k] = r[k];
-    return BEAGLE_SUCCESS;
-}
+int Instance::setRates(int index, const double* r) { return rateSets.set(index, r, K); }
 
 int Instance::updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet)
 {
-    if (rateSet < 0 || (size_t) rateSet >= rateSets.size()) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: category rates index");
+    if (!rateSets.has(rateSet)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: category rates index");
     if (!pendingJobs.empty() && rateSet != pendingRateSet) {       // one rate set per launch
         int frc = flushMatrices();
         if (frc) return frc;
@@ -1045,7 +903,7 @@ int Instance::updateMatrices(int eigenIndex, const int* probIdx, const double* l
     if (pendingMatrixOut.size() != (size_t) nMatrices) pendingMatrixOut.assign(nMatrices, 0);
     bool clash = false;
     for (int i = 0; i < count && !clash; ++i) clash = pendingMatrixOut[probIdx[i]] != 0;
-    if (clash || (pendingJobs.size() + count) * sizeof(MatrixJob) > stageCap / 4) {
+    if (clash || (pendingJobs.size() + count) * sizeof(MatrixJob) > stage.capacity() / 4) {
         int rc = flushMatrices();
         if (rc) return rc;
     }
@@ -2874,28 +2732,15 @@ int Instance::integrate4(const int* parent, const int* child, const int* prob, c
     return BEAGLE_SUCCESS;
 }
 
-// the block sums as their own completion signal: fill them with the pattern fetchResult waits to see overwritten
-void Instance::armSums()
-{
-    sumsArmed = pollResult && !pendingResult && !deferred;
-    if (!sumsArmed) return;
-    uint64_t* p = reinterpret_cast<uint64_t*>(h_sums);
-    for (int i = 0; i < nblocks; ++i) p[i] = kSumSentinel;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-}
-
 // the stream writes the sequence number of this integration behind its kernel: what fetchResult polls
 void Instance::postResultFlag()
 {
-    if (!pollResult) return;
+    if (!wait.poll) return;
     flagWritten = !sumsArmed;                    // (a result awaited through its block sums needs no stream operation behind the kernel)
-    if (!flagWritten) ++flagSeq;                 // (the sequence moves on: nobody will see this number in the flag word, a later one is larger)
-    else if (hipStreamWriteValue32(stream, h_flag_dev, ++flagSeq, 0) != hipSuccess) {
-        (void) hipGetLastError();
-        pollResult = false;
-    }
-    flagClock = launchClock;                     // what the stream has finished when the flag shows flagSeq -- and nothing younger
-    siteSeq = flagSeq;                           // (the integration in front of this flag wrote the site values)
+    if (!flagWritten) ++wait.seq;                // (the sequence moves on: nobody will see this number in the flag word, a later one is larger)
+    else (void) wait.post(stream);               // (refused: polling is off from now on, fetchResult synchronises)
+    flagClock = launchClock;                     // what the stream has finished when the flag shows wait.seq -- and nothing younger
+    siteSeq = wait.seq;                          // (the integration in front of this flag wrote the site values)
 }
 
 int Instance::fetchResult(double* out)
@@ -2904,40 +2749,19 @@ int Instance::fetchResult(double* out)
     {
         StatTimer st_(ST_WAIT);
         bool landed = false, bySums = false;
+        const std::chrono::milliseconds limit(1);                     // of spinning; then the runtime's wait
         if (sumsArmed) {
-            // every block of the integration kernel ends with ONE store of its sum: when all have changed, the kernel has done its work
-            const volatile uint64_t* p = reinterpret_cast<const volatile uint64_t*>(h_sums);
-            const auto t0 = std::chrono::steady_clock::now();
-            int i = 0;
-            for (long spins = 0; i < nblocks; ++spins) {
-                if (p[i] != kSumSentinel) { ++i; continue; }
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) break;
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#endif
-            }
-            landed = bySums = i == nblocks;
-            if (landed) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            landed = bySums = CompletionWait::sumsLanded(h_sums, (size_t) nblocks, limit);
             sumsArmed = false;
         }
-        if (!landed && pollResult && flagWritten) {
-            // spin on the word the stream writes behind the integration kernel, for about a millisecond of wall time; then the runtime's wait
-            volatile uint32_t* f = h_flag;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (long spins = 0; !(landed = (*f == flagSeq)); ++spins) {
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(1)) break;
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#endif
-            }
-            if (landed) __atomic_thread_fence(__ATOMIC_ACQUIRE);      // the block sums were written before the flag: read them after it
-        }
+        // (the block sums were written before the flag: they are read after it)
+        if (!landed && wait.poll && flagWritten) landed = wait.flagLanded(limit);
         // the flag covers the launches up to the integration it follows; launches queued behind it in deferred mode (the reduction of
         // mbamdReduceLogLikelihood, further lists) are complete only after a real synchronisation
         if (landed) syncedClock = std::max(syncedClock, flagClock);
         else { HIP_TRY(hipStreamSynchronize(stream)); syncedClock = launchClock; }
         // (seen through the sums: the kernel's other stores -- the site values -- may still be on their way; getSites then synchronises)
-        if (!bySums || *reinterpret_cast<volatile uint32_t*>(h_flag) == flagSeq) seenSeq = flagSeq;
+        if (!bySums || wait.flagShowsSeq()) seenSeq = wait.seq;
     }
     pendingResult = false;
     double s = 0.0;
@@ -2984,12 +2808,9 @@ static void buildResources()
     g_resources.length = n;
 }
 
-}  // namespace mbamd
-
 // ---------------------------------------------------------------------------------------------
 // per-pattern read-outs as Instance methods (a handle of children gathers them)
 // ---------------------------------------------------------------------------------------------
-namespace mbamd {
 
 int Instance::getSites(double* out)
 {
@@ -3135,10 +2956,6 @@ int Instance::getScaledPartials(int idx, int cumIdx, float* out, float* outLn)
 // =============================================================================================
 // C ABI
 // =============================================================================================
-#include "libhmsbeagle/mbamd_parsimony.h"
-#include "mbamd_parsimony.h"
-#include "mbamd_f64.h"
-
 using namespace mbamd;
 
 // What an instance number of the C ABI stands for.  It owns exactly one of: one single-precision engine ("plain"); a list of
@@ -3437,8 +3254,7 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         // every entry point forwards to the fp64 engine (mbamd_f64.h); one device, no shards
         h->flags = (h->flags & ~BEAGLE_FLAG_PRECISION_SINGLE) | BEAGLE_FLAG_PRECISION_DOUBLE;
         h->f64.reset(new Engine64());
-        rc = h->f64->create(tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount,
-                            matrixBufferCount, categoryCount, scaleBufferCount, dev, sw);
+        rc = h->f64->create(h->dim, patternCount, dev, sw);
     } else if (devices.size() > 1 && patternCount > 64) {
         rc = h->makeChildren(std::vector<std::pair<int, int>>(1, std::make_pair(0, patternCount)));      // pattern shards from the start
     } else {
@@ -3626,7 +3442,7 @@ int beagleSetStateFrequencies(int instance, int idx, const double* f)
     if (h->f64) return h->f64->setFreqs(idx, f);
     API_TRACE("beagleSetStateFrequencies(%d, %s...)", idx, trace_doubles(f, std::min(6, h->dim.stateCount)).c_str());
     if (idx < 0 || idx >= h->dim.eigenBufferCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetStateFrequencies: index");
-    EACH_ENGINE(true, c->uploadIfChanged(c->h_freqs, (size_t) idx * c->S, c->d_freqs, f, c->S));
+    EACH_ENGINE(true, c->setFreqs(idx, f));
 }
 int beagleSetCategoryWeights(int instance, int idx, const double* w)
 {
@@ -3635,7 +3451,7 @@ int beagleSetCategoryWeights(int instance, int idx, const double* w)
     if (h->f64) return h->f64->setWeights(idx, w);
     API_TRACE("beagleSetCategoryWeights(%d, %s)", idx, trace_doubles(w, h->dim.categoryCount).c_str());
     if (idx < 0 || idx >= h->dim.eigenBufferCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetCategoryWeights: index");
-    EACH_ENGINE(true, c->uploadIfChanged(c->h_weights, (size_t) idx * c->K, c->d_weights, w, c->K));
+    EACH_ENGINE(true, c->setWeights(idx, w));
 }
 int beagleSetCategoryRates(int instance, const double* r)
 {
@@ -4248,6 +4064,15 @@ int mbamdGetScaledPartials(int instance, int bufferIndex, int cumulativeScaleInd
 
 
 // ---- Fitch parsimony (include/libhmsbeagle/mbamd_parsimony.h) --------------------------------------------------
+static std::mutex g_parsMutex;
+static std::vector<ParsInstance*> g_pars;
+
+static ParsInstance* pars_lookup(int id)
+{
+    std::lock_guard<std::mutex> lock(g_parsMutex);
+    return id >= 0 && id < (int) g_pars.size() ? g_pars[id] : nullptr;
+}
+
 #define GET_PARS(id)                                                                                 \
     ParsInstance* pi = pars_lookup(id);                                                              \
     if (!pi) return fail(BEAGLE_ERROR_UNINITIALIZED_INSTANCE, "no such parsimony instance");         \

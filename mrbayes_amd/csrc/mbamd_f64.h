@@ -12,6 +12,13 @@
 #ifndef MBAMD_F64_H_
 #define MBAMD_F64_H_
 
+#include <memory>
+#include <utility>
+
+#include "mbamd_host.h"          // fail / HIP_TRY, StatTimer, Switches, Dims; PinnedRing, HostMirror, grow_*, RateSets
+#include "mbamd_kernels.h"       // the device primitives, RatesArg, MBAMD_MAX_SUBSETS
+#include "mbamd_walk4_host.h"    // Walk4Builder: the program compiler of the four-state walk
+
 namespace mbamd {
 
 struct Op64 {
@@ -1250,21 +1257,17 @@ public:
     int32_t* d_scale = nullptr;            // [nScale][Ppad]
     double* d_site = nullptr;              // [Ppad]
     double* d_sums = nullptr;              // [partitions of a call][Ppad/64]
-    size_t sumsCap = 0;
     double* d_ev = nullptr;
-    size_t evCap = 0;
     void* d_stage = nullptr;
-    size_t stageCap = 0;
+    size_t sumsCap = 0, evCap = 0, stageCap = 0, hSumsCap = 0;      // bytes behind d_sums, d_ev, d_stage, h_sums
     // small host -> device transfers (operation lists, matrix jobs, weights, frequencies) go through a ring: the bytes are copied into
     // pinned host memory, from there asynchronously into the device ring's slot of the same offset, and a slot is written again only
     // after the ring wrapped -- one stream synchronisation per RING_BYTES instead of one per call (a codon M3 evaluation made ten).
     static constexpr size_t RING_BYTES = 4u << 20, RING_MAX_ITEM = 256u << 10;
-    uint8_t* h_ring = nullptr;
-    uint8_t* d_ring = nullptr;
-    size_t ringPos = 0;
+    PinnedRing ring;                       // 256-byte slots, allocated on first use ...
+    uint8_t* d_ring = nullptr;             // ... with its device-side twin
     double* h_sums = nullptr;              // pinned: the block sums of a log-likelihood call
-    size_t hSumsCap = 0;
-    std::vector<RatesArg> rateSets;
+    RateSets rateSets;
     bool haveSite = false;
     std::vector<std::pair<int, int>> parts;       // v3: [first, last) of every pattern partition (empty: none were set)
     // four-state tree walk (k64_walk4): the program compiler, its latest program (re-used when the same list comes again)
@@ -1285,12 +1288,11 @@ public:
 
     static int blockOf(int S) { return S <= 4 ? 4 : S <= 8 ? 8 : S <= 16 ? 16 : S <= 20 ? 20 : 32; }
 
-    int create(int tips, int partialsBuffers, int compactBuffers, int states, int patterns, int eigens, int matrices, int cats, int scales, int dev,
-               const Switches& switches)
+    int create(const Dims& dim, int patterns, int dev, const Switches& switches)
     {
         sw = switches;
-        device = dev; tipCount = tips; nBuffers = partialsBuffers + compactBuffers; S = states; P = patterns; Ppad = round_up(patterns, 64);
-        K = cats; nEigen = eigens; nMatrices = matrices; nScale = scales;
+        device = dev; tipCount = dim.tipCount; nBuffers = dim.partialsBufferCount + dim.compactBufferCount; S = dim.stateCount; P = patterns; Ppad = round_up(patterns, 64);
+        K = dim.categoryCount; nEigen = dim.eigenBufferCount; nMatrices = dim.matrixBufferCount; nScale = dim.scaleBufferCount;
         IB = blockOf(S);
         SPAD = (S + IB - 1) / IB * IB;
         bufDoubles = (size_t) K * S * Ppad;
@@ -1312,13 +1314,11 @@ public:
         HIP_TRY(hipMalloc(&d_scale, (size_t) (nScale + 1) * Ppad * sizeof(int32_t)));
         HIP_TRY(hipMemsetAsync(d_scale, 0, (size_t) (nScale + 1) * Ppad * sizeof(int32_t), stream));
         HIP_TRY(hipMalloc(&d_site, (size_t) Ppad * sizeof(double)));
-        sumsCap = (size_t) (Ppad / 64);
-        HIP_TRY(hipMalloc(&d_sums, sumsCap * sizeof(double)));
+        HIP_TRY(hipMalloc(&d_sums, (size_t) (Ppad / 64) * sizeof(double)));
+        sumsCap = (size_t) (Ppad / 64) * sizeof(double);
         isTip.assign((size_t) nBuffers, 0);
         stateSlot.assign((size_t) nBuffers, -1);
         valid.assign((size_t) nBuffers, 0);
-        rateSets.assign(1, RatesArg());
-        for (int k = 0; k < MBAMD_MAX_RATES; ++k) rateSets[0].r[k] = 1.0;
         std::vector<double> ones((size_t) Ppad, 0.0);
         for (int c = 0; c < P; ++c) ones[c] = 1.0;
         HIP_TRY(hipMemcpyAsync(d_pweights, ones.data(), (size_t) Ppad * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1334,7 +1334,7 @@ public:
         for (void* p : all)
             if (p) (void) hipFree(p);
         if (d_ring) (void) hipFree(d_ring);
-        if (h_ring) (void) hipHostFree(h_ring);
+        ring.destroy();
         if (h_sums) (void) hipHostFree(h_sums);
         (void) hipStreamDestroy(stream);
         live = false;
@@ -1344,19 +1344,13 @@ public:
     {
         *hostSlot = *devSlot = nullptr;
         if (bytes > RING_MAX_ITEM || sw.f64NoRing) return BEAGLE_SUCCESS;
-        if (h_ring == nullptr) {
-            HIP_TRY(hipHostMalloc((void**) &h_ring, RING_BYTES, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void**) &d_ring, RING_BYTES));
-        }
-        const size_t need = (bytes + 255) & ~(size_t) 255;
-        if (ringPos + need > RING_BYTES) {
-            HIP_TRY(hipStreamSynchronize(stream));              // every slot's copy and its readers are behind us
-            ringPos = 0;
-        }
-        *hostSlot = h_ring + ringPos;
-        *devSlot = d_ring + ringPos;
-        ringPos += need;
-        std::memcpy(*hostSlot, src, bytes);
+        if (!ring.live()) { const int rc = ring.create(RING_BYTES, 256); if (rc) return rc; }
+        if (d_ring == nullptr) HIP_TRY(hipMalloc((void**) &d_ring, RING_BYTES));
+        size_t off = 0;
+        const int rc = ring.put(src, bytes, stream, &off);      // (wrapped: every slot's copy and its readers are behind us)
+        if (rc) return rc;
+        *hostSlot = ring.host(off);
+        *devSlot = d_ring + off;
         return BEAGLE_SUCCESS;
     }
     int stage(const void* src, size_t bytes, void** out)
@@ -1372,12 +1366,7 @@ public:
             }
         }
         HIP_TRY(hipStreamSynchronize(stream));                  // (the staging buffer is re-used: wait for its last reader)
-        if (bytes > stageCap) {
-            if (d_stage) (void) hipFree(d_stage);
-            d_stage = nullptr;
-            stageCap = std::max(bytes * 2, (size_t) 65536);
-            HIP_TRY(hipMalloc(&d_stage, stageCap));
-        }
+        { const int rc = grow_device(stream, &d_stage, &stageCap, bytes, std::max(bytes * 2, (size_t) 65536)); if (rc) return rc; }
         HIP_TRY(hipMemcpyAsync(d_stage, src, bytes, hipMemcpyHostToDevice, stream));
         *out = d_stage;
         return BEAGLE_SUCCESS;
@@ -1452,45 +1441,24 @@ public:
         std::memcpy(h.data() + (size_t) 2 * S * S, lam, sizeof(double) * S);
         return upload(d_eigen + (size_t) idx * eigDoubles, h.data(), eigDoubles * sizeof(double));
     }
-    // host mirrors of the frequencies / weights on the device (NaN = nothing sent yet): true when `v` is what the device already holds
-    std::vector<double> hostFreqs, hostWeights;
-    static void forget(std::vector<double>& mirror, size_t at, size_t n)
-    {
-        for (size_t i = 0; i < n && at + i < mirror.size(); ++i) mirror[at + i] = std::numeric_limits<double>::quiet_NaN();
-    }
-    static bool sameAsLast(std::vector<double>& mirror, size_t total, size_t at, const double* v, size_t n)
-    {
-        if (mirror.size() != total) mirror.assign(total, std::numeric_limits<double>::quiet_NaN());
-        if (std::memcmp(mirror.data() + at, v, n * sizeof(double)) == 0) return true;      // (bitwise: a NaN pattern never equals user data by accident of -0.0 / 0.0)
-        std::memcpy(mirror.data() + at, v, n * sizeof(double));
-        return false;
-    }
+    HostMirror hostFreqs, hostWeights;     // of d_freqs / d_weights
     int setFreqs(int idx, const double* f)
     {
         { const int rcq = flushQueue(); if (rcq) return rcq; }
         if (idx < 0 || idx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetStateFrequencies: index");
         // (MrBayes sets the frequencies and category weights of every eigen part before every evaluation: unchanged values are not sent again)
-        if (sameAsLast(hostFreqs, (size_t) nEigen * S, (size_t) idx * S, f, (size_t) S)) return BEAGLE_SUCCESS;
-        const int rc = upload(d_freqs + (size_t) idx * S, f, (size_t) S * sizeof(double));
-        if (rc) forget(hostFreqs, (size_t) idx * S, (size_t) S);       // (the device kept the old vector: the next identical call must send again)
-        return rc;
+        return hostFreqs.send((size_t) nEigen * S, (size_t) idx * S, f, (size_t) S, [&] { return upload(d_freqs + (size_t) idx * S, f, (size_t) S * sizeof(double)); });
     }
     int setWeights(int idx, const double* w)
     {
         { const int rcq = flushQueue(); if (rcq) return rcq; }
         if (idx < 0 || idx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetCategoryWeights: index");
-        if (sameAsLast(hostWeights, (size_t) nEigen * K, (size_t) idx * K, w, (size_t) K)) return BEAGLE_SUCCESS;
-        const int rc = upload(d_weights + (size_t) idx * K, w, (size_t) K * sizeof(double));
-        if (rc) forget(hostWeights, (size_t) idx * K, (size_t) K);
-        return rc;
+        return hostWeights.send((size_t) nEigen * K, (size_t) idx * K, w, (size_t) K, [&] { return upload(d_weights + (size_t) idx * K, w, (size_t) K * sizeof(double)); });
     }
     int setRates(int index, const double* r)
     {
         { const int rcq = flushQueue(); if (rcq) return rcq; }
-        if (index < 0 || index > 65535) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "category rates: index");
-        if ((size_t) index >= rateSets.size()) rateSets.resize((size_t) index + 1, rateSets[0]);
-        for (int k = 0; k < K; ++k) rateSets[index].r[k] = r[k];
-        return BEAGLE_SUCCESS;
+        return rateSets.set(index, r, K);
     }
     int setPatternWeights(const double* w)
     {
@@ -1529,14 +1497,9 @@ public:
         void* dj = nullptr;
         int rc = stage(jobs.data(), jobs.size() * sizeof(MatrixJob64), &dj);
         if (rc) return rc;
-        const size_t need = (size_t) count * K * S;
-        if (need > evCap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (d_ev) (void) hipFree(d_ev);
-            d_ev = nullptr;
-            evCap = need * 2;
-            HIP_TRY(hipMalloc(&d_ev, evCap * sizeof(double)));
-        }
+        const size_t need = (size_t) count * K * S * sizeof(double);
+        rc = grow_device(stream, (void**) &d_ev, &evCap, need, need * 2);
+        if (rc) return rc;
         const int total = count * K * S;
         MBAMD_LAUNCH(k64_exponentials, (unsigned) ((total + 255) / 256), 256, 0, stream, (const MatrixJob64*) dj, rateSets[matQueueRate], S, K, total, d_ev);
         launchMatrices((const MatrixJob64*) dj, count);
@@ -1548,7 +1511,7 @@ public:
         if (!queue.empty()) { const int rcq = flushQueue(); if (rcq) return rcq; }        // (queued operations read the matrices as they are now)
         if (count <= 0) return BEAGLE_SUCCESS;
         if (eigenIdx < 0 || eigenIdx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: eigen index");
-        if (rateIdx < 0 || (size_t) rateIdx >= rateSets.size()) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: rate index");
+        if (!rateSets.has(rateIdx)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: rate index");
         for (int i = 0; i < count; ++i)
             if (prob[i] < 0 || prob[i] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: matrix index");
         if (!matQueue.empty() && (matQueueRate != rateIdx || matQueue.size() + (size_t) count > 60000)) { const int rc = flushMatrices(); if (rc) return rc; }
@@ -2151,22 +2114,10 @@ public:
         const int pc = partitions ? partitionCount : 1;
         const int nblocks = Ppad / 64;
         const size_t nsums = (size_t) nblocks * pc;
-        if (nsums > hSumsCap) {
-            if (h_sums) (void) hipHostFree(h_sums);
-            h_sums = nullptr;
-            hSumsCap = 0;
-            HIP_TRY(hipHostMalloc((void**) &h_sums, nsums * sizeof(double), hipHostMallocDefault));
-            hSumsCap = nsums;
-        }
+        { const int rc = grow_pinned(stream, (void**) &h_sums, &hSumsCap, nsums * sizeof(double), nsums * sizeof(double)); if (rc) return rc; }
+        { const int rc = grow_device(stream, (void**) &d_sums, &sumsCap, nsums * sizeof(double), nsums * sizeof(double)); if (rc) return rc; }
         double* const h = h_sums;
         std::vector<int> blocksOf((size_t) pc);
-        if ((size_t) nblocks * pc > sumsCap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (d_sums) (void) hipFree(d_sums);
-            d_sums = nullptr;
-            sumsCap = (size_t) nblocks * pc;
-            HIP_TRY(hipMalloc(&d_sums, sumsCap * sizeof(double)));
-        }
         for (int d = 0; d < pc; ++d) {
             int first = 0, last = P;
             if (partitions) {

@@ -1,5 +1,7 @@
 // mbamd_integrate_wg.h -- root / edge integration for the 20/61-state tree-walk layout (included by mbamd_kernels.h inside namespace
 // mbamd).  Product and TEST-ONLY host emulation compile this same kernel (the emulation runs its 256 threads as fibers).
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_INTEGRATE_WG_H_
 #define MBAMD_INTEGRATE_WG_H_
 #define MBAMD_INTEGRATE_WG_THREADS 256

@@ -43,6 +43,7 @@
 
 #include <stdint.h>
 
+#include <mbamd_dev_runtime.h>   // __global__, threadIdx, the launch macros (csrc/device/)
 #include <mbamd_dev_base.h>      // MBAMD_AS_GLOBAL / MBAMD_AS_CONST, f4, mbd_* primitives (csrc/device/)
 
 namespace mbamd {
@@ -278,9 +279,9 @@ struct MatrixJob {
     double pad_;
 };
 
-// category rates travel as a kernel argument (no host-to-device copy per beagleSetCategoryRates)
-#define MBAMD_MAX_RATES 16
-struct RatesArg { double r[MBAMD_MAX_RATES]; };
+}  // namespace mbamd
+#include "mbamd_rates.h"         // RatesArg: category rates travel as a kernel argument
+namespace mbamd {
 
 // exp(lambda*t) hoisted: one thread per (job, k, s) fills ev[(job*K+k)*S + s]; the matrix kernel
 // below then reads it (second launch on the same stream, so no barrier is needed).

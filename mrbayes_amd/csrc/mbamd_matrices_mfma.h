@@ -1,6 +1,8 @@
 // mbamd_matrices_mfma.h -- transition matrices of the general-state paths on the fp64 matrix cores (included by mbamd_kernels.h's
 // users after mbamd_walkg.h: it fills the tree walk's tables).  Written against mbd_mfma_f64_16x16x4 (<mbamd_dev_base.h>): the
 // product and the TEST-ONLY host emulation compile this same kernel.
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_MATRICES_MFMA_H_
 #define MBAMD_MATRICES_MFMA_H_
 namespace mbamd {

@@ -1,5 +1,5 @@
 // mbamd_parsimony.h -- Fitch parsimony on the device (include/libhmsbeagle/mbamd_parsimony.h).
-// Included at the end of mbamd_engine.cpp: kernels, the host object behind a parsimony handle, and the C ABI.
+// The kernels and the host object behind a parsimony handle (ParsInstance); the C ABI over it is in mbamd_engine.cpp.
 //
 // HBM layout: sets[setIndex][P_pad] of T, T the narrowest unsigned type holding the division's state bits (u8 DNA / RNA,
 // u16, u32 amino acids, u64 codons, 2 x u64 beyond): one byte per node and pattern for DNA where the reference moves eight
@@ -9,6 +9,12 @@
 // is one wave's instruction stream and dependency chain, not HBM (a pass at 500 taxa x 20 000 patterns moves 30 MB).
 #ifndef MBAMD_PARSIMONY_H_
 #define MBAMD_PARSIMONY_H_
+
+#include <utility>
+
+#include "libhmsbeagle/mbamd_parsimony.h"
+#include "mbamd_host.h"          // fail / HIP_TRY, StatTimer, Switches; CompletionWait, grow_pinned
+#include "mbamd_kernels.h"       // the device primitives, k_copy_from_ring4
 
 namespace mbamd {
 
@@ -231,13 +237,11 @@ public:
     int next = 0;
     double* d_out = nullptr;                         // per-block partial sums: where the kernels write them -- the device address of h_out
     double* h_out = nullptr;                         // pinned, mapped: the host reads the sums where the kernels put them (no copy)
-    size_t outCap = 0;
-    // a result is waited for by polling a word the stream writes behind the kernel (as Instance::fetchResult does: the runtime's
-    // wait on a stream costs ~25 us); MBAMD_NO_POLL=1: hipStreamSynchronize
-    uint32_t* h_flag = nullptr;                      // pinned
-    uint32_t* h_flag_dev = nullptr;
-    uint32_t flagSeq = 0;
-    bool poll = false;
+    size_t outCap = 0;                               // bytes
+    // a result is waited for by polling (CompletionWait, mbamd_host.h: the runtime's wait on a stream costs ~25 us) -- the sums the
+    // next launch writes are armed; only if they do not land in 2 ms does the stream write the flag word; MBAMD_NO_POLL=1: hipStreamSynchronize
+    CompletionWait wait;
+    size_t armed = 0;                                // sums the launch in flight was armed for
     void* h_stage = nullptr;                         // pinned: one set in the device type
     static constexpr int SCORE_Y = 4;
     struct Pending {
@@ -295,13 +299,7 @@ public:
         HIP_TRY(hipHostMalloc(&h_stage, (size_t) Ppad * 16, hipHostMallocDefault));
         HIP_TRY(hipStreamSynchronize(stream));
         state.assign((size_t) nSets + 2, SetState());
-        if (!sw.noPoll && hipHostMalloc((void**) &h_flag, 64, hipHostMallocDefault) == hipSuccess &&
-            hipHostGetDevicePointer((void**) &h_flag_dev, h_flag, 0) == hipSuccess) {
-            *h_flag = 0;
-            poll = true;
-        } else {
-            (void) hipGetLastError();
-        }
+        wait.create(!sw.noPoll);
         if (sw.parsPhaseLimit) phaseLimit = std::max(1, std::min(MBAMD_PARS_MAXPHASES, *sw.parsPhaseLimit));
         if (sw.parsWaves) waves = std::max(1, std::min(MBAMD_PARS_MAXW, *sw.parsWaves));
         return BEAGLE_SUCCESS;
@@ -325,10 +323,10 @@ public:
             d_wbuf[i] = nullptr; h_wpin[i] = nullptr; wBusy[i] = false;
         }
         if (h_out) (void) hipHostFree(h_out);
-        if (h_flag) (void) hipHostFree(h_flag);
+        wait.destroy();
         if (h_stage) (void) hipHostFree(h_stage);
         (void) hipStreamDestroy(stream);
-        d_sets = nullptr; d_w = nullptr; d_out = nullptr; h_out = nullptr; h_stage = nullptr; h_flag = nullptr; h_flag_dev = nullptr; poll = false; outCap = 0;
+        d_sets = nullptr; d_w = nullptr; d_out = nullptr; h_out = nullptr; h_stage = nullptr; outCap = 0;
         live = false;
     }
 
@@ -457,64 +455,25 @@ public:
     }
     int growOut(size_t doubles)
     {
-        if (doubles <= outCap) return BEAGLE_SUCCESS;
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (h_out) (void) hipHostFree(h_out);
-        d_out = nullptr; h_out = nullptr;
-        outCap = std::max(doubles * 2, (size_t) 4096);
-        HIP_TRY(hipHostMalloc((void**) &h_out, outCap * sizeof(double), hipHostMallocDefault));
+        if (doubles * sizeof(double) <= outCap) return BEAGLE_SUCCESS;
+        const int rc = grow_pinned(stream, (void**) &h_out, &outCap, doubles * sizeof(double), std::max(doubles * 2, (size_t) 4096) * sizeof(double));
+        if (!h_out) d_out = nullptr;
+        if (rc) return rc;
         HIP_TRY(hipHostGetDevicePointer((void**) &d_out, h_out, 0));
         return BEAGLE_SUCCESS;
     }
-    // Round 6: the sums are their own completion signal (as the likelihood engine's block sums, mbamd_engine.cpp armSums): the host
-    // fills the `count` sums the next launch writes with a bit pattern no sum has, and waits until all of them have changed -- no
-    // stream operation behind the kernel.
-    static constexpr uint64_t kSumSentinel = 0x7FF4DEADBEEF0001ull;
-    size_t armed = 0;
-    void armSums(size_t count)
-    {
-        armed = poll ? count : 0;
-        uint64_t* p = reinterpret_cast<uint64_t*>(h_out);
-        for (size_t i = 0; i < armed; ++i) p[i] = kSumSentinel;
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-    }
+    // the sums are their own completion signal: the `count` sums the next launch writes
+    void armSums(size_t count) { armed = wait.arm(h_out, count) ? count : 0; }
     // the kernels queued so far have written their sums into h_out when this returns
     int waitForSums()
     {
         StatTimer st_(ST_PARS_WAIT);
-        bool landed = false;
-        if (armed) {
-            const volatile uint64_t* p = reinterpret_cast<const volatile uint64_t*>(h_out);
-            const auto t0 = std::chrono::steady_clock::now();
-            size_t i = 0;
-            for (long spins = 0; i < armed; ++spins) {
-                if (p[i] != kSumSentinel) { ++i; continue; }
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#endif
-            }
-            landed = i == armed;
-            armed = 0;
-            if (landed) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return BEAGLE_SUCCESS; }
-        }
-        if (poll) {
-            if (hipStreamWriteValue32(stream, h_flag_dev, ++flagSeq, 0) != hipSuccess) {
-                (void) hipGetLastError();
-                poll = false;
-            } else {
-                volatile uint32_t* f = h_flag;
-                const auto t0 = std::chrono::steady_clock::now();
-                for (long spins = 0; !(landed = (*f == flagSeq)); ++spins) {
-                    if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-#if defined(__x86_64__) || defined(__i386__)
-                    __builtin_ia32_pause();
-#endif
-                }
-                if (landed) __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            }
-        }
-        if (!landed) HIP_TRY(hipStreamSynchronize(stream));
+        const std::chrono::milliseconds limit(2);                   // of spinning; then the runtime's wait
+        const size_t n = armed;
+        armed = 0;
+        if (n && CompletionWait::sumsLanded(h_out, n, limit)) return BEAGLE_SUCCESS;
+        if (wait.poll && wait.post(stream) && wait.flagLanded(limit)) return BEAGLE_SUCCESS;
+        HIP_TRY(hipStreamSynchronize(stream));
         return BEAGLE_SUCCESS;
     }
 
@@ -871,15 +830,6 @@ public:
         return BEAGLE_SUCCESS;
     }
 };
-
-static std::mutex g_parsMutex;
-static std::vector<ParsInstance*> g_pars;
-
-static ParsInstance* pars_lookup(int id)
-{
-    std::lock_guard<std::mutex> lock(g_parsMutex);
-    return id >= 0 && id < (int) g_pars.size() ? g_pars[id] : nullptr;
-}
 
 }  // namespace mbamd
 

@@ -30,6 +30,8 @@
 // its way to publish it with every factor it needs for that already in the ring or coming without a further wait on `parked`.  The
 // tile is not overwritten while it is read: the next START comes after the JOIN, whose factor wave 0 takes only after wave 1 has
 // read the tile into registers, contracted it and published the product.
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_PATHG_KERNEL_H_
 #define MBAMD_PATHG_KERNEL_H_
 namespace mbamd {

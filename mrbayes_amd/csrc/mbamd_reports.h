@@ -25,6 +25,8 @@
 #ifndef MBAMD_REPORTS_H_
 #define MBAMD_REPORTS_H_
 
+#include "mbamd_kernels.h"       // the device primitives, the buffer layouts
+
 namespace mbamd {
 
 // LAYOUT as in k_import_partials: 0 general tile-major buffer, 1 4-state arena, 2 20/61-state tree-walk arena

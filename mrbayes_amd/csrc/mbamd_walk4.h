@@ -37,6 +37,8 @@
 // The stores are non-temporal: a result is never read again in the launch that wrote it (parents read the LDS copy), and
 // letting 0.7 GB of write-allocated lines stream through L2 evicted the matrices and programs every wave keeps
 // re-reading -- every scalar load then paid an HBM round trip (measured: 1.6x on the whole kernel).
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_WALK4_H_
 #define MBAMD_WALK4_H_
 

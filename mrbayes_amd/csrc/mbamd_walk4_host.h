@@ -29,6 +29,8 @@
 #include <utility>
 #include <vector>
 
+#include "mbamd_kernels.h"       // Walk4Entry and the MBAMD_W4_* entry codes (mbamd_walk4.h)
+
 namespace mbamd {
 
 // one operation of the list, buffer indices only

@@ -29,6 +29,8 @@
 // operands of job u+2 are fetched into the third of three register sets: the A rows (or the tip's gather rows) and, for
 // a child that lives in HBM (result of an earlier launch, of another wave, or evicted), its B rows.  Tip states are
 // fetched one entry earlier still, entry descriptors three entries ahead through the scalar cache.
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_WALKG_H_
 #define MBAMD_WALKG_H_
 

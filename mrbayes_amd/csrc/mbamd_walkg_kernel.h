@@ -2,6 +2,8 @@
 // holds the layouts, tables and arguments, shared with the host).  Written against the primitives of <mbamd_dev_walkg_kernel.h>
 // (csrc/device/ for gfx950; the TEST-ONLY host emulation supplies the same names on fibers), so this file is compiled into the
 // product AND run, as is, by the CPU CI.
+// (a part of mbamd_kernels.h, which includes this file where it belongs: included on its own, it brings the whole in first)
+#include "mbamd_kernels.h"
 #ifndef MBAMD_WALKG_KERNEL_H_
 #define MBAMD_WALKG_KERNEL_H_
 namespace mbamd {

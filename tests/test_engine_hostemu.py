@@ -45,6 +45,25 @@ def test_product_sources_have_no_emulation_fork():
         assert os.path.exists(os.path.join(root, "tests", "hostemu", f)), "no emulation twin for " + f
 
 
+def test_every_engine_header_compiles_alone(tmp_path):
+    """Every header directly under mrbayes_amd/csrc/ includes what it uses: a source that includes nothing else compiles, whatever
+    the order in which mbamd_engine.cpp happens to include them."""
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "mrbayes_amd", "csrc")
+    headers = sorted(f for f in os.listdir(csrc) if f.endswith(".h"))
+    assert "mbamd_host.h" in headers and "mbamd_f64.h" in headers and "mbamd_parsimony.h" in headers, headers
+    def alone(h):
+        src = tmp_path / (h[:-2] + "_alone.cpp")
+        src.write_text('#include "%s"\n' % h)
+        return subprocess.run([build_emu.host_compiler(), "-fsyntax-only", "-std=c++17", "-w", "-I", os.path.join(root, "tests", "hostemu"),
+                               "-I", os.path.join(root, "include"), "-I", csrc, str(src)], capture_output=True, text=True)
+    with ThreadPoolExecutor(max_workers=8) as pool:            # (a second or so per header: side by side)
+        failed = {h: r.stderr[:2000] for h, r in zip(headers, pool.map(alone, headers)) if r.returncode != 0}
+    assert not failed, "\n".join("%s:\n%s" % kv for kv in failed.items())
+
+
 def test_engine_switches_read_in_one_place():
     """The engine reads its environment in mrbayes_amd/csrc/mbamd_switches.h only, and INTEGRATION.md names every switch read there."""
     import os
