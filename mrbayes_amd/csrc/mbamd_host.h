@@ -1,4 +1,4 @@
-// mbamd_host.h -- the host runtime the library's three engines share: the single-precision engine (Instance, mbamd_engine.cpp),
+// mbamd_host.h -- the host runtime the library's three engines share: the single-precision engine (Instance, mbamd_f32.h),
 // the double-precision engine (Engine64, mbamd_f64.h) and the parsimony engine (ParsInstance, mbamd_parsimony.h).  Each of them
 // owns a stream and talks to one device; what they all need for that is here, once:
 //   diagnostics      the switches read when the library loads, MBAMD_STATS timers, MBAMD_API_TRACE lines, fail / HIP_TRY

@@ -1,4 +1,4 @@
-// mbamd_reports.h -- the final ("up") pass and the scaled read-out of conditional likelihoods (included by mbamd_engine.cpp).
+// mbamd_reports.h -- the final ("up") pass and the scaled read-out of conditional likelihoods (included by mbamd_f32.h).
 //
 // what MrBayes computes when a run reports ancestral states, site rates, positively selected sites or
 // site omegas -- CondLikeUp_Bin / _Gen / _NUC4 (reference src/likelihood.c:4574-4795) and the read-outs PrintAncStates_*,

@@ -434,6 +434,70 @@ def check_hazard_lists(lib, nstates, ncat, npat, seed=5, double_precision=False)
         assert np.array_equal(a, b)
 
 
+def check_scale_factor_calls(lib, kind, ncat, npat, monkeypatch, shards=None):
+    """beagleReset / Accumulate / Remove / CopyScaleFactors on cumulative buffers of the client's own, after one full evaluation
+    with always-rescale on 8 taxa: the three storage forms of a scale buffer (4 states: int8 exponents in the arena; 20: the
+    general-state arena; 33: one int32 buffer per pattern on the level kernels, where a reset waits for the accumulate that
+    follows it and the two run as one store), and under MBAMD_SHARD child engines.  Expected values are integer sums of the
+    node buffers' exponents: equality is exact."""
+    if shards is None:
+        monkeypatch.delenv("MBAMD_SHARD", raising=False)
+    else:
+        monkeypatch.setenv("MBAMD_SHARD", str(shards))
+    # (branches of 0.6: every node's partials fall below 1/2 somewhere, so the node buffers hold non-zero exponents)
+    div = synthetic_division(kind, 8, npat, seed=91, tree_seed=92, ncat=ncat, brlen=0.6)
+    bd = lk.BeagleDivision(div, lib)
+    inst = bd.inst
+    try:
+        if shards is not None:
+            assert inst.child_count() == min(shards, (npat + 63) // 64)
+        bd.LogLike(0)
+        t = div.tree
+        nodes = [bd.nodeScalerIndex[0][p] for p in t.int_down_pass]
+        exps = [inst.get_scale_exponents(i).astype(np.int64) for i in nodes]
+        assert exps[0].shape == (ncat, npat)
+        assert any(e.any() for e in exps)
+        total = sum(exps)
+        assert np.array_equal(inst.get_scale_exponents(bd.siteScalerIndex[0]), total)      # what the evaluation itself accumulated
+        # buffers the evaluation never used: the flip partners of the node buffers, and of the site buffer
+        free = [bd.nodeScalerScratchIndex[p] for p in t.int_down_pass]
+        cum, fourth, never = bd.siteScalerScratchIndex, free[0], free[1]
+        zero = np.zeros((ncat, npat), dtype=np.int64)
+        read = inst.get_scale_exponents
+
+        inst.reset_scale_factors(cum)
+        assert np.array_equal(read(cum), zero)
+        inst.accumulate_scale_factors(nodes, cum)
+        assert np.array_equal(read(cum), total)
+        inst.reset_scale_factors(cum)                       # reset + accumulate back to back (33 states: one store)
+        inst.accumulate_scale_factors(nodes, cum)
+        assert np.array_equal(read(cum), total)
+        inst.reset_scale_factors(cum)                       # another call in between
+        assert np.array_equal(read(nodes[0]), exps[0])
+        inst.accumulate_scale_factors(nodes, cum)
+        assert np.array_equal(read(cum), total)
+        inst.reset_scale_factors(cum)                       # the buffer among its own sources
+        inst.accumulate_scale_factors(nodes[:2] + [cum] + nodes[2:], cum)
+        assert np.array_equal(read(cum), total)
+        inst.reset_scale_factors(cum)                       # an index out of range: the error, and the reset still happened
+        with pytest.raises(bg.BeagleError) as e:
+            inst.accumulate_scale_factors(nodes[:2] + [bd.numScalers * bd.step], cum)
+        assert e.value.code == bg.BEAGLE_ERROR_OUT_OF_RANGE and "scale factors: index" in str(e.value)
+        assert np.array_equal(read(cum), zero)
+        inst.accumulate_scale_factors(nodes, cum)
+        half = nodes[: len(nodes) // 2]
+        inst.remove_scale_factors(half, cum)
+        assert np.array_equal(read(cum), total - sum(exps[: len(half)]))
+        for src, want in ((cum, total - sum(exps[: len(half)])), (nodes[1], exps[1]), (never, zero)):
+            inst.copy_scale_factors(fourth, src)
+            assert np.array_equal(read(fourth), want)
+            assert np.array_equal(read(src), want)
+    finally:
+        bd.finalize()
+        if shards is not None:
+            monkeypatch.delenv("MBAMD_SHARD")
+
+
 def check_sharded_instance(lib, oracle, div, monkeypatch, shards=3):
     """Site-pattern sharding inside one instance: MBAMD_SHARD=<g> (or a resource list with several GPUs)
     splits the patterns over g child engines -- here g children on the same device.  Every read-out equals the unsharded

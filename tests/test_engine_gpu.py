@@ -514,6 +514,11 @@ def test_handle_roles(gpu, monkeypatch):
     ec.check_handle_roles(gpu, monkeypatch)
 
 
+@pytest.mark.parametrize("kind,ncat,npat,shards", [("gtr", 2, 130, None), ("gtr", 2, 130, 3), ("wag", 2, 70, None), ("gen33", 1, 70, None)])
+def test_scale_factor_calls(gpu, monkeypatch, kind, ncat, npat, shards):
+    ec.check_scale_factor_calls(gpu, kind, ncat, npat, monkeypatch, shards)
+
+
 def test_instances_created_and_destroyed_repeatedly(gpu):
     """Buffers land at different device addresses every time (address-dependent bugs, e.g. a pointer whose low
     half has bit 31 set, show up here); results must not move."""

@@ -53,7 +53,7 @@ def test_every_engine_header_compiles_alone(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "mrbayes_amd", "csrc")
     headers = sorted(f for f in os.listdir(csrc) if f.endswith(".h"))
-    assert "mbamd_host.h" in headers and "mbamd_f64.h" in headers and "mbamd_parsimony.h" in headers, headers
+    assert "mbamd_host.h" in headers and "mbamd_f32.h" in headers and "mbamd_f64.h" in headers and "mbamd_parsimony.h" in headers, headers
     def alone(h):
         src = tmp_path / (h[:-2] + "_alone.cpp")
         src.write_text('#include "%s"\n' % h)
@@ -212,6 +212,11 @@ def test_error_codes(emu, monkeypatch):
 
 def test_handle_roles(emu, monkeypatch):
     ec.check_handle_roles(emu, monkeypatch)
+
+
+@pytest.mark.parametrize("kind,ncat,npat,shards", [("gtr", 2, 130, None), ("gtr", 2, 130, 3), ("wag", 2, 70, None), ("gen33", 1, 70, None)])
+def test_scale_factor_calls(emu, monkeypatch, kind, ncat, npat, shards):
+    ec.check_scale_factor_calls(emu, kind, ncat, npat, monkeypatch, shards)
 
 
 @pytest.mark.parametrize("waves", [2, 3, 4, 8])
