@@ -216,8 +216,13 @@ BEAGLE_DLLEXPORT int beagleSetPatternWeights(int instance, const double* inPatte
  * transition matrices
  * ------------------------------------------------------------------------------------------- */
 /* reference src/mbbeagle.c:1477-1483: P_k = U diag(exp(lambda * rate_k * t)) U^-1 for each listed
- * branch, negatives clamped to 0 like the native path (src/likelihood.c:9540).  Derivative index
- * lists must be NULL (MrBayes always passes NULL). */
+ * branch, negatives clamped to 0 like the native path (src/likelihood.c:9540).  Either derivative index
+ * list may be NULL (MrBayes always passes NULL), independently of the other; where given, matrix buffer
+ * firstDerivativeIndices[i] takes P'_k = dP_k/dt = U diag(lambda rate_k exp(lambda rate_k t)) U^-1 and
+ * secondDerivativeIndices[i] takes P''_k = U diag((lambda rate_k)^2 exp(lambda rate_k t)) U^-1 of branch i.  They
+ * are ordinary matrix buffers (read back by beagleGetTransitionMatrix as [category][from][to]) and are not
+ * clamped: their entries are legitimately negative.  A derivative index equal to another output of the same
+ * call is BEAGLE_ERROR_OUT_OF_RANGE. */
 BEAGLE_DLLEXPORT int beagleUpdateTransitionMatrices(int instance, int eigenIndex, const int* probabilityIndices,
                                                     const int* firstDerivativeIndices,
                                                     const int* secondDerivativeIndices,
@@ -252,7 +257,17 @@ BEAGLE_DLLEXPORT int beagleCalculateRootLogLikelihoods(int instance, const int* 
                                                        double* outSumLogLikelihood);
 /* reference src/mbbeagle.c:1262-1274 (unrooted trees: integrate across the root branch).
  * Returns BEAGLE_ERROR_FLOATING_POINT when the sum is NaN or infinite -- the signal MrBayes'
- * dynamic-rescaling state machine reacts to (src/mbbeagle.c:471-535).  Derivative arguments must be NULL. */
+ * dynamic-rescaling state machine reacts to (src/mbbeagle.c:471-535).
+ *
+ * Branch-length derivatives (upstream BEAGLE's semantics; MrBayes passes NULL throughout): with count == 1,
+ * firstDerivativeIndices / secondDerivativeIndices name the matrix buffers holding P' and P'' of the branch
+ * (beagleUpdateTransitionMatrices).  Per pattern c, with L_c = sum_k w_k sum_i pi_i parent[k,c,i] sum_j P_k[i,j] child[k,c,j]
+ * and D1_c, D2_c the same sums with P' and P'':  d1_c = D1_c / L_c,  d2_c = D2_c / L_c - d1_c^2, and
+ *     *outSumFirstDerivative = sum_c weight_c d1_c,   *outSumSecondDerivative = sum_c weight_c d2_c
+ * are the first and second derivative of the log-likelihood in the branch length; *outSumLogLikelihood is as without
+ * derivatives.  The first derivative alone (second index and output NULL) is allowed; a second derivative without a
+ * first, or an index array without its output pointer (or the reverse), is BEAGLE_ERROR_OUT_OF_RANGE; count > 1 with
+ * derivatives is BEAGLE_ERROR_NO_IMPLEMENTATION (one subset at a time, as upstream).  A derivative call is synchronous. */
 BEAGLE_DLLEXPORT int beagleCalculateEdgeLogLikelihoods(int instance, const int* parentBufferIndices,
                                                        const int* childBufferIndices,
                                                        const int* probabilityIndices,
@@ -266,6 +281,9 @@ BEAGLE_DLLEXPORT int beagleCalculateEdgeLogLikelihoods(int instance, const int* 
                                                        double* outSumSecondDerivative);
 /* reference src/mbbeagle.c:1295,1309,1329: per-pattern log-likelihoods of the last Calculate call */
 BEAGLE_DLLEXPORT int beagleGetSiteLogLikelihoods(int instance, double* outLogLikelihoods);
+/* patternCount unweighted d1_c / d2_c of the last Calculate call, if it computed derivatives (BEAGLE_ERROR_GENERAL
+ * otherwise); either pointer may be NULL */
+BEAGLE_DLLEXPORT int beagleGetSiteDerivatives(int instance, double* outFirstDerivatives, double* outSecondDerivatives);
 
 /* ---------------------------------------------------------------------------------------------
  * engine extensions (not part of the upstream API; used by bench.py / the multi-GPU driver)
@@ -290,7 +308,7 @@ BEAGLE_DLLEXPORT int beagleSetCPUThreadCount(int instance, int threadCount);
 BEAGLE_DLLEXPORT int beagleSetPatternPartitions(int instance, int partitionCount, const int* inPatternPartitions);
 /* reference src/mbbeagle.c:2055 */
 BEAGLE_DLLEXPORT int beagleSetCategoryRatesWithIndex(int instance, int categoryRatesIndex, const double* inCategoryRates);
-/* reference src/mbbeagle.c:2140-2147 */
+/* reference src/mbbeagle.c:2140-2147; derivative index lists as for beagleUpdateTransitionMatrices */
 BEAGLE_DLLEXPORT int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* eigenIndices,
                                                                       const int* categoryRateIndices,
                                                                       const int* probabilityIndices,
@@ -314,6 +332,8 @@ BEAGLE_DLLEXPORT int beagleCalculateRootLogLikelihoodsByPartition(int instance, 
                                                                   const int* partitionIndices, int partitionCount, int count,
                                                                   double* outSumLogLikelihoodByPartition,
                                                                   double* outSumLogLikelihood);
+/* derivative arguments as for beagleCalculateEdgeLogLikelihoods, per named partition (count == 1): the ...ByPartition
+ * outputs get one value per partition, the plain outputs the totals */
 BEAGLE_DLLEXPORT int beagleCalculateEdgeLogLikelihoodsByPartition(
     int instance, const int* parentBufferIndices, const int* childBufferIndices, const int* probabilityIndices,
     const int* firstDerivativeIndices, const int* secondDerivativeIndices, const int* categoryWeightsIndices,

@@ -62,7 +62,7 @@ EXPORTS = [
     "beagleSetTransitionMatrix", "beagleGetTransitionMatrix", "beagleUpdatePartials", "beagleWaitForPartials",
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
-    "beagleGetSiteLogLikelihoods", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -88,6 +88,15 @@ def _d(a) -> np.ndarray:
 
 def _i(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _opt_i(a) -> Optional[np.ndarray]:
+    return None if a is None else _i(a)
+
+
+def _ptr(a: Optional[np.ndarray]):
+    """the int pointer of an optional index array (None: NULL)"""
+    return None if a is None else a.ctypes.data_as(_ip)
 
 
 class BeagleLibrary:
@@ -134,6 +143,7 @@ class BeagleLibrary:
         L.beagleCalculateEdgeLogLikelihoods.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.c_int,
                                                         _dp, _dp, _dp]
         L.beagleGetSiteLogLikelihoods.argtypes = [C.c_int, _dp]
+        L.beagleGetSiteDerivatives.argtypes = [C.c_int, _dp, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetStepTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
@@ -270,9 +280,11 @@ class BeagleInstance:
         self._chk(self.lib.beagleSetPatternWeights(self.id, a.ctypes.data_as(_dp)), "beagleSetPatternWeights")
 
     # ---- matrices -------------------------------------------------------------------------------
-    def update_transition_matrices(self, eigen_index, prob_indices, edge_lengths):
+    def update_transition_matrices(self, eigen_index, prob_indices, edge_lengths, first=None, second=None):
+        """first / second: matrix buffers that take dP/dt and d2P/dt2 of the same branches (either may be None)."""
         p, e = _i(prob_indices), _d(edge_lengths)
-        self._chk(self.lib.beagleUpdateTransitionMatrices(self.id, eigen_index, p.ctypes.data_as(_ip), None, None,
+        d1, d2 = _opt_i(first), _opt_i(second)
+        self._chk(self.lib.beagleUpdateTransitionMatrices(self.id, eigen_index, p.ctypes.data_as(_ip), _ptr(d1), _ptr(d2),
                                                           e.ctypes.data_as(_dp), len(p)),
                   "beagleUpdateTransitionMatrices")
 
@@ -344,6 +356,27 @@ class BeagleInstance:
         self._chk(rc, "beagleCalculateEdgeLogLikelihoods", allow=(BEAGLE_ERROR_FLOATING_POINT,))
         return rc, out.value
 
+    def calculate_edge_derivatives(self, parents, children, probs, first, second, weights, freqs, cums):
+        """The edge log-likelihood with its first and second derivative in the branch length (`first` / `second`: the matrix
+        buffers holding dP/dt and d2P/dt2; second=None: first derivative only).  Returns (rc, lnL, d1, d2); d2 is None without
+        `second`.  Error codes other than BEAGLE_ERROR_FLOATING_POINT raise."""
+        p, ch, pr, w, f, c = _i(parents), _i(children), _i(probs), _i(weights), _i(freqs), _i(cums)
+        d1, d2 = _opt_i(first), _opt_i(second)
+        out, o1, o2 = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        rc = self.lib.beagleCalculateEdgeLogLikelihoods(self.id, p.ctypes.data_as(_ip), ch.ctypes.data_as(_ip),
+                                                        pr.ctypes.data_as(_ip), _ptr(d1), _ptr(d2), w.ctypes.data_as(_ip),
+                                                        f.ctypes.data_as(_ip), c.ctypes.data_as(_ip), len(p),
+                                                        C.byref(out), C.byref(o1) if d1 is not None else None,
+                                                        C.byref(o2) if d2 is not None else None)
+        self._chk(rc, "beagleCalculateEdgeLogLikelihoods", allow=(BEAGLE_ERROR_FLOATING_POINT,))
+        return rc, out.value, (o1.value if d1 is not None else None), (o2.value if d2 is not None else None)
+
+    def get_site_derivatives(self):
+        """(d1, d2): the unweighted per-pattern derivatives of the last derivative call."""
+        a, b = np.empty(self.pattern_count), np.empty(self.pattern_count)
+        self._chk(self.lib.beagleGetSiteDerivatives(self.id, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp)), "beagleGetSiteDerivatives")
+        return a, b
+
     # ---- BEAGLE v3: multi-partition instances (reference src/mbbeagle.c:1500-3010) -------------------------------
     def child_count(self) -> int:
         return int(self.lib.mbamdGetChildCount(self.id))
@@ -356,10 +389,12 @@ class BeagleInstance:
         a = _d(rates)
         self._chk(self.lib.beagleSetCategoryRatesWithIndex(self.id, index, a.ctypes.data_as(_dp)), "beagleSetCategoryRatesWithIndex")
 
-    def update_transition_matrices_with_multiple_models(self, eigen_indices, rate_indices, prob_indices, edge_lengths):
+    def update_transition_matrices_with_multiple_models(self, eigen_indices, rate_indices, prob_indices, edge_lengths,
+                                                        first=None, second=None):
         g, r, p, e = _i(eigen_indices), _i(rate_indices), _i(prob_indices), _d(edge_lengths)
+        d1, d2 = _opt_i(first), _opt_i(second)
         self._chk(self.lib.beagleUpdateTransitionMatricesWithMultipleModels(
-            self.id, g.ctypes.data_as(_ip), r.ctypes.data_as(_ip), p.ctypes.data_as(_ip), None, None, e.ctypes.data_as(_dp), len(p)),
+            self.id, g.ctypes.data_as(_ip), r.ctypes.data_as(_ip), p.ctypes.data_as(_ip), _ptr(d1), _ptr(d2), e.ctypes.data_as(_dp), len(p)),
             "beagleUpdateTransitionMatricesWithMultipleModels")
 
     def update_partials_by_partition(self, operations):
@@ -392,6 +427,22 @@ class BeagleInstance:
             C.byref(out), None, None, None, None)
         self._chk(rc, "beagleCalculateEdgeLogLikelihoodsByPartition", allow=(BEAGLE_ERROR_FLOATING_POINT,))
         return rc, by, out.value
+
+    def calculate_edge_derivatives_by_partition(self, parents, children, probs, first, second, weights, freqs, cums, partitions):
+        """index arrays laid out [1][len(partitions)]; returns (rc, lnL, d1, d2), each a pair (per-partition sums, total);
+        d2 is None without `second`"""
+        p, ch, pr, w, f, c, pt = _i(parents), _i(children), _i(probs), _i(weights), _i(freqs), _i(cums), _i(partitions)
+        d1, d2 = _opt_i(first), _opt_i(second)
+        by = [np.zeros(len(pt)) for _ in range(3)]
+        tot = [C.c_double(0.0) for _ in range(3)]
+        rc = self.lib.beagleCalculateEdgeLogLikelihoodsByPartition(
+            self.id, p.ctypes.data_as(_ip), ch.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), _ptr(d1), _ptr(d2), w.ctypes.data_as(_ip),
+            f.ctypes.data_as(_ip), c.ctypes.data_as(_ip), pt.ctypes.data_as(_ip), len(pt), 1, by[0].ctypes.data_as(_dp), C.byref(tot[0]),
+            by[1].ctypes.data_as(_dp) if d1 is not None else None, C.byref(tot[1]) if d1 is not None else None,
+            by[2].ctypes.data_as(_dp) if d2 is not None else None, C.byref(tot[2]) if d2 is not None else None)
+        self._chk(rc, "beagleCalculateEdgeLogLikelihoodsByPartition", allow=(BEAGLE_ERROR_FLOATING_POINT,))
+        return (rc, (by[0], tot[0].value), (by[1], tot[1].value) if d1 is not None else None,
+                (by[2], tot[2].value) if d2 is not None else None)
 
     def calculate_root_log_likelihoods_by_partition(self, buffers, weights, freqs, cums, partitions, count):
         b, w, f, c, pt = _i(buffers), _i(weights), _i(freqs), _i(cums), _i(partitions)

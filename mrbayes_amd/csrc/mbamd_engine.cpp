@@ -251,6 +251,60 @@ static int integrate_any(Handle* h, const int* parent, const int* child, const i
     return result;
 }
 
+// A log-likelihood call over one edge with branch-length derivatives (mbamd_derivatives.h; BEAGLE's semantics, beagle.h).  Index
+// arrays are [partitionCount] (count == 1); each named partition's sums go to the ...By outputs, the totals to the plain ones.  The
+// call is synchronous on every engine it reaches: queued matrix jobs, deferred lists and a held path run first (edgeDerivatives).
+static int edge_derivatives(Handle* h, const char* who, const int* parent, const int* child, const int* prob, const int* d1, const int* d2,
+                            const int* wIdx, const int* fIdx, const int* cumIdx, const int* partitionIndices, int partitionCount, int count,
+                            double* lnlBy, double* lnlSum, double* d1By, double* d1Sum, double* d2By, double* d2Sum)
+{
+    const bool out1 = d1By || d1Sum, out2 = d2By || d2Sum;
+    if (d2 && !d1) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a second derivative without a first");
+    if ((d1 != nullptr) != out1 || (d2 != nullptr) != out2)
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a derivative index array and its output go together");
+    if (count != 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "derivatives are served for one subset at a time (count == 1)");
+    if (!parent || !child || !prob || !wIdx || !fIdx) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    const int pc = partitionIndices ? partitionCount : 1;
+    if (pc < 1) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "partition count");
+    std::vector<double> sums((size_t) pc * 3, 0.0);
+    int result = BEAGLE_SUCCESS;
+    if (h->f64) {
+        result = h->f64->edgeDerivatives(parent, child, prob, d1, d2, wIdx, fIdx, cumIdx, partitionIndices, pc, sums.data());
+        if (result != BEAGLE_SUCCESS && result != BEAGLE_ERROR_FLOATING_POINT) return result;
+    } else {
+        bool any = false;
+        const int erc = each_engine(h, false, [&](Instance* c, const Handle::Span& ch) -> int {
+            int dpos = 0;
+            if (partitionIndices) {
+                dpos = -1;
+                for (int d = 0; d < pc; ++d) if (partitionIndices[d] == ch.partition) dpos = d;
+                if (dpos < 0) return BEAGLE_SUCCESS;   // this partition is not part of the call
+            }
+            double s3[3] = {0.0, 0.0, 0.0};
+            const int rc = c->edgeDerivatives(parent[dpos], child[dpos], prob[dpos], d1[dpos], d2 ? d2[dpos] : -1, wIdx[dpos], fIdx[dpos],
+                                              cumIdx ? cumIdx[dpos] : BEAGLE_OP_NONE, s3);
+            if (rc == BEAGLE_ERROR_FLOATING_POINT) result = rc;
+            else if (rc) return rc;
+            for (int q = 0; q < 3; ++q) sums[(size_t) dpos * 3 + q] += s3[q];      // (the shards of a partition, in pattern order)
+            any = true;
+            return BEAGLE_SUCCESS;
+        });
+        if (erc) return erc;
+        if (!any) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "no such partition");
+    }
+    double total[3] = {0.0, 0.0, 0.0};
+    double* const by[3] = {lnlBy, d1By, d2By};
+    double* const all[3] = {lnlSum, d1Sum, d2Sum};
+    for (int q = 0; q < 3; ++q) {
+        for (int d = 0; d < pc; ++d) {
+            total[q] += sums[(size_t) d * 3 + q];
+            if (by[q]) by[q][d] = sums[(size_t) d * 3 + q];
+        }
+        if (all[q]) *all[q] = total[q];
+    }
+    return result;
+}
+
 extern "C" {
 
 const char* beagleGetVersion(void) { return "mbamd-0.2 (HIP/gfx950; BEAGLE API 3.x compatible subset)"; }
@@ -575,18 +629,16 @@ int beagleUpdateTransitionMatrices(int instance, int eigenIndex, const int* prob
 {
     StatTimer st_(ST_MATRICES);
     GET_INSTANCE_NOFLUSH(instance);
-    if (h->f64) return h->f64->updateMatrices(eigenIndex, 0, probabilityIndices, edgeLengths, count);
+    if (h->f64) return h->f64->updateMatrices(eigenIndex, 0, probabilityIndices, edgeLengths, count, firstDerivativeIndices, secondDerivativeIndices);
     API_TRACE("beagleUpdateTransitionMatrices(eigen=%d, count=%d, indices=%s..., lengths=%s...)", eigenIndex, count,
               trace_ints(probabilityIndices, std::min(6, count)).c_str(), trace_doubles(edgeLengths, std::min(6, count)).c_str());
-    if (firstDerivativeIndices || secondDerivativeIndices)
-        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatrices: derivatives");
     h->closeLog();
     return each_engine(h, false, [&](Instance* c, const Handle::Span&) {
         if (c->hasPending()) {                   // deferred lists read the matrices about to be replaced
             int frc_ = c->flushPending();
             if (frc_ != BEAGLE_SUCCESS) return in ? frc_ : (int) BEAGLE_ERROR_GENERAL;      // (a child's failed flush is reported as a general error)
         }
-        return c->updateMatrices(eigenIndex, probabilityIndices, edgeLengths, count);
+        return c->updateMatrices(eigenIndex, probabilityIndices, edgeLengths, count, 0, firstDerivativeIndices, secondDerivativeIndices);
     });
 }
 // v3 (reference src/mbbeagle.c:2140-2147): every matrix names its own eigen-system and category-rate vector
@@ -596,11 +648,9 @@ int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* ei
 {
     StatTimer st_(ST_MATRICES);
     GET_INSTANCE_NOFLUSH(instance);
-    if (h->f64) return (firstDerivativeIndices || secondDerivativeIndices) ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatricesWithMultipleModels: derivatives") : h->f64->updateMatricesMulti(eigenIndices, categoryRateIndices, probabilityIndices, edgeLengths, count);
+    if (h->f64) return h->f64->updateMatricesMulti(eigenIndices, categoryRateIndices, probabilityIndices, edgeLengths, count, firstDerivativeIndices, secondDerivativeIndices);
     API_TRACE("beagleUpdateTransitionMatricesWithMultipleModels(count=%d, eigen=%s..., rates=%s...)", count,
               trace_ints(eigenIndices, std::min(6, count)).c_str(), trace_ints(categoryRateIndices, std::min(6, count)).c_str());
-    if (firstDerivativeIndices || secondDerivativeIndices)
-        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdateTransitionMatricesWithMultipleModels: derivatives");
     h->closeLog();
     return each_engine(h, false, [&](Instance* c, const Handle::Span&) {
         if (c->hasPending()) { int frc = c->flushPending(); if (frc) return frc; }
@@ -608,7 +658,9 @@ int beagleUpdateTransitionMatricesWithMultipleModels(int instance, const int* ei
         while (i < count) {                      // runs of equal (eigen-system, rate vector)
             int j = i + 1;
             while (j < count && eigenIndices[j] == eigenIndices[i] && categoryRateIndices[j] == categoryRateIndices[i]) ++j;
-            const int rc = c->updateMatrices(eigenIndices[i], probabilityIndices + i, edgeLengths + i, j - i, categoryRateIndices[i]);
+            const int rc = c->updateMatrices(eigenIndices[i], probabilityIndices + i, edgeLengths + i, j - i, categoryRateIndices[i],
+                                             firstDerivativeIndices ? firstDerivativeIndices + i : nullptr,
+                                             secondDerivativeIndices ? secondDerivativeIndices + i : nullptr);
             if (rc) return rc;
             i = j;
         }
@@ -811,8 +863,16 @@ int beagleCalculateEdgeLogLikelihoods(int instance, const int* parentBufferIndic
 {
     StatTimer st_(ST_LNL);
     GET_INSTANCE_KEEPING_PATH(instance);
-    if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivative || outSumSecondDerivative)
-        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoods: derivatives");
+    if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivative || outSumSecondDerivative) {
+        h->closeLog();
+        const int drc_ = edge_derivatives(h, "beagleCalculateEdgeLogLikelihoods", parentBufferIndices, childBufferIndices, probabilityIndices,
+                                          firstDerivativeIndices, secondDerivativeIndices, categoryWeightsIndices, stateFrequenciesIndices,
+                                          cumulativeScaleIndices, nullptr, 1, count, nullptr, outSumLogLikelihood, nullptr, outSumFirstDerivative,
+                                          nullptr, outSumSecondDerivative);
+        API_TRACE("beagleCalculateEdgeLogLikelihoods(derivatives) -> %d, lnL %.6f, d1 %.6f", drc_, outSumLogLikelihood ? *outSumLogLikelihood : 0.0,
+                  outSumFirstDerivative ? *outSumFirstDerivative : 0.0);
+        return drc_;
+    }
     if (h->f64) return h->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices, cumulativeScaleIndices, count, outSumLogLikelihood);
     const int rc_ = integrate_any(h, parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices,
                                   stateFrequenciesIndices, cumulativeScaleIndices, count, nullptr, 1, nullptr, outSumLogLikelihood);
@@ -854,8 +914,16 @@ int beagleCalculateEdgeLogLikelihoodsByPartition(int instance, const int* parent
     StatTimer st_(ST_LNL);
     GET_INSTANCE(instance);
     if (firstDerivativeIndices || secondDerivativeIndices || outSumFirstDerivativeByPartition || outSumFirstDerivative ||
-        outSumSecondDerivativeByPartition || outSumSecondDerivative)
-        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeLogLikelihoodsByPartition: derivatives");
+        outSumSecondDerivativeByPartition || outSumSecondDerivative) {
+        if (!partitionIndices || partitionCount < 1) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeLogLikelihoodsByPartition: partition indices");
+        if (in && (partitionCount != 1 || partitionIndices[0] != 0))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeLogLikelihoodsByPartition: no partitions were set");
+        h->closeLog();
+        return edge_derivatives(h, "beagleCalculateEdgeLogLikelihoodsByPartition", parentBufferIndices, childBufferIndices, probabilityIndices,
+                                firstDerivativeIndices, secondDerivativeIndices, categoryWeightsIndices, stateFrequenciesIndices,
+                                cumulativeScaleIndices, partitionIndices, partitionCount, count, outSumLogLikelihoodByPartition, outSumLogLikelihood,
+                                outSumFirstDerivativeByPartition, outSumFirstDerivative, outSumSecondDerivativeByPartition, outSumSecondDerivative);
+    }
     if (h->f64)
         return h->f64->logLikelihoods(parentBufferIndices, childBufferIndices, probabilityIndices, categoryWeightsIndices, stateFrequenciesIndices,
                                        cumulativeScaleIndices, count, outSumLogLikelihood, partitionIndices, partitionCount, outSumLogLikelihoodByPartition);
@@ -877,6 +945,28 @@ int beagleGetSiteLogLikelihoods(int instance, double* outLogLikelihoods)
     if (h->f64) return h->f64->getSites(outLogLikelihoods);
     if (in) return in->getSites(outLogLikelihoods);                  // (an error before the first log-likelihood)
     EACH_ENGINE(true, c->hasSites() ? c->getSites(outLogLikelihoods + ch.start) : BEAGLE_SUCCESS);        // (children without a result are skipped)
+}
+// the unweighted per-pattern d lnL / dt and d2 lnL / dt2 of the last likelihood call, if that was a derivative call (either output may be NULL)
+int beagleGetSiteDerivatives(int instance, double* outFirstDerivatives, double* outSecondDerivatives)
+{
+    StatTimer st_(ST_SITE);
+    GET_INSTANCE(instance);
+    double* const out[3] = {nullptr, outFirstDerivatives, outSecondDerivatives};
+    if (h->f64) {
+        if (!h->f64->hasDerivatives()) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteDerivatives: the last likelihood call computed no derivatives");
+        for (int q = 1; q < 3; ++q) if (out[q]) std::memcpy(out[q], h->f64->siteDerivatives(q), (size_t) h->dim.patternCount * sizeof(double));
+        return BEAGLE_SUCCESS;
+    }
+    bool any = false;
+    const int rc = each_engine(h, false, [&](Instance* c, const Handle::Span& ch) -> int {
+        if (!c->hasDerivatives()) return BEAGLE_SUCCESS;                // (children without a result are skipped)
+        for (int q = 1; q < 3; ++q) if (out[q]) std::memcpy(out[q] + ch.start, c->siteDerivatives(q), (size_t) ch.count * sizeof(double));
+        any = true;
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    if (!any) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteDerivatives: the last likelihood call computed no derivatives");
+    return BEAGLE_SUCCESS;
 }
 
 // ---- engine extensions ---------------------------------------------------------------------

@@ -15,6 +15,7 @@
 #include "libhmsbeagle/mbamd_reports.h"
 #include "mbamd_walk4_host.h"
 #include "mbamd_kernels_mfma.h"
+#include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
 
 namespace mbamd {
 
@@ -122,7 +123,9 @@ struct Instance {
     int setEigen(int idx, const double* U, const double* Ui, const double* lam);
     int setRateMatrices(int first, int count, const double* q, const double* pi, int mode, int warmFirst = -1);
     int setRates(int index, const double* r);
-    int updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet = 0);
+    // d1Idx / d2Idx: the matrix buffers that take dP/dt and d2P/dt2 of the same branches (either may be null)
+    int updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet = 0,
+                       const int* d1Idx = nullptr, const int* d2Idx = nullptr);
     int setMatrix(int idx, const double* in);
     int getMatrix(int idx, double* out);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
@@ -142,6 +145,12 @@ struct Instance {
     int reduceResult(double* deviceOut, void* waitingStream);
     bool hasSites() const { return haveSite; }
     int getSites(double* out);
+    // Branch-length derivatives over one edge (mbamd_derivatives.h), synchronous: everything queued or held runs first.  prob / d1 / d2:
+    // the matrix buffers holding P, P' and P'' of the branch (d2 < 0: first derivative only); out3: the weighted sums of lnL, d1, d2.
+    // The per-pattern values stay with the engine: siteDerivatives(1 / 2), and getSites() returns this call's log-likelihoods.
+    int edgeDerivatives(int parent, int child, int prob, int d1, int d2, int wIdx, int fIdx, int cumIdx, double out3[3]);
+    bool hasDerivatives() const { return derivValid; }
+    const double* siteDerivatives(int order) const { return h_deriv + (size_t) order * Ppad; }
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -242,6 +251,10 @@ private:
     double* h_site_dev = nullptr;
     bool siteToHost = false, siteOnHost = false;   // mode / where the latest evaluation put its values
     int nblocks = 0;                  // partial sums of the weighted site log-likelihoods (one per integration workgroup)
+    // a derivative call's results, pinned host memory the kernel writes: [3][Ppad] per-pattern lnL / d1 / d2, then [3][Ppad / 64] block sums
+    double* h_deriv = nullptr;
+    double* h_deriv_dev = nullptr;
+    bool derivValid = false;          // the last likelihood call was a derivative call: its site values are the instance's
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
     bool haveSite = false;
@@ -440,6 +453,7 @@ private:
     int planTable(Plan& plan, const void* table, size_t bytes);
     int timedRun(const Plan& plan, int32_t* cum);
     int flushMatrices();
+    template <int ORDER> int launchMatrices(const MatrixJob* jobs, int count);
     std::vector<MatrixJob> pendingJobs;          // queued beagleUpdateTransitionMatrices work
     std::vector<char> pendingMatrixOut;          // matrix buffers the queued jobs write
     int submit(Plan* plan, int cumIdx, int32_t* cumPtr);
@@ -649,6 +663,7 @@ inline Instance::~Instance()
     if (h_sums) (void) hipHostFree(h_sums);
     wait.destroy();
     if (h_site) (void) hipHostFree(h_site);
+    if (h_deriv) (void) hipHostFree(h_deriv);
     stage.destroy();
     for (auto& ev : events) { (void) hipEventDestroy(ev.first); (void) hipEventDestroy(ev.second); }
     for (auto& ev : spans) { (void) hipEventDestroy(ev.first); (void) hipEventDestroy(ev.second); }
@@ -918,7 +933,8 @@ inline int Instance::setEigen(int idx, const double* U, const double* Ui, const 
 // src/mbbeagle.c:1475-1486), and all parts of an evaluation go out as ONE launch when the next other call arrives.
 inline int Instance::setRates(int index, const double* r) { return rateSets.set(index, r, K); }
 
-inline int Instance::updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet)
+inline int Instance::updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet,
+                                    const int* d1Idx, const int* d2Idx)
 {
     if (!rateSets.has(rateSet)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: category rates index");
     if (!pendingJobs.empty() && rateSet != pendingRateSet) {       // one rate set per launch
@@ -929,25 +945,42 @@ inline int Instance::updateMatrices(int eigenIndex, const int* probIdx, const do
     if (eigenIndex < 0 || eigenIndex >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: eigen index");
     if (count <= 0) return BEAGLE_SUCCESS;
     if (K > MBAMD_MAX_RATES) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "more than 16 rate categories");
-    for (int i = 0; i < count; ++i)
-        if (probIdx[i] < 0 || probIdx[i] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: matrix index");
+    // the outputs of the call: probabilities, then the first / second derivative matrices where asked for (order 1 / 2 jobs)
+    const int* const outIdx[3] = {probIdx, d1Idx, d2Idx};
+    for (int o = 0; o < 3; ++o)
+        for (int i = 0; outIdx[o] && i < count; ++i)
+            if (outIdx[o][i] < 0 || outIdx[o][i] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: matrix index");
     if (pendingMatrixOut.size() != (size_t) nMatrices) pendingMatrixOut.assign(nMatrices, 0);
+    if (d1Idx || d2Idx) {                        // a derivative matrix on top of another output of the same call
+        std::vector<char> seen((size_t) nMatrices, 0);
+        for (int o = 0; o < 3; ++o)
+            for (int i = 0; outIdx[o] && i < count; ++i) {
+                if (o > 0 && seen[outIdx[o][i]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: a derivative index equals another output of the call");
+                seen[outIdx[o][i]] = 1;
+            }
+    }
     bool clash = false;
-    for (int i = 0; i < count && !clash; ++i) clash = pendingMatrixOut[probIdx[i]] != 0;
-    if (clash || (pendingJobs.size() + count) * sizeof(MatrixJob) > stage.capacity() / 4) {
+    size_t njobs = 0;
+    for (int o = 0; o < 3; ++o) {
+        if (!outIdx[o]) continue;
+        njobs += (size_t) count;
+        for (int i = 0; i < count && !clash; ++i) clash = pendingMatrixOut[outIdx[o][i]] != 0;
+    }
+    if (clash || (pendingJobs.size() + njobs) * sizeof(MatrixJob) > stage.capacity() / 4) {
         int rc = flushMatrices();
         if (rc) return rc;
     }
     const double* eig = d_eigen + (size_t) eigenIndex * eigenDoubles;
-    for (int i = 0; i < count; ++i) {
-        MatrixJob j;
-        j.out = matrixPtr(probIdx[i]);
-        j.length = lengths[i];
-        j.eig = eig;
-        j.pad_ = 0.0;
-        pendingJobs.push_back(j);
-        pendingMatrixOut[probIdx[i]] = 1;
-    }
+    for (int o = 0; o < 3; ++o)
+        for (int i = 0; outIdx[o] && i < count; ++i) {
+            MatrixJob j;
+            j.out = matrixPtr(outIdx[o][i]);
+            j.length = lengths[i];
+            j.eig = eig;
+            j.pad_ = (double) o;                 // the derivative order: flushMatrices launches per order
+            pendingJobs.push_back(j);
+            pendingMatrixOut[outIdx[o][i]] = 1;
+        }
     // four states (one call per evaluation): the matrix kernel is launched here, so that it runs while MrBayes assembles the
     // operation list (+2 % on both chains, profiles/r06_scale_read.txt)
     if (s4) return flushMatrices();
@@ -957,28 +990,49 @@ inline int Instance::updateMatrices(int eigenIndex, const int* probIdx, const do
 inline int Instance::flushMatrices()
 {
     if (pendingJobs.empty()) return BEAGLE_SUCCESS;
-    const RatesArg rates = rateSets[pendingRateSet];
-    const int count = (int) pendingJobs.size();
     { int src = spanBegin(); if (src) return src; }
+    // one launch per derivative order (MatrixJob::pad_ holds a job's order: 0 -- all there is on MrBayes' path -- 1 or 2)
+    bool derivatives = false;
+    for (const MatrixJob& j : pendingJobs) derivatives = derivatives || j.pad_ != 0.0;
+    int rc = BEAGLE_SUCCESS;
+    if (!derivatives) {
+        rc = launchMatrices<0>(pendingJobs.data(), (int) pendingJobs.size());
+    } else {
+        std::vector<MatrixJob> byOrder[3];
+        for (MatrixJob j : pendingJobs) {
+            const int order = j.pad_ == 1.0 ? 1 : (j.pad_ == 2.0 ? 2 : 0);
+            j.pad_ = 0.0;
+            byOrder[order].push_back(j);
+        }
+        if (!byOrder[0].empty()) rc = launchMatrices<0>(byOrder[0].data(), (int) byOrder[0].size());
+        if (rc == BEAGLE_SUCCESS && !byOrder[1].empty()) rc = launchMatrices<1>(byOrder[1].data(), (int) byOrder[1].size());
+        if (rc == BEAGLE_SUCCESS && !byOrder[2].empty()) rc = launchMatrices<2>(byOrder[2].data(), (int) byOrder[2].size());
+    }
+    pendingJobs.clear();
+    std::fill(pendingMatrixOut.begin(), pendingMatrixOut.end(), 0);
+    return rc;
+}
+
+// the transition-matrix launch of `count` jobs of one derivative ORDER (0: the probabilities), whichever kernel the layout takes
+template <int ORDER>
+inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
+{
+    const RatesArg rates = rateSets[pendingRateSet];
     if (s4 && count <= MBAMD_S4_INLINE_JOBS && count * K <= 64) {
         // a branch move's one or two matrices: the jobs in the kernel arguments (mbamd_kernels.h)
         MatrixJobs4 ja;
         std::memset(&ja, 0, sizeof ja);
-        std::memcpy(ja.j, pendingJobs.data(), sizeof(MatrixJob) * count);
-        pendingJobs.clear();
-        std::fill(pendingMatrixOut.begin(), pendingMatrixOut.end(), 0);
-        MBAMD_LAUNCH(k_transition_matrices_s4_inline, 1u, 64, 0, stream, ja, rates, K, count * K);
+        std::memcpy(ja.j, jobs, sizeof(MatrixJob) * count);
+        MBAMD_LAUNCH(k_transition_matrices_s4_inline<ORDER>, 1u, 64, 0, stream, ja, rates, K, count * K);
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
     }
     const MatrixJob* djobs = nullptr;
-    int rc = stageDirect(pendingJobs.data(), sizeof(MatrixJob) * count, (const void**) &djobs);
-    pendingJobs.clear();
-    std::fill(pendingMatrixOut.begin(), pendingMatrixOut.end(), 0);
+    int rc = stageDirect(jobs, sizeof(MatrixJob) * count, (const void**) &djobs);
     if (rc) return rc;
     if (s4) {
         const int total = count * K;
-        MBAMD_LAUNCH(k_transition_matrices_s4, (unsigned) ((total + 255) / 256), 256, 0, stream, djobs, rates, K, total);
+        MBAMD_LAUNCH(k_transition_matrices_s4<ORDER>, (unsigned) ((total + 255) / 256), 256, 0, stream, djobs, rates, K, total);
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
     }
@@ -986,11 +1040,15 @@ inline int Instance::flushMatrices()
         const unsigned grid = (unsigned) (count * K);
         const int packedT = mfma ? T : 0;
         const size_t wgTab = wg ? wgTabFloats : 0;
+        auto k1 = k_transition_matrices_mfma<1, ORDER>;
+        auto k2 = k_transition_matrices_mfma<2, ORDER>;
+        auto k3 = k_transition_matrices_mfma<3, ORDER>;
+        auto k4 = k_transition_matrices_mfma<4, ORDER>;
         switch ((S + 15) / 16) {
-            case 1: MBAMD_LAUNCH_BARRIER(k_transition_matrices_mfma<1>, grid, 64, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
-            case 2: MBAMD_LAUNCH_BARRIER(k_transition_matrices_mfma<2>, grid, 128, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
-            case 3: MBAMD_LAUNCH_BARRIER(k_transition_matrices_mfma<3>, grid, 192, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
-            default: MBAMD_LAUNCH_BARRIER(k_transition_matrices_mfma<4>, grid, 256, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
+            case 1: MBAMD_LAUNCH_BARRIER(k1, grid, 64, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
+            case 2: MBAMD_LAUNCH_BARRIER(k2, grid, 128, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
+            case 3: MBAMD_LAUNCH_BARRIER(k3, grid, 192, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
+            default: MBAMD_LAUNCH_BARRIER(k4, grid, 256, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
         }
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
@@ -1001,10 +1059,10 @@ inline int Instance::flushMatrices()
         const size_t nev = (size_t) count * K * S;
         rc = grow((void**) &d_ev, &evCap, nev * sizeof(double));
         if (rc) return rc;
-        MBAMD_LAUNCH(k_eigen_exponentials, (unsigned) ((nev + 255) / 256), 256, 0, stream, djobs, rates, S, K, (int) nev, d_ev);
+        MBAMD_LAUNCH(k_eigen_exponentials<ORDER>, (unsigned) ((nev + 255) / 256), 256, 0, stream, djobs, rates, S, K, (int) nev, d_ev);
         evs = d_ev;
     }
-    MBAMD_LAUNCH_BARRIER(k_transition_matrices_ev, (unsigned) (count * K), threads, 0, stream, djobs, evs, rates, S, SP, K, 1,
+    MBAMD_LAUNCH_BARRIER(k_transition_matrices_ev<ORDER>, (unsigned) (count * K), threads, 0, stream, djobs, evs, rates, S, SP, K, 1,
                          mfma ? T : 0, wg ? wgTabFloats : (size_t) 0);
     HIP_TRY(hipGetLastError());
     return BEAGLE_SUCCESS;
@@ -2709,6 +2767,7 @@ inline int Instance::integrate(const int* parent, const int* child, const int* p
     if (rc) return rc;
     postResultFlag();
     haveSite = true;
+    derivValid = false;
     pendingResult = true;
     if (deferred || launchOnly) {
         if (out) *out = 0.0;
@@ -2837,6 +2896,66 @@ inline int Instance::integrate4(const int* parent, const int* child, const int* 
     return BEAGLE_SUCCESS;
 }
 
+// Branch-length derivatives over one edge: one launch of k_edge_derivatives on this engine's partials layout, then a wait.  Never the
+// fused path-and-likelihood launch: a held path runs first, like every queued list and matrix job.
+inline int Instance::edgeDerivatives(int parent, int child, int prob, int d1, int d2, int wIdx, int fIdx, int cumIdx, double out3[3])
+{
+    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
+    int rc = checkIntegrate(&parent, &child, &prob, &wIdx, &fIdx, &cumIdx, 1);
+    if (rc) return rc;
+    if (d1 < 0 || d1 >= nMatrices || d2 >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge derivatives: derivative matrix index");
+    const int nb = Ppad / 64;
+    if (!h_deriv) {
+        HIP_TRY(hipHostMalloc(&h_deriv, (size_t) 3 * (Ppad + nb) * sizeof(double), hipHostMallocDefault));
+        HIP_TRY(hipHostGetDevicePointer((void**) &h_deriv_dev, h_deriv, 0));
+    }
+    DerivArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.parent = partials[parent];
+    a.child_tip = tipStates[child] ? 1 : 0;
+    a.child = tipStates[child] ? (const void*) tipStates[child] : (const void*) partials[child];
+    a.matrix[0] = matrixPtr(prob);
+    a.matrix[1] = matrixPtr(d1);
+    a.matrix[2] = d2 >= 0 ? matrixPtr(d2) : nullptr;
+    a.weights = d_weights + (size_t) wIdx * K;
+    a.freqs = d_freqs + (size_t) fIdx * S;
+    if (cumIdx != BEAGLE_OP_NONE) {
+        if (arena()) {
+            if (scaleState[cumIdx] != 0) {
+                rc = ensureWide(cumIdx);
+                if (rc) return rc;
+                a.cum = wideScale[cumIdx];
+            }
+        } else {
+            rc = ensureScale(cumIdx);
+            if (rc) return rc;
+            a.cum = scale[cumIdx];
+        }
+    }
+    a.pattern_weights = d_pweights;
+    a.site = h_deriv_dev;
+    a.sums = h_deriv_dev + (size_t) 3 * Ppad;
+    a.pstride = s4 ? (size_t) geom.pstride : (size_t) (wgTileBytes / 4);
+    a.tstride = s4 ? geom.tstride : wgTipTileBytes;
+    a.S = S; a.SP = SP; a.K = K; a.Ppad = Ppad;
+    a.first = 0; a.last = P;
+    a.sumStride = nb;
+    auto kernel = s4 ? k_edge_derivatives<DERIV_S4, float> : wg ? k_edge_derivatives<DERIV_WG, float> : k_edge_derivatives<DERIV_LEVELS, float>;
+    MBAMD_LAUNCH(kernel, (unsigned) nb, 64, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    syncedClock = launchClock;
+    for (int q = 0; q < 3; ++q) {
+        double s = 0.0;
+        for (int b = 0; b < nb; ++b) s += h_deriv[(size_t) 3 * Ppad + (size_t) q * nb + b];
+        out3[q] = s;
+    }
+    haveSite = true;
+    derivValid = true;
+    if (!(out3[0] == out3[0]) || out3[0] > 1.79e308 || out3[0] < -1.79e308) return BEAGLE_ERROR_FLOATING_POINT;
+    return BEAGLE_SUCCESS;
+}
+
 // the stream writes the sequence number of this integration behind its kernel: what fetchResult polls
 inline void Instance::postResultFlag()
 {
@@ -2948,6 +3067,10 @@ inline const char* Instance::implName() const
 inline int Instance::getSites(double* out)
 {
     if (!haveSite) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteLogLikelihoods: no likelihood computed yet");
+    if (derivValid) {                            // (a derivative call is synchronous: its values are in place)
+        std::memcpy(out, h_deriv, (size_t) P * sizeof(double));
+        return BEAGLE_SUCCESS;
+    }
     // (a result that was fetched -- the stream's flag behind the integration kernel was seen, or the stream synchronised -- has its
     //  site values in place: no second wait; a runtime synchronisation of an idle stream still costs ~25 us)
     if (!(siteOnHost && siteSeq != 0 && seenSeq == siteSeq && !pendingResult)) HIP_TRY(hipStreamSynchronize(stream));

@@ -18,6 +18,7 @@
 #include "mbamd_host.h"          // fail / HIP_TRY, StatTimer, Switches, Dims; PinnedRing, HostMirror, grow_*, RateSets
 #include "mbamd_kernels.h"       // the device primitives, RatesArg, MBAMD_MAX_SUBSETS
 #include "mbamd_walk4_host.h"    // Walk4Builder: the program compiler of the four-state walk
+#include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
 
 namespace mbamd {
 
@@ -1028,8 +1029,10 @@ struct MatrixJob64 {
     double* out;                 // [K][S][S] then transposed [K][S][SPAD]
     double length;
     const double* eig;           // [U | U^-1 | lambda]
-    double pad_;
+    double pad_;                 // host side: the derivative order of the job (0, 1, 2), one launch per order
 };
+// (ORDER: 0 = the probabilities, 1 / 2 = their first / second derivative in the branch length -- deriv_exponential, mbamd_kernels.h)
+template <int ORDER>
 __global__ void __launch_bounds__(256)
 k64_exponentials(const MatrixJob64* __restrict__ jobs, RatesArg rates, int S, int K, int total, double* __restrict__ ev)
 {
@@ -1037,9 +1040,15 @@ k64_exponentials(const MatrixJob64* __restrict__ jobs, RatesArg rates, int S, in
     if (g >= total) return;
     const int s = g % S, bk = g / S;
     const int b = bk / K, k = bk % K;
-    ev[g] = exp(jobs[b].eig[(size_t) 2 * S * S + s] * jobs[b].length * rates.r[k]);
+    ev[g] = deriv_exponential<ORDER>(exp(jobs[b].eig[(size_t) 2 * S * S + s] * jobs[b].length * rates.r[k]), jobs[b].eig[(size_t) 2 * S * S + s], rates.r[k]);
 }
 // TiProbs_Gen (reference src/likelihood.c:9498-9545): P_k = U diag(exp(lambda t r_k)) U^-1, negatives clamped to zero
+template <int ORDER> __device__ __forceinline__ double matrix_entry64(double sum)
+{
+    if constexpr (ORDER == 0) return sum < 0.0 ? 0.0 : sum;
+    return sum;
+}
+template <int ORDER>
 __global__ void __launch_bounds__(256)
 k64_matrices(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev, int S, int SPAD, int K)
 {
@@ -1053,14 +1062,14 @@ k64_matrices(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev
         const int i = idx / S, j = idx % S;
         double sum = 0.0;
         for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
-        const double v = sum < 0.0 ? 0.0 : sum;
+        const double v = matrix_entry64<ORDER>(sum);
         M[(size_t) i * S + j] = v;
         MT[(size_t) j * SPAD + i] = v;
     }
 }
 
 // the same product on the fp64 matrix cores for 16 <= S <= 64 (one wave per 16 rows, as k_transition_matrices_mfma of the fp32 engine)
-template <int NJ>
+template <int NJ, int ORDER>
 __global__ void __launch_bounds__(64 * NJ)
 k64_matrices_mfma(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev, int S, int SPAD, int K)
 {
@@ -1100,7 +1109,7 @@ k64_matrices_mfma(const MatrixJob64* __restrict__ jobs, const double* __restrict
         for (int r = 0; r < 4; ++r) {
             const int row = 16 * wave + ls + 4 * r, j = 16 * jt + li;
             if (row < S && j < S) {
-                const double v = acc[jt][r] < 0.0 ? 0.0 : acc[jt][r];
+                const double v = matrix_entry64<ORDER>(acc[jt][r]);
                 M[(size_t) row * S + j] = v;
                 MT[(size_t) j * SPAD + row] = v;
             }
@@ -1330,7 +1339,7 @@ public:
         if (!live) return;
         (void) hipSetDevice(device);
         (void) hipStreamSynchronize(stream);
-        void* all[] = {d_partials, d_states, d_matrices, d_eigen, d_freqs, d_weights, d_pweights, d_scale, d_site, d_sums, d_ev, d_stage};
+        void* all[] = {d_partials, d_states, d_matrices, d_eigen, d_freqs, d_weights, d_pweights, d_scale, d_site, d_sums, d_ev, d_stage, d_deriv};
         for (void* p : all)
             if (p) (void) hipFree(p);
         if (d_ring) (void) hipFree(d_ring);
@@ -1467,19 +1476,23 @@ public:
         std::memcpy(h.data(), w, (size_t) P * sizeof(double));
         return upload(d_pweights, h.data(), (size_t) Ppad * sizeof(double));
     }
-    void launchMatrices(const MatrixJob64* dj, int count)
+    template <int ORDER> void launchMatrices(const MatrixJob64* dj, int count)
     {
         if (S >= 16 && S <= 64) {
             const unsigned grid = (unsigned) (count * K);
+            auto k1 = k64_matrices_mfma<1, ORDER>;
+            auto k2 = k64_matrices_mfma<2, ORDER>;
+            auto k3 = k64_matrices_mfma<3, ORDER>;
+            auto k4 = k64_matrices_mfma<4, ORDER>;
             switch ((S + 15) / 16) {
-                case 1: MBAMD_LAUNCH_BARRIER(k64_matrices_mfma<1>, grid, 64, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-                case 2: MBAMD_LAUNCH_BARRIER(k64_matrices_mfma<2>, grid, 128, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-                case 3: MBAMD_LAUNCH_BARRIER(k64_matrices_mfma<3>, grid, 192, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-                default: MBAMD_LAUNCH_BARRIER(k64_matrices_mfma<4>, grid, 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+                case 1: MBAMD_LAUNCH_BARRIER(k1, grid, 64, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+                case 2: MBAMD_LAUNCH_BARRIER(k2, grid, 128, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+                case 3: MBAMD_LAUNCH_BARRIER(k3, grid, 192, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+                default: MBAMD_LAUNCH_BARRIER(k4, grid, 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
             }
             return;
         }
-        MBAMD_LAUNCH(k64_matrices, (unsigned) (count * K), 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K);
+        MBAMD_LAUNCH(k64_matrices<ORDER>, (unsigned) (count * K), 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K);
     }
     // Matrix updates are queued like operation lists: MrBayes updates a codon model's eigen parts one call each (src/mbbeagle.c:1475-1486),
     // and three launches of 200 matrices fill the chip worse than one of 600.  Every other entry point flushes (flushQueue); a second
@@ -1487,12 +1500,10 @@ public:
     std::vector<MatrixJob64> matQueue;
     std::vector<char> matQueued;               // per matrix buffer: an update is in the queue
     int matQueueRate = -1;
-    int flushMatrices()
+    // the exponentials and the matrices of `jobs`, all of one derivative ORDER (the launches share d_ev: stream order keeps them apart)
+    template <int ORDER> int runMatrices(const std::vector<MatrixJob64>& jobs)
     {
-        if (matQueue.empty()) return BEAGLE_SUCCESS;
-        std::vector<MatrixJob64> jobs;
-        jobs.swap(matQueue);
-        std::fill(matQueued.begin(), matQueued.end(), 0);
+        if (jobs.empty()) return BEAGLE_SUCCESS;
         const int count = (int) jobs.size();
         void* dj = nullptr;
         int rc = stage(jobs.data(), jobs.size() * sizeof(MatrixJob64), &dj);
@@ -1501,38 +1512,74 @@ public:
         rc = grow_device(stream, (void**) &d_ev, &evCap, need, need * 2);
         if (rc) return rc;
         const int total = count * K * S;
-        MBAMD_LAUNCH(k64_exponentials, (unsigned) ((total + 255) / 256), 256, 0, stream, (const MatrixJob64*) dj, rateSets[matQueueRate], S, K, total, d_ev);
-        launchMatrices((const MatrixJob64*) dj, count);
+        MBAMD_LAUNCH(k64_exponentials<ORDER>, (unsigned) ((total + 255) / 256), 256, 0, stream, (const MatrixJob64*) dj, rateSets[matQueueRate], S, K, total, d_ev);
+        launchMatrices<ORDER>((const MatrixJob64*) dj, count);
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
     }
-    int updateMatrices(int eigenIdx, int rateIdx, const int* prob, const double* lengths, int count)
+    int flushMatrices()
+    {
+        if (matQueue.empty()) return BEAGLE_SUCCESS;
+        std::vector<MatrixJob64> jobs;
+        jobs.swap(matQueue);
+        std::fill(matQueued.begin(), matQueued.end(), 0);
+        bool derivatives = false;
+        for (const MatrixJob64& j : jobs) derivatives = derivatives || j.pad_ != 0.0;
+        if (!derivatives) return runMatrices<0>(jobs);
+        std::vector<MatrixJob64> byOrder[3];       // one launch per derivative order (MatrixJob64::pad_)
+        for (MatrixJob64 j : jobs) {
+            const int order = j.pad_ == 1.0 ? 1 : (j.pad_ == 2.0 ? 2 : 0);
+            j.pad_ = 0.0;
+            byOrder[order].push_back(j);
+        }
+        int rc = runMatrices<0>(byOrder[0]);
+        if (rc == BEAGLE_SUCCESS) rc = runMatrices<1>(byOrder[1]);
+        if (rc == BEAGLE_SUCCESS) rc = runMatrices<2>(byOrder[2]);
+        return rc;
+    }
+    // d1 / d2: the matrix buffers that take the first / second derivative of the same branches (either may be null)
+    int updateMatrices(int eigenIdx, int rateIdx, const int* prob, const double* lengths, int count, const int* d1 = nullptr, const int* d2 = nullptr)
     {
         if (!queue.empty()) { const int rcq = flushQueue(); if (rcq) return rcq; }        // (queued operations read the matrices as they are now)
         if (count <= 0) return BEAGLE_SUCCESS;
         if (eigenIdx < 0 || eigenIdx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: eigen index");
         if (!rateSets.has(rateIdx)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: rate index");
-        for (int i = 0; i < count; ++i)
-            if (prob[i] < 0 || prob[i] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: matrix index");
-        if (!matQueue.empty() && (matQueueRate != rateIdx || matQueue.size() + (size_t) count > 60000)) { const int rc = flushMatrices(); if (rc) return rc; }
+        const int* const outIdx[3] = {prob, d1, d2};
+        std::vector<char> seen;
+        if (d1 || d2) seen.assign((size_t) nMatrices, 0);
+        size_t njobs = 0;
+        for (int o = 0; o < 3; ++o)
+            for (int i = 0; outIdx[o] && i < count; ++i) {
+                const int m = outIdx[o][i];
+                if (m < 0 || m >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: matrix index");
+                if (!seen.empty()) {
+                    if (o > 0 && seen[(size_t) m]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdateTransitionMatrices: a derivative index equals another output of the call");
+                    seen[(size_t) m] = 1;
+                }
+                ++njobs;
+            }
+        if (!matQueue.empty() && (matQueueRate != rateIdx || matQueue.size() + njobs > 60000)) { const int rc = flushMatrices(); if (rc) return rc; }
         if (matQueued.size() != (size_t) nMatrices) matQueued.assign((size_t) nMatrices, 0);
         matQueueRate = rateIdx;
-        for (int i = 0; i < count; ++i) {
-            if (matQueued[(size_t) prob[i]]) { const int rc = flushMatrices(); if (rc) return rc; }
-            matQueued[(size_t) prob[i]] = 1;
-            matQueue.push_back({matrixPtr(prob[i]), lengths[i], d_eigen + (size_t) eigenIdx * eigDoubles, 0.0});
-        }
+        for (int o = 0; o < 3; ++o)
+            for (int i = 0; outIdx[o] && i < count; ++i) {
+                const int m = outIdx[o][i];
+                if (matQueued[(size_t) m]) { const int rc = flushMatrices(); if (rc) return rc; }
+                matQueued[(size_t) m] = 1;
+                matQueue.push_back({matrixPtr(m), lengths[i], d_eigen + (size_t) eigenIdx * eigDoubles, (double) o});
+            }
         return sw.f64NoMatrixQueue ? flushMatrices() : BEAGLE_SUCCESS;
     }
     // v3: an eigen-system and a category-rate vector per matrix; one launch per run of equal rate vectors
-    int updateMatricesMulti(const int* eigenIdx, const int* rateIdx, const int* prob, const double* lengths, int count)
+    int updateMatricesMulti(const int* eigenIdx, const int* rateIdx, const int* prob, const double* lengths, int count,
+                            const int* d1 = nullptr, const int* d2 = nullptr)
     {
         { const int rcq = flushQueue(); if (rcq) return rcq; }
         int i = 0;
         while (i < count) {
             int j = i + 1;
             while (j < count && eigenIdx[j] == eigenIdx[i] && rateIdx[j] == rateIdx[i]) ++j;
-            const int rc = updateMatrices(eigenIdx[i], rateIdx[i], prob + i, lengths + i, j - i);
+            const int rc = updateMatrices(eigenIdx[i], rateIdx[i], prob + i, lengths + i, j - i, d1 ? d1 + i : nullptr, d2 ? d2 + i : nullptr);
             if (rc) return rc;
             i = j;
         }
@@ -2170,14 +2217,89 @@ public:
             total += s;
         }
         haveSite = true;
+        derivValid = false;
         if (out) *out = total;
         if (!(total == total) || total > 1.79e308 || total < -1.79e308) return BEAGLE_ERROR_FLOATING_POINT;
         return BEAGLE_SUCCESS;
     }
+    // Branch-length derivatives over one edge (mbamd_derivatives.h), per named partition: index arrays are [partitionCount]
+    // (`partitions` null: one entry, all patterns); d2 null: first derivative only.  sums: [partitionCount][3] weighted sums of
+    // lnL, d1, d2.  Synchronous; the per-pattern values are kept for getSites / siteDerivatives.
+    double* d_deriv = nullptr;             // [3][Ppad] per-pattern values, then [partitions of a call][3][Ppad / 64] block sums
+    size_t derivCap = 0;
+    std::vector<double> derivSite;         // host copy of the per-pattern values of the last derivative call
+    bool derivValid = false;
+    int edgeDerivatives(const int* parent, const int* child, const int* prob, const int* d1, const int* d2, const int* wIdx, const int* fIdx,
+                        const int* cumIdx, const int* partitions, int partitionCount, double* sums)
+    {
+        { const int rcq = flushQueue(); if (rcq) return rcq; }
+        const int pc = partitions ? partitionCount : 1;
+        const int nblocks = Ppad / 64;
+        const size_t nsite = (size_t) 3 * Ppad, nsums = (size_t) pc * 3 * nblocks;
+        { const int rc = grow_device(stream, (void**) &d_deriv, &derivCap, (nsite + nsums) * sizeof(double), (nsite + nsums) * sizeof(double)); if (rc) return rc; }
+        std::vector<int> blocksOf((size_t) pc, 0);
+        for (int d = 0; d < pc; ++d) {
+            int first = 0, last = P;
+            if (partitions) {
+                int rc = partitionRange(partitions[d], &first, &last, "edge derivatives by partition");
+                if (rc) return rc;
+                last = std::min(last, P);
+            }
+            if (parent[d] < 0 || parent[d] >= nBuffers || !valid[parent[d]] || isTip[parent[d]])
+                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge derivatives: parent buffer");
+            const int ci = child[d];
+            if (ci < 0 || ci >= nBuffers || !valid[ci] || prob[d] < 0 || prob[d] >= nMatrices || d1[d] < 0 || d1[d] >= nMatrices ||
+                (d2 && (d2[d] < 0 || d2[d] >= nMatrices)))
+                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge derivatives: child buffer / matrix");
+            if (wIdx[d] < 0 || wIdx[d] >= nEigen || fIdx[d] < 0 || fIdx[d] >= nEigen)
+                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge derivatives: weights / frequencies index");
+            if (cumIdx && cumIdx[d] != BEAGLE_OP_NONE && (cumIdx[d] < 0 || cumIdx[d] >= nScale))
+                return fail(BEAGLE_ERROR_OUT_OF_RANGE, "edge derivatives: cumulative scale index");
+            DerivArgs a;
+            std::memset(&a, 0, sizeof a);
+            a.parent = partialsPtr(parent[d]);
+            a.child = isTip[ci] ? (const void*) statesPtr(ci) : (const void*) partialsPtr(ci);
+            a.child_tip = isTip[ci] ? 1 : 0;
+            a.matrix[0] = matrixPtr(prob[d]);
+            a.matrix[1] = matrixPtr(d1[d]);
+            a.matrix[2] = d2 ? matrixPtr(d2[d]) : nullptr;
+            a.weights = d_weights + (size_t) wIdx[d] * K;
+            a.freqs = d_freqs + (size_t) fIdx[d] * S;
+            if (cumIdx && cumIdx[d] != BEAGLE_OP_NONE) a.cum = d_scale + (size_t) cumIdx[d] * Ppad;
+            a.pattern_weights = d_pweights;
+            a.site = d_deriv;
+            a.sums = d_deriv + nsite + (size_t) d * 3 * nblocks;
+            a.S = S; a.SP = S; a.K = K; a.Ppad = Ppad;
+            a.first = first; a.last = last;
+            a.sumStride = nblocks;
+            blocksOf[d] = (last + 63) / 64 - first / 64;
+            if (blocksOf[d] <= 0) continue;
+            auto kernel = k_edge_derivatives<DERIV_F64, double>;
+            MBAMD_LAUNCH(kernel, (unsigned) blocksOf[d], 64, 0, stream, a);
+        }
+        HIP_TRY(hipGetLastError());
+        derivSite.resize(nsite + nsums);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(derivSite.data(), d_deriv, (nsite + nsums) * sizeof(double), hipMemcpyDeviceToHost));
+        bool finite = true;
+        for (int d = 0; d < pc; ++d)
+            for (int q = 0; q < 3; ++q) {
+                double t = 0.0;
+                for (int i = 0; i < blocksOf[d]; ++i) t += derivSite[nsite + ((size_t) d * 3 + q) * nblocks + i];
+                sums[d * 3 + q] = t;
+                if (q == 0 && (!(t == t) || t > 1.79e308 || t < -1.79e308)) finite = false;
+            }
+        haveSite = true;
+        derivValid = true;
+        return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;
+    }
+    bool hasDerivatives() const { return derivValid; }
+    const double* siteDerivatives(int order) const { return derivSite.data() + (size_t) order * Ppad; }
     int getSites(double* out)
     {
         { const int rcq = flushQueue(); if (rcq) return rcq; }
         if (!haveSite) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteLogLikelihoods: no log-likelihood was calculated");
+        if (derivValid) { std::memcpy(out, derivSite.data(), (size_t) P * sizeof(double)); return BEAGLE_SUCCESS; }
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(out, d_site, (size_t) P * sizeof(double), hipMemcpyDeviceToHost));
         return BEAGLE_SUCCESS;

@@ -283,9 +283,26 @@ struct MatrixJob {
 #include "mbamd_rates.h"         // RatesArg: category rates travel as a kernel argument
 namespace mbamd {
 
+// Branch-length derivatives of the transition probabilities (mbamd_derivatives.h): the matrix kernels below take the ORDER of
+// the derivative as a template parameter.  ORDER 0 is P itself -- the expressions as they always were, negatives clamped to 0;
+// ORDER 1 / 2 multiply every exponential by (lambda_s r_k)^ORDER in fp64 (d/dt of exp(lambda r t)) and do not clamp: the entries
+// of P' and P'' are legitimately negative.  The host tags a job with its order in MatrixJob::pad_ and launches per order.
+template <int ORDER> __device__ __forceinline__ double deriv_exponential(double e, double lam, double r)
+{
+    if constexpr (ORDER == 0) return e;
+    const double lr = lam * r;
+    return ORDER == 1 ? e * lr : e * (lr * lr);
+}
+template <int ORDER> __device__ __forceinline__ float matrix_entry(double sum)
+{
+    if constexpr (ORDER == 0) return (sum < 0.0) ? 0.0f : (float) sum;
+    return (float) sum;
+}
+
 // exp(lambda*t) hoisted: one thread per (job, k, s) fills ev[(job*K+k)*S + s]; the matrix kernel
 // below then reads it (second launch on the same stream, so no barrier is needed).
 // `jobs` may live in pinned host memory (read once, directly over the host link).
+template <int ORDER>
 __global__ void __launch_bounds__(256)
 k_eigen_exponentials(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, int K, int total, double* __restrict__ ev)
 {
@@ -294,11 +311,12 @@ k_eigen_exponentials(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, 
     const int s = g % S, bk = g / S;
     const int b = bk / K, k = bk % K;
     const double* __restrict__ lam = jobs[b].eig + (size_t) 2 * S * S;
-    ev[g] = exp(lam[s] * jobs[b].length * rates.r[k]);
+    ev[g] = deriv_exponential<ORDER>(exp(lam[s] * jobs[b].length * rates.r[k]), lam[s], rates.r[k]);
 }
 
 // 4-state path: one thread per (branch, category) does the whole 4x4 matrix, exps included
 // (TiProbs_Gen for S = 4, src/likelihood.c:9498-9545); output transposed mT[j][i] = P(i->j).
+template <int ORDER>
 __global__ void __launch_bounds__(256)
 k_transition_matrices_s4(const MatrixJob* __restrict__ jobs, RatesArg rates, int K, int total)
 {
@@ -310,13 +328,13 @@ k_transition_matrices_s4(const MatrixJob* __restrict__ jobs, RatesArg rates, int
     const double* __restrict__ Ui = job.eig + 16;
     const double* __restrict__ lam = job.eig + 32;
     double e[4];
-    for (int s = 0; s < 4; ++s) e[s] = exp(lam[s] * job.length * rates.r[k]);
+    for (int s = 0; s < 4; ++s) e[s] = deriv_exponential<ORDER>(exp(lam[s] * job.length * rates.r[k]), lam[s], rates.r[k]);
     float* __restrict__ out = job.out + (size_t) k * 16;
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) {
             double sum = 0.0;
             for (int s = 0; s < 4; ++s) sum += U[i * 4 + s] * e[s] * Ui[s * 4 + j];
-            out[j * 4 + i] = (sum < 0.0) ? 0.0f : (float) sum;
+            out[j * 4 + i] = matrix_entry<ORDER>(sum);
         }
 }
 
@@ -342,6 +360,7 @@ k_copy_from_ring4(const unsigned* __restrict__ src, unsigned* __restrict__ dst, 
 // path kernel waits behind it in 86 % of a chain's generations).
 #define MBAMD_S4_INLINE_JOBS 8
 struct MatrixJobs4 { MatrixJob j[MBAMD_S4_INLINE_JOBS]; };
+template <int ORDER>
 __global__ void __launch_bounds__(64)
 k_transition_matrices_s4_inline(MatrixJobs4 jobs, RatesArg rates, int K, int total)
 {
@@ -353,19 +372,20 @@ k_transition_matrices_s4_inline(MatrixJobs4 jobs, RatesArg rates, int K, int tot
     const double* __restrict__ Ui = job.eig + 16;
     const double* __restrict__ lam = job.eig + 32;
     double e[4];
-    for (int s = 0; s < 4; ++s) e[s] = exp(lam[s] * job.length * rates.r[k]);
+    for (int s = 0; s < 4; ++s) e[s] = deriv_exponential<ORDER>(exp(lam[s] * job.length * rates.r[k]), lam[s], rates.r[k]);
     float* __restrict__ out = job.out + (size_t) k * 16;
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) {
             double sum = 0.0;
             for (int s = 0; s < 4; ++s) sum += U[i * 4 + s] * e[s] * Ui[s * 4 + j];
-            out[j * 4 + i] = (sum < 0.0) ? 0.0f : (float) sum;
+            out[j * 4 + i] = matrix_entry<ORDER>(sum);
         }
 }
 
 // packedT > 0: additionally write the MFMA A-operand copy behind the K transposed matrices:
 //   packed[((k*NT + i/32)*T + j/2)*64 + (i%32) + 32*(j%2)] = P_k(i->j),  NT = ceil(S/32), T = packedT = ceil(S/2)
 // wgTab > 0: additionally scatter into the tree-walk tables of category k, wgTab floats into the buffer (mbamd_walkg.h)
+template <int ORDER>
 __global__ void __launch_bounds__(256)
 k_transition_matrices_ev(const MatrixJob* __restrict__ jobs, const double* __restrict__ ev, RatesArg rates, int S, int SP, int K,
                          int transposed, int packedT, size_t wgTab)
@@ -378,7 +398,7 @@ k_transition_matrices_ev(const MatrixJob* __restrict__ jobs, const double* __res
     const double* __restrict__ Ui = jobs[b].eig + (size_t) S * S;
     if (ev == nullptr) {
         const double* __restrict__ lam = jobs[b].eig + (size_t) 2 * S * S;
-        if ((int) threadIdx.x < S) own[threadIdx.x] = exp(lam[threadIdx.x] * jobs[b].length * rates.r[k]);
+        if ((int) threadIdx.x < S) own[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * jobs[b].length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
         MBAMD_SYNC();
     }
     const double* __restrict__ e = ev ? ev + (size_t) blockIdx.x * S : own;
@@ -388,7 +408,7 @@ k_transition_matrices_ev(const MatrixJob* __restrict__ jobs, const double* __res
         const int i = idx / S, j = idx % S;
         double sum = 0.0;
         for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
-        const float v = (sum < 0.0) ? 0.0f : (float) sum;
+        const float v = matrix_entry<ORDER>(sum);
         if (transposed) out[(size_t) j * SP + i] = v;
         else            out[(size_t) i * SP + j] = v;
         if (packedT > 0) {

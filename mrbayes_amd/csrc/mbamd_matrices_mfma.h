@@ -9,7 +9,8 @@ namespace mbamd {
 
 // ---------------------------------------------------------------------------------------------
 // Transition matrices for larger state counts (TiProbs_Gen / TiProbs_GenCov, reference
-// src/likelihood.c:9424-9700): P_k = U diag(exp(lambda t r_k)) U^-1 in fp64, clamped at 0, stored as
+// src/likelihood.c:9424-9700): P_k = U diag(exp(lambda t r_k)) U^-1 in fp64, clamped at 0 (ORDER 1 / 2: its first / second
+// derivative in t, unclamped -- deriv_exponential, mbamd_kernels.h), stored as
 // fp32 transposed + in MFMA A-operand order.  The S x S x S contraction runs on the fp64 matrix cores
 // (v_mfma_f64_16x16x4_f64): one wave per 16 rows of P,
 //     A (16 x 4)  = U[i0 + (lane&15)][4 st + (lane>>4)] * exp(lambda_s t r_k)
@@ -19,7 +20,7 @@ namespace mbamd {
 // doubles, <= 64 KiB) is L2 resident.  grid = count * K workgroups of ceil(S/16) waves; NJ = ceil(S/16).
 // ---------------------------------------------------------------------------------------------
 
-template <int NJ>
+template <int NJ, int ORDER>
 __global__ void __launch_bounds__(64 * NJ, 3)     // (three workgroups per CU: at 61 states 141 + 32 registers allowed two, and the 594 workgroups of codon 100 x 5 000 ran in two rounds)
 k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, int SP, int K, int packedT, size_t wgTab)
 {
@@ -29,7 +30,7 @@ k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, i
     const MBAMD_AS_GLOBAL double* __restrict__ U = as_global(job.eig);
     const MBAMD_AS_GLOBAL double* __restrict__ Ui = U + (size_t) S * S;
     const MBAMD_AS_GLOBAL double* __restrict__ lam = U + (size_t) 2 * S * S;
-    if ((int) threadIdx.x < S) ev[threadIdx.x] = exp(lam[threadIdx.x] * job.length * rates.r[k]);
+    if ((int) threadIdx.x < S) ev[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * job.length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
     MBAMD_SYNC();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int li = lane & 15, ls = lane >> 4;
@@ -69,7 +70,7 @@ k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, i
             const int row = 16 * wave + ls + 4 * r, j = 16 * jt + li;
             if (row < S && j < S) {
                 const double sum = acc[jt][r];
-                const float v = (sum < 0.0) ? 0.0f : (float) sum;
+                const float v = matrix_entry<ORDER>(sum);
                 out[(size_t) j * SP + row] = v;
                 if (packedT > 0) packed[((size_t) (k * NT + row / 32) * packedT + j / 2) * 64 + (row % 32) + 32 * (j % 2)] = v;
                 if (wgTab > 0) wg_table_put(job.out + wgTab + (size_t) k * wg_table_floats(S), S, row, j, v);   // tree-walk tables (mbamd_walkg.h)
