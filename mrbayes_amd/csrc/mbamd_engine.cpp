@@ -432,8 +432,7 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         const Instance* first = h->first();
         returnInfo->resourceNumber = dev;
         returnInfo->resourceName = (dev < g_resources.length) ? g_resources.list[dev].name : const_cast<char*>("HIP device");
-        returnInfo->implName = const_cast<char*>(h->f64 ? (stateCount == 4 ? MBAMD_IMPL_NAME ": double-precision kernels (four states: tree walk)" : MBAMD_IMPL_NAME ": double-precision level kernels")
-                                                        : first->implName());
+        returnInfo->implName = const_cast<char*>(h->f64 ? h->f64->implName() : first->implName());
         returnInfo->implDescription = const_cast<char*>("hand-written HIP kernels for AMD CDNA4 (MI355X)");
         returnInfo->flags = h->flags;
     }
@@ -491,14 +490,7 @@ int beagleSetPatternPartitions(int instance, int partitionCount, const int* inPa
     if (partitionCount < 1 || !inPatternPartitions) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: arguments");
     if (!h->logOpen) return fail(BEAGLE_ERROR_GENERAL, "beagleSetPatternPartitions: call it before the first matrix / partials update");
     std::vector<std::pair<int, int>> ranges;
-    for (int c = 0; c < h->dim.patternCount; ++c) {
-        const int p = inPatternPartitions[c];
-        if (p < 0 || p >= partitionCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: partition index");
-        if ((int) ranges.size() == p) ranges.emplace_back(c, 1);
-        else if ((int) ranges.size() == p + 1 && ranges[p].first + ranges[p].second == c) ranges[p].second++;
-        else return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleSetPatternPartitions: partitions must be contiguous, increasing pattern ranges");
-    }
-    if ((int) ranges.size() != partitionCount) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: empty partition");
+    { const int rcr = pattern_partition_ranges(inPatternPartitions, h->dim.patternCount, partitionCount, ranges); if (rcr) return rcr; }
     h->partitionCount = partitionCount;
     if (partitionCount == 1 && in) return BEAGLE_SUCCESS;
     h->engine.reset();                            // hand the single-partition buffers back
@@ -985,16 +977,9 @@ int mbamdKernelTiming(int instance, int enable)
 int mbamdGetKernelTiming(int instance, double* outMilliseconds, long* outLaunches, int reset)
 {
     GET_INSTANCE(instance);
-    if (Engine64* e = h->f64.get()) {            // (no device timing on a double-precision instance: the partials launches are counted)
-        { const int rcq = e->flushQueue(); if (rcq) return rcq; }
-        if (outMilliseconds) *outMilliseconds = 0.0;
-        if (outLaunches) *outLaunches = (long) (e->walkLaunches + e->levelLaunches);
-        if (reset) e->walkLaunches = e->levelLaunches = 0;
-        return BEAGLE_SUCCESS;
-    }
     double ms = 0.0;
     long launches = 0;
-    const int rc = each_engine(h, false, [&](Instance* c, const Handle::Span&) {
+    const int rc = h->f64 ? h->f64->kernelTiming(&ms, &launches, reset) : each_engine(h, false, [&](Instance* c, const Handle::Span&) {
         double m = 0.0;
         const int trc = c->kernelTiming(&m, &launches, reset);
         ms = std::max(ms, m);
@@ -1054,7 +1039,7 @@ int mbamdWalkTrace(int instance, long long* out, int maxSteps, int* outSteps, in
 int mbamdGetChildCount(int instance)
 {
     GET_INSTANCE_NOFLUSH(instance);
-    if (h->f64) return std::max<int>(1, (int) h->f64->parts.size());
+    if (h->f64) return h->f64->childCount();
     return h->children.empty() ? 1 : (int) h->children.size();
 }
 int mbamdSetDeferredResult(int instance, int enable)

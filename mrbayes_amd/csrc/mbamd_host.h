@@ -8,6 +8,7 @@
 //   grow_device / grow_pinned   grow-on-demand of a scratch buffer                                    (all three)
 //   RateSets         category rates by index                                                          (Instance, Engine64)
 //   Dims             the dimensions an instance was created with                                      (Instance, Engine64)
+//   pattern_partition_ranges   the pattern -> partition map of beagleSetPatternPartitions as ranges   (the C ABI, Engine64)
 // Everything is `inline`: the state exists once however often the header is included.
 #pragma once
 
@@ -20,6 +21,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "libhmsbeagle/beagle.h"
@@ -103,6 +105,22 @@ struct Dims {
     int tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount, categoryCount,
         scaleBufferCount;
 };
+
+// v3 pattern partitions (beagleSetPatternPartitions): ids[c] = partition of pattern c.  Partitions must be contiguous, increasing
+// pattern ranges (MrBayes lists its divisions one after the other): -> (first pattern, pattern count) of each of the `count` partitions.
+inline int pattern_partition_ranges(const int* ids, int patterns, int count, std::vector<std::pair<int, int>>& ranges)
+{
+    ranges.clear();
+    for (int c = 0; c < patterns; ++c) {
+        const int p = ids[c];
+        if (p < 0 || p >= count) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: partition index");
+        if ((int) ranges.size() == p) ranges.emplace_back(c, 1);
+        else if ((int) ranges.size() == p + 1 && ranges[p].first + ranges[p].second == c) ranges[p].second++;
+        else return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleSetPatternPartitions: partitions must be contiguous, increasing pattern ranges");
+    }
+    if ((int) ranges.size() != count) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetPatternPartitions: empty partition");
+    return BEAGLE_SUCCESS;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Completion wait.  A result is waited for by polling pinned host memory: the runtime's wait on a stream costs ~25 us, a

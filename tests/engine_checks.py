@@ -1218,6 +1218,68 @@ def check_double_precision_general_paths(lib, golden_dir, case, monkeypatch):
         assert got[False][5] == 1 and got[True][5] >= 2, (got[False][5], got[True][5])
 
 
+GENERAL_CATEGORY_SHAPES = ((20, 4), (20, 5), (61, 2), (61, 3), (16, 8))      # (states, categories)
+
+
+def check_double_precision_general_categories(lib, monkeypatch, states, ncat, npat=70):
+    """16 ... 64 states in fp64 on both sides of ceil(S / 16) x K = 8: up to there a wave keeps all categories' tiles and rescales in
+    registers, beyond it a wave computes one category and k64_rescale follows.  8 taxa, 70 patterns (two 64-pattern blocks, the
+    second with 6 patterns), both scaling schemes.
+    (a) the default kernels give the bits of the plain one-wave kernels (every switch of F64_GENERAL_SWITCHES set): per-site
+        log-likelihoods and cumulative exponents, for a full evaluation and a partial update of the deepest tip's branch;
+    (b) against numpy float64 pruning (tests/pruning_reference.py): the sum within ABS_F64 + REL_F64 |ref|, and every site
+        |L / L_ref - 1| <= (2 ntaxa - 2) (S + 8) u kappa_max, u = 2^-53: every term of the pruning sums is non-negative, so to first
+        order the relative errors of the 2 ntaxa - 3 matrices and dot products add; (S + 8) u kappa is the bound on one matrix that
+        test_derivatives.py uses, kappa_max the largest kappa over the tree's branch lengths."""
+    from tests import pruning_reference as pr
+    div = pr.make_division(states, ncat, npat)
+    ref = pr.reference(states, ncat, npat)
+    t, S = div.tree, div.nstates
+    deep = max(range(t.ntaxa), key=lambda i: _depth(t, i))
+    nodes = [n for n in list(range(t.ntaxa)) + list(t.int_down_pass) if n != t.root] + [t.root_left]
+    kappa_max = max(pr.kappa(div, tl) for tl in sorted({pr.branch_length(t, n) for n in nodes}))
+    bound = (2 * t.ntaxa - 2) * (S + 8) * pr.U64 * kappa_max
+    ref_sum = float(np.dot(div.weights, np.log(ref["L"])))
+    for scaling in (lk.MB_BEAGLE_SCALE_ALWAYS, lk.MB_BEAGLE_SCALE_DYNAMIC):
+        got = {}
+        for plain in (False, True):
+            for name in F64_GENERAL_SWITCHES:
+                if plain:
+                    monkeypatch.setenv(name, "1")
+                else:
+                    monkeypatch.delenv(name, raising=False)
+            bd = lk.BeagleDivision(div, lib, scaling=scaling, double_precision=True)
+            try:
+                assert b"double-precision" in bd.inst.details.implName
+                lnl = bd.LogLike(0)
+                site = bd.inst.get_site_log_likelihoods().copy()
+                cum = bd.inst.get_scale_exponents(bd.siteScalerIndex[0]).copy()
+                bd.AcceptMove(0)
+                old = t.length[deep]
+                t.length[deep] = old * 1.7
+                try:
+                    bd.TouchBranch(0, deep)
+                    moved = bd.LogLike(0)
+                    site2 = bd.inst.get_site_log_likelihoods().copy()
+                    cum2 = bd.inst.get_scale_exponents(bd.siteScalerIndex[0]).copy()
+                finally:
+                    t.length[deep] = old
+                got[plain] = (lnl, site, cum, moved, site2, cum2)
+            finally:
+                bd.finalize()
+        for name in F64_GENERAL_SWITCHES:
+            monkeypatch.delenv(name, raising=False)
+        for a, b in zip(got[False], got[True]):
+            assert np.array_equal(a, b), (states, ncat, scaling)
+        lnl, site = got[False][0], got[False][1]
+        assert abs(got[False][3] - lnl) > 1e-9 * abs(lnl)                     # (the partial update changed something)
+        worst = float(np.abs(np.exp(site - np.log(ref["L"])) - 1.0).max())
+        print("%d states x %d x %d, scaling %d: lnL %.9f (reference %.9f), worst site error / bound %.3g (kappa_max %.1f)" %
+              (states, ncat, npat, scaling, lnl, ref_sum, worst / bound, kappa_max))
+        assert abs(lnl - ref_sum) <= ABS_F64 + REL_F64 * abs(ref_sum), (states, ncat, scaling, lnl, ref_sum)
+        assert worst <= bound, (states, ncat, scaling, worst, bound)
+
+
 def check_double_precision_walk_categories(lib, monkeypatch, ntips=24, npat=200, seed=11):
     """The fp64 four-state walk keeps a pattern's categories in the lanes of ONE wave (category count rounded up to a power of two,
     the surplus lanes repeating the last category): every category count 1 ... 8 must give the bits of the level kernels --

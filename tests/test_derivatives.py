@@ -17,19 +17,15 @@ u = 2^-24 (single precision); u = 2^-53 kappa on the double-precision engine, ka
 the matrices (computed below from the eigen-system).  The weighted sums get sum_c weight_c times the per-site bounds.
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 from mrbayes_amd import beagle as bg
 from mrbayes_amd import likelihood as lk
-from mrbayes_amd.division import synthetic_division
 from tests.hostemu import build_emu
+from tests.pruning_reference import NTAXA, U32, U64, branch_length, interior_edge, kappa, make_division, reference, spectral
 
-NTAXA = 8
-U32 = 2.0 ** -24
-U64 = 2.0 ** -53
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 
 
@@ -44,90 +40,6 @@ def gpu():
     if not lib.resources():
         pytest.fail("no HIP device visible: -m gpu tests need the MI355X")
     return lib
-
-
-# ---- cases ----------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def make_division(states, ncat, npat, seed=11, tree_seed=5):
-    kind = {4: "gtr", 20: "wag"}.get(states, "gen%d" % states)
-    div = synthetic_division(kind, NTAXA, npat, seed=seed, tree_seed=tree_seed, alpha=0.7, ncat=ncat, p_gap=0.05)
-    div.weights = 1.0 + (np.arange(npat) % 3).astype(np.float64)         # pattern weights that are not all one
-    return div
-
-
-def _length(t, node):
-    return min(max(t.length[node], lk.BRLENS_MIN), lk.BRLENS_MAX)
-
-
-def spectral(div, t, order):
-    """(matrices [K][S][S], sums of the absolute spectral terms [K][S][S]) of d^order P / dt^order at branch length t"""
-    es = div.eigen[0]
-    U, Ui, lam = np.asarray(es.evec, dtype=np.float64), np.asarray(es.ivec, dtype=np.float64), np.asarray(es.eval, dtype=np.float64)
-    mats, mags = [], []
-    for r in div.cat_rates:
-        e = (lam * r) ** order * np.exp(lam * r * t)
-        terms = U[:, :, None] * e[None, :, None] * Ui[None, :, :]       # [i][s][j]
-        mats.append(terms.sum(axis=1))
-        mags.append(np.abs(terms).sum(axis=1))
-    return np.stack(mats), np.stack(mags)
-
-
-def kappa(div, t):
-    """the cancellation inside the spectral sum: max over entries above 1e-6 of the largest of sum_s |terms| / |entry|"""
-    worst = 1.0
-    for order in (0, 1, 2):
-        m, mag = spectral(div, t, order)
-        for k in range(m.shape[0]):
-            keep = np.abs(m[k]) > 1e-6 * np.abs(m[k]).max()
-            worst = max(worst, float((mag[k][keep] / np.abs(m[k][keep])).max()))
-    return worst
-
-
-@functools.lru_cache(maxsize=None)
-def reference(states, ncat, npat, seed=11, tree_seed=5, interior=False):
-    """Pruning in float64 -> per-site L, D1, D2, A1, A2 over the root branch, whose child end is the root tip (interior: over
-    the branch below the top interior node instead, see interior_edge: both ends are interior partials)."""
-    div = make_division(states, ncat, npat, seed, tree_seed)
-    t, S, K, P = div.tree, div.nstates, div.ncat, div.npatterns
-    cl = {}
-    for tip in range(t.ntaxa):
-        st = np.asarray(div.tip_states[tip])
-        one = np.zeros((P, S))
-        ok = st < S
-        one[np.arange(P)[ok], st[ok]] = 1.0
-        one[~ok] = 1.0
-        cl[tip] = np.broadcast_to(one, (K, P, S))
-    for p in t.int_down_pass:
-        out = np.ones((K, P, S))
-        for c in (t.left[p], t.right[p]):
-            m, _ = spectral(div, _length(t, c), 0)
-            out = out * np.einsum("kij,kcj->kci", m, cl[c])
-        cl[p] = out
-    parent, child, tl = cl[t.root_left], cl[t.root], _length(t, t.root_left)
-    if interior:
-        v, u = interior_edge(t)
-        parent = np.einsum("kij,kcj->kci", spectral(div, _length(t, u), 0)[0], cl[u]) * np.einsum("kij,kcj->kci", spectral(div, tl, 0)[0], cl[t.root])
-        child, tl = cl[v], _length(t, v)
-    w = div.category_weights(0)
-    pi = np.asarray(div.pi, dtype=np.float64)
-    res = {"t": tl}
-    for order, name in ((0, "L"), (1, "D1"), (2, "D2")):
-        m, _ = spectral(div, tl, order)
-        res[name] = np.einsum("k,i,kci,kij,kcj->c", w, pi, parent, m, child)
-        res["A" + name] = np.einsum("k,i,kci,kij,kcj->c", w, pi, parent, np.abs(m), child)
-    L = res["L"]
-    res["d1"] = res["D1"] / L
-    res["d2"] = res["D2"] / L - res["d1"] ** 2
-    res["scale1"] = (res["AD1"] + np.abs(res["D1"])) / L
-    res["scale2"] = (res["AD2"] + np.abs(res["D2"])) / L + 2.0 * np.abs(res["d1"]) * res["scale1"]
-    return res
-
-
-def interior_edge(t):
-    """(v, u): an interior child v of the top interior node and its sibling u.  The branch above v has interior partials at both
-    ends once the top node's other two neighbours -- u and the root tip -- are combined into a buffer of their own."""
-    l, r = t.left[t.root_left], t.right[t.root_left]
-    return (l, r) if l >= t.ntaxa else (r, l)
 
 
 def expected_layout(states, ncat, double_precision):
@@ -293,7 +205,7 @@ def check_argument_errors(lib, double_precision=False):
         bd.LogLike(0)
         ix = edge_indices(bd)
         pcopy, m1, m2 = (bd.tiProbsScratchIndex[i] for i in (0, 1, 2))
-        tl = _length(div.tree, div.tree.root_left)
+        tl = branch_length(div.tree, div.tree.root_left)
         inst.update_transition_matrices(bd.cijkIndex[0], [pcopy], [tl], first=[m1], second=[m2])
         assert _raw_edge(inst, ix, [m1], [m2], True, True) == 0
         assert _raw_edge(inst, ix, [m1], None, True, False) == 0                                   # the first derivative alone
@@ -338,7 +250,7 @@ def _derivative_call(lib, div):
         bd.LogLike(0)
         ix = edge_indices(bd)
         pcopy, m1, m2 = (bd.tiProbsScratchIndex[i] for i in (0, 1, 2))
-        inst.update_transition_matrices(bd.cijkIndex[0], [pcopy], [_length(div.tree, div.tree.root_left)], first=[m1], second=[m2])
+        inst.update_transition_matrices(bd.cijkIndex[0], [pcopy], [branch_length(div.tree, div.tree.root_left)], first=[m1], second=[m2])
         rc, lnl, d1, d2 = inst.calculate_edge_derivatives(first=[m1], second=[m2], **ix)
         assert rc == 0
         return inst.child_count(), (lnl, d1, d2), (inst.get_site_log_likelihoods(),) + inst.get_site_derivatives()
@@ -406,7 +318,7 @@ def check_partitions(lib, double_precision=False):
                 if p == tr.root:
                     continue
                 eig_idx.append(d); rate_idx.append(d); prob_idx.append(d * nNodes + p)
-                lengths.append(_length(tr, p))
+                lengths.append(branch_length(tr, p))
             for p in tr.int_down_pass:
                 l, r = tr.left[p], tr.right[p]
                 ops.append([p, p - N, -1, l, d * nNodes + l, r, d * nNodes + r, d, nInt + d])
@@ -482,7 +394,7 @@ def check_held_path(lib):
     twin's that never saw a derivative call."""
     div = make_division.__wrapped__(4, 4, 130)             # (a division of its own: the branch lengths change; both engines read it)
     t = div.tree
-    ref_t = _length(t, t.root_left)
+    ref_t = branch_length(t, t.root_left)
     bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS)
     twin = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS)
     try:

@@ -391,6 +391,13 @@ def test_double_precision_walk_equals_levels(emu, golden_dir, case, monkeypatch)
     ec.check_double_precision_walk(emu, golden_dir, case, monkeypatch)
 
 
+@pytest.mark.parametrize("states,ncat", ec.GENERAL_CATEGORY_SHAPES)
+def test_double_precision_general_categories(emu, monkeypatch, states, ncat):
+    """fp64, 16 ... 64 states, fused and unfused rescale (ceil(S / 16) x K on both sides of 8): default kernels against the plain ones
+    bit for bit, and against numpy float64 pruning."""
+    ec.check_double_precision_general_categories(emu, monkeypatch, states, ncat)
+
+
 def test_double_precision_walk_category_counts(emu, monkeypatch):
     """fp64, four states: every category count 1 ... 8 on the walk (categories in the lanes of one wave) against the level kernels."""
     ec.check_double_precision_walk_categories(emu, monkeypatch)
