@@ -286,6 +286,52 @@ BEAGLE_DLLEXPORT int beagleGetSiteLogLikelihoods(int instance, double* outLogLik
 BEAGLE_DLLEXPORT int beagleGetSiteDerivatives(int instance, double* outFirstDerivatives, double* outSecondDerivatives);
 
 /* ---------------------------------------------------------------------------------------------
+ * the gradient in all branch lengths: pre-order partials (upstream BEAGLE 4's names and argument order;
+ * MrBayes calls none of them).  The order a client follows:
+ *   1. the log-likelihood (beagleUpdatePartials ..., beagleCalculate{Root,Edge}LogLikelihoods with count == 1);
+ *   2. beagleUpdatePrePartials with the pre-order list of the tree;
+ *   3. beagleCalculateEdgeDerivatives over any number of branches -- again after every branch-length change, from step 1.
+ * None of the three is served on a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).
+ * ------------------------------------------------------------------------------------------- */
+/* The top-down pass.  An operation computes pre(n), the conditional likelihoods of the REST of the tree at the child end
+ * of n's branch, from its parent's:
+ *     destinationPartials = pre(n)             child1Partials = pre(parent of n)     child1TransitionMatrix = P of n's branch
+ *     child2Partials = post-order partials, or compact tip states, of n's sibling    child2TransitionMatrix = the sibling's P
+ *     tmp[k,c,i]   = pre_parent[k,c,i] * sum_j P_sib,k[i,j] post_sib[k,c,j]
+ *     pre_n[k,c,j] = sum_i P_n,k[i,j] tmp[k,c,i]                                     (the transpose)
+ * so that sum_j pre_n[k,c,j] post_n[k,c,j] is category k's site likelihood at every node.  A missing tip state in the
+ * sibling is the factor 1.  child2Partials == BEAGLE_OP_NONE (the one extension) means there is no sibling factor: MrBayes'
+ * unrooted trees hang from a tip, so the top interior node's "parent" has a single child; the client supplies that parent's
+ * vector, pi_i * tip_root[c,i], with beagleSetPartials (on a rooted tree it supplies pi, as upstream clients do).
+ * Operations come in dependency order (top-down); operations that do not depend on one another run in one launch.
+ * Every destination column (pattern, category) is renormalised by its own power of two and the exponent is DISCARDED:
+ * pre-order buffers are always self-normalised, so destinationScaleWrite, destinationScaleRead and cumulativeScaleIndex must
+ * be BEAGLE_OP_NONE (BEAGLE_ERROR_NO_IMPLEMENTATION otherwise), and beagleGetPartials of such a buffer returns columns each
+ * scaled by an unspecified power of two.  A buffer stays a pre-order buffer until anything else writes it. */
+BEAGLE_DLLEXPORT int beagleUpdatePrePartials(int instance, const BeagleOperation* operations, int operationCount,
+                                             int cumulativeScaleIndex);
+/* beagleSetTransitionMatrix without paddedValue: nothing is clamped.  For the branch-length gradient the client passes
+ * D_k = r_k Q, [category][from][to], r_k the category rates; the P'_k that beagleUpdateTransitionMatrices makes at edge
+ * length zero is the same matrix. */
+BEAGLE_DLLEXPORT int beagleSetDifferentialMatrix(int instance, int matrixIndex, const double* inMatrix);
+/* For edge e = 0 .. count-1, between postBufferIndices[e] (post-order partials or compact tip states of node n) and
+ * preBufferIndices[e] (pre(n), written by beagleUpdatePrePartials and by nothing since: BEAGLE_ERROR_OUT_OF_RANGE
+ * otherwise), with D = derivativeMatrixIndices[e]:
+ *     g_k(c) = (sum_l pre[k,c,l] sum_j D_k[l,j] post[k,c,j]) / (sum_l pre[k,c,l] post[k,c,l])
+ *     d_c    = sum_k q_k(c) g_k(c)            the derivative of pattern c's log-likelihood in the branch length
+ *     outDerivatives[e * patternCount + c] = d_c (unweighted),   outSumDerivatives[e] = sum_c weight_c d_c,
+ *     outSumSquaredDerivatives[e] = sum_c weight_c d_c^2;   each of the three may be NULL.
+ * q_k(c) are the posterior category probabilities of pattern c.  They are the same for every branch and are computed, at the
+ * first call after a log-likelihood call, from the operands of that latest beagleCalculate{Root,Edge}LogLikelihoods call as
+ * they are then.  With more than one category: no such call yet is BEAGLE_ERROR_GENERAL, one with count > 1 is
+ * BEAGLE_ERROR_NO_IMPLEMENTATION, and categoryWeightsIndices[e] must be that call's weights index
+ * (BEAGLE_ERROR_OUT_OF_RANGE).  The call is synchronous. */
+BEAGLE_DLLEXPORT int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                                    const int* derivativeMatrixIndices, const int* categoryWeightsIndices,
+                                                    int count, double* outDerivatives, double* outSumDerivatives,
+                                                    double* outSumSquaredDerivatives);
+
+/* ---------------------------------------------------------------------------------------------
  * engine extensions (not part of the upstream API; used by bench.py / the multi-GPU driver)
  * ------------------------------------------------------------------------------------------- */
 /* Block until all queued device work of the instance has finished. */

@@ -62,7 +62,8 @@ EXPORTS = [
     "beagleSetTransitionMatrix", "beagleGetTransitionMatrix", "beagleUpdatePartials", "beagleWaitForPartials",
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
-    "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
+    "beagleCalculateEdgeDerivatives", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -144,6 +145,9 @@ class BeagleLibrary:
                                                         _dp, _dp, _dp]
         L.beagleGetSiteLogLikelihoods.argtypes = [C.c_int, _dp]
         L.beagleGetSiteDerivatives.argtypes = [C.c_int, _dp, _dp]
+        L.beagleUpdatePrePartials.argtypes = [C.c_int, C.POINTER(BeagleOperation), C.c_int, C.c_int]
+        L.beagleSetDifferentialMatrix.argtypes = [C.c_int, C.c_int, _dp]
+        L.beagleCalculateEdgeDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetStepTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
@@ -376,6 +380,31 @@ class BeagleInstance:
         a, b = np.empty(self.pattern_count), np.empty(self.pattern_count)
         self._chk(self.lib.beagleGetSiteDerivatives(self.id, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp)), "beagleGetSiteDerivatives")
         return a, b
+
+    # ---- the gradient in all branch lengths: pre-order partials ------------------------------------------------
+    def update_pre_partials(self, operations, cumulative_scale_index=BEAGLE_OP_NONE):
+        """operations: int array [n][7] in BeagleOperation field order, with the pre-order meaning of the fields
+        (pre(n), NONE, NONE, pre(parent), n's matrix, the sibling's post-order buffer or BEAGLE_OP_NONE, the sibling's matrix)."""
+        a = _i(operations).reshape(-1, 7)
+        self._chk(self.lib.beagleUpdatePrePartials(self.id, a.ctypes.data_as(C.POINTER(BeagleOperation)), a.shape[0],
+                                                   cumulative_scale_index), "beagleUpdatePrePartials")
+
+    def set_differential_matrix(self, idx, m):
+        a = _d(m)
+        self._chk(self.lib.beagleSetDifferentialMatrix(self.id, idx, a.ctypes.data_as(_dp)), "beagleSetDifferentialMatrix")
+
+    def calculate_edge_gradient(self, posts, pres, dmats, weights, sites=True):
+        """d lnL / dt over every listed branch in one call (beagleCalculateEdgeDerivatives).  Returns (rc, per-site derivatives
+        [count][patterns] or None without `sites`, sums [count], sums of squares [count]); an error code raises."""
+        po, pr, dm, w = _i(posts), _i(pres), _i(dmats), _i(weights)
+        n = len(po)
+        per = np.empty((n, self.pattern_count)) if sites else None
+        sums, sq = np.zeros(n), np.zeros(n)
+        rc = self.lib.beagleCalculateEdgeDerivatives(self.id, po.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), dm.ctypes.data_as(_ip),
+                                                     w.ctypes.data_as(_ip), n, per.ctypes.data_as(_dp) if sites else None,
+                                                     sums.ctypes.data_as(_dp), sq.ctypes.data_as(_dp))
+        self._chk(rc, "beagleCalculateEdgeDerivatives")
+        return rc, per, sums, sq
 
     # ---- BEAGLE v3: multi-partition instances (reference src/mbbeagle.c:1500-3010) -------------------------------
     def child_count(self) -> int:

@@ -62,6 +62,22 @@ __device__ __forceinline__ Real deriv_matrix(const void* m, const DerivArgs& a, 
     else return reinterpret_cast<const Real*>(m)[(size_t) k * a.SP * a.SP + (size_t) j * a.SP + i];
 }
 
+// the compact tip of pattern c: a mask of compatible states (four-state bitplanes) or a state code (>= S: missing)
+template <int LAYOUT>
+__device__ __forceinline__ unsigned deriv_tip(const void* states, const DerivArgs& a, int c)
+{
+    if constexpr (LAYOUT == DERIV_S4) {
+        const uint64_t* planes = reinterpret_cast<const uint64_t*>(states) + (size_t) (c >> 6) * a.tstride;
+        unsigned tip = 0;
+        for (int i = 0; i < 4; ++i) tip |= (unsigned) (planes[i] >> (c & 63) & 1u) << i;
+        return tip;
+    } else if constexpr (LAYOUT == DERIV_WG) {
+        return reinterpret_cast<const uint8_t*>(states)[(size_t) (c / MBAMD_WG_TW) * a.tstride + (c % MBAMD_WG_TW)];
+    } else {
+        return reinterpret_cast<const uint8_t*>(states)[c];
+    }
+}
+
 __device__ __forceinline__ float deriv_fma(float x, float y, float z) { return fmaf(x, y, z); }
 __device__ __forceinline__ double deriv_fma(double x, double y, double z) { return fma(x, y, z); }
 
@@ -84,18 +100,7 @@ k_edge_derivatives(DerivArgs a)
                 emax = a.cum[c];
             }
         }
-        // the compact tip of this pattern: a mask of compatible states (bitplanes) or a state code (>= S: missing)
-        unsigned tip = 0;
-        if (a.child_tip) {
-            if constexpr (LAYOUT == DERIV_S4) {
-                const uint64_t* planes = reinterpret_cast<const uint64_t*>(a.child) + (size_t) (c >> 6) * a.tstride;
-                for (int i = 0; i < 4; ++i) tip |= (unsigned) (planes[i] >> (c & 63) & 1u) << i;
-            } else if constexpr (LAYOUT == DERIV_WG) {
-                tip = reinterpret_cast<const uint8_t*>(a.child)[(size_t) (c / MBAMD_WG_TW) * a.tstride + (c % MBAMD_WG_TW)];
-            } else {
-                tip = reinterpret_cast<const uint8_t*>(a.child)[c];
-            }
-        }
+        const unsigned tip = a.child_tip ? deriv_tip<LAYOUT>(a.child, a, c) : 0u;
         double L = 0.0, D1 = 0.0, D2 = 0.0;
         for (int k = 0; k < K; ++k) {
             double cat0 = 0.0, cat1 = 0.0, cat2 = 0.0;

@@ -961,6 +961,56 @@ int beagleGetSiteDerivatives(int instance, double* outFirstDerivatives, double* 
     return BEAGLE_SUCCESS;
 }
 
+// ---- the pre-order pass and the gradient in all branch lengths (mbamd_preorder.h; semantics: beagle.h) -----------------------
+int beagleUpdatePrePartials(int instance, const BeagleOperation* operations, int operationCount, int cumulativeScaleIndex)
+{
+    StatTimer st_(ST_PARTIALS);
+    GET_INSTANCE(instance);
+    API_TRACE("beagleUpdatePrePartials(count=%d, cumulative=%d)", operationCount, cumulativeScaleIndex);
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: not on a multi-partition instance");
+    if (operationCount > 0 && !operations) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: null");
+    h->closeLog();
+    if (h->f64) return h->f64->updatePrePartials(operations, operationCount, cumulativeScaleIndex);
+    EACH_ENGINE(true, c->updatePrePartials(operations, operationCount, cumulativeScaleIndex));
+}
+int beagleSetDifferentialMatrix(int instance, int matrixIndex, const double* inMatrix)
+{
+    GET_INSTANCE(instance);
+    if (h->partitionCount > 1 || (h->f64 && h->f64->childCount() > 1))
+        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleSetDifferentialMatrix: not on a multi-partition instance");
+    if (!inMatrix) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetDifferentialMatrix: null");
+    if (h->f64) return h->f64->setMatrix(matrixIndex, inMatrix);
+    EACH_ENGINE(true, c->setMatrix(matrixIndex, inMatrix));
+}
+int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* derivativeMatrixIndices,
+                                   const int* categoryWeightsIndices, int count, double* outDerivatives, double* outSumDerivatives,
+                                   double* outSumSquaredDerivatives)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("beagleCalculateEdgeDerivatives(count=%d%s)", count, outDerivatives ? ", per site" : "");
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCalculateEdgeDerivatives: not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!postBufferIndices || !preBufferIndices || !derivativeMatrixIndices || !categoryWeightsIndices)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeDerivatives: null index array");
+    if (h->f64)
+        return h->f64->edgeGradient(postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices, count, outDerivatives,
+                                    outSumDerivatives, outSumSquaredDerivatives);
+    // pattern shards: the children's sums are added (in pattern order), their per-site values concatenated
+    const size_t n = (size_t) std::max(count, 0);
+    std::vector<double> sum(n, 0.0), sq(n, 0.0), part(n), partSq(n);
+    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
+        const int crc = c->edgeGradient(postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices, count,
+                                        outDerivatives ? outDerivatives + ch.start : nullptr, (size_t) h->dim.patternCount, part.data(), partSq.data());
+        if (crc) return crc;
+        for (size_t e = 0; e < n; ++e) { sum[e] += part[e]; sq[e] += partSq[e]; }
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    if (outSumDerivatives) std::copy(sum.begin(), sum.end(), outSumDerivatives);
+    if (outSumSquaredDerivatives) std::copy(sq.begin(), sq.end(), outSumSquaredDerivatives);
+    return BEAGLE_SUCCESS;
+}
+
 // ---- engine extensions ---------------------------------------------------------------------
 int mbamdSynchronize(int instance)
 {

@@ -16,6 +16,7 @@
 #include "mbamd_walk4_host.h"
 #include "mbamd_kernels_mfma.h"
 #include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
+#include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient: the pre-order pass and the gradient in all branch lengths
 
 namespace mbamd {
 
@@ -151,6 +152,12 @@ struct Instance {
     int edgeDerivatives(int parent, int child, int prob, int d1, int d2, int wIdx, int fIdx, int cumIdx, double out3[3]);
     bool hasDerivatives() const { return derivValid; }
     const double* siteDerivatives(int order) const { return h_deriv + (size_t) order * Ppad; }
+    // The pre-order pass and the gradient in all branch lengths (mbamd_preorder.h; semantics: beagle.h), both after everything queued
+    // or held.  updatePrePartials: one launch per group of mutually independent operations.  edgeGradient: synchronous; sums[e] and
+    // sumsSq[e] are this engine's weighted sums of edge e, sites (or null) takes d_c of edge e at sites[e * siteStride + c].
+    int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
+    int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
+                     double* sums, double* sumsSq);
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -255,6 +262,16 @@ private:
     double* h_deriv = nullptr;
     double* h_deriv_dev = nullptr;
     bool derivValid = false;          // the last likelihood call was a derivative call: its site values are the instance's
+    // ---- pre-order pass (mbamd_preorder.h) ----
+    std::vector<char> preOrder;       // per partials buffer: a pre-order operation wrote it and nothing else has since
+    void clearPreOrder(int idx) { if (idx >= 0 && idx < (int) preOrder.size()) preOrder[idx] = 0; }
+    LnlOperands lastLnl;              // the operands of the latest log-likelihood call: what q is made of
+    uint64_t qStamp = 0;              // lastLnl.stamp when d_q was computed
+    double* d_q = nullptr;            size_t qCap = 0;             // [K][Ppad] posterior category probabilities
+    void* d_preTable = nullptr;       size_t preTableCap = 0;      // the PreOp / GradEdge table of the call being served
+    int lnlOperands(DerivArgs& a, int parent, int child, int prob, int wIdx, int fIdx, int cumIdx);
+    DerivArgs layoutArgs() const;
+    int ensurePosteriors();
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
     bool haveSite = false;
@@ -658,7 +675,7 @@ inline Instance::~Instance()
     for (Plan* pl : plans) { if (pl->d_table) (void) hipFree(pl->d_table); delete pl; }
     plans.clear();
     void* bufs[] = {matrices, d_eigen, d_freqs, d_weights, d_rates, d_pweights, d_site,
-                    d_ev, d_tmp, d_trace};
+                    d_ev, d_tmp, d_trace, d_q, d_preTable};
     for (void* b : bufs) if (b) (void) hipFree(b);
     if (h_sums) (void) hipHostFree(h_sums);
     wait.destroy();
@@ -770,6 +787,7 @@ inline int Instance::setTipMasks(int tip, const std::vector<uint8_t>& h)
 inline int Instance::setTipStates(int tip, const int* states)
 {
     if (tip < 0 || tip >= nBuffers) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTipStates: tip index");
+    clearPreOrder(tip);
     std::vector<uint8_t> h(Ppad, (uint8_t) S);
     for (int c = 0; c < P; ++c) h[c] = (uint8_t) ((states[c] < 0 || states[c] >= S) ? S : states[c]);
     if (s4) {
@@ -791,6 +809,7 @@ inline int Instance::importPartials(int idx, const double* in, bool hasCategorie
 {
     if (idx < 0 || idx >= nBuffers) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "partials buffer index");
     if (idx < (int) finalExpOf.size()) finalExpOf[idx] = nullptr;
+    clearPreOrder(idx);
     if (s4 && !hasCategories) {
         // beagleSetTipPartials with 0/1 entries (IUPAC ambiguity codes, reference src/mbbeagle.c:150-166): a state mask
         // per pattern says the same thing in one byte, and the tree walk reads it like any compact tip
@@ -1173,6 +1192,8 @@ inline int Instance::updatePartials(const BeagleOperation* ops, int n, int cumId
     if (!finalExpOf.empty())                     // a buffer an operation overwrites no longer holds final partials
         for (int o = 0; o < n; ++o)
             if (ops[o].destinationPartials >= 0 && ops[o].destinationPartials < nBuffers) finalExpOf[ops[o].destinationPartials] = nullptr;
+    if (!preOrder.empty())                       // ... nor the rest-of-tree vector of a pre-order pass
+        for (int o = 0; o < n; ++o) clearPreOrder(ops[o].destinationPartials);
     if (s4) return updatePartials4(ops, n, cumIdx);
     if (wg) return updatePartialsG(ops, n, cumIdx);
     int32_t* cumPtr = nullptr;
@@ -2753,6 +2774,7 @@ inline int Instance::integrate(const int* parent, const int* child, const int* p
         if (heldPath) { int prc = runHeldPath(); if (prc) return prc; }
         return rc;
     }
+    lastLnl.remember(parent, child, prob, wIdx, fIdx, cumIdx, count);
     armSums(launchOnly);
     if (!arena()) {
         rc = integrateLevels(parent, child, prob, wIdx, fIdx, cumIdx, count);
@@ -2896,6 +2918,204 @@ inline int Instance::integrate4(const int* parent, const int* child, const int* 
     return BEAGLE_SUCCESS;
 }
 
+// the partials / matrix / tip layout of this engine, as the read-out kernels take it (patterns [0, P))
+inline DerivArgs Instance::layoutArgs() const
+{
+    DerivArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.pstride = s4 ? (size_t) geom.pstride : (size_t) (wgTileBytes / 4);
+    a.tstride = s4 ? geom.tstride : wgTipTileBytes;
+    a.S = S; a.SP = SP; a.K = K; a.Ppad = Ppad;
+    a.first = 0; a.last = P;
+    return a;
+}
+// ... with the (checked) operands of a log-likelihood call over one subset in device pointers; child < 0: a root call
+inline int Instance::lnlOperands(DerivArgs& a, int parent, int child, int prob, int wIdx, int fIdx, int cumIdx)
+{
+    a = layoutArgs();
+    a.parent = partials[parent];
+    if (child >= 0) {
+        a.child_tip = tipStates[child] ? 1 : 0;
+        a.child = tipStates[child] ? (const void*) tipStates[child] : (const void*) partials[child];
+        a.matrix[0] = matrixPtr(prob);
+    }
+    a.weights = d_weights + (size_t) wIdx * K;
+    a.freqs = d_freqs + (size_t) fIdx * S;
+    if (cumIdx != BEAGLE_OP_NONE) {
+        if (arena()) {
+            if (scaleState[cumIdx] != 0) {
+                const int rc = ensureWide(cumIdx);
+                if (rc) return rc;
+                a.cum = wideScale[cumIdx];
+            }
+        } else {
+            const int rc = ensureScale(cumIdx);
+            if (rc) return rc;
+            a.cum = scale[cumIdx];
+        }
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// beagleUpdatePrePartials: the list is checked as a whole, cut into launches (pre_order_groups) and run, one launch per group.
+inline int Instance::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx)
+{
+    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
+    if (n <= 0) return BEAGLE_SUCCESS;
+    if (cumIdx != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (cumulativeScaleIndex must be BEAGLE_OP_NONE)");
+    std::vector<char> written((size_t) nBuffers, 0);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        if (b.destinationScaleWrite != BEAGLE_OP_NONE || b.destinationScaleRead != BEAGLE_OP_NONE)
+            return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (scale indices must be BEAGLE_OP_NONE)");
+        const int d = b.destinationPartials, p = b.child1Partials, sib = b.child2Partials;
+        if (d < 0 || d >= nBuffers || p < 0 || p >= nBuffers || (sib != BEAGLE_OP_NONE && (sib < 0 || sib >= nBuffers)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: partials index");
+        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
+            (sib != BEAGLE_OP_NONE && (b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: matrix index");
+        if (tipStates[d]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination holds compact tip states");
+        if (tipStates[p] || (!valid[p] && !written[p])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the parent's pre-order buffer holds no partials");
+        if (sib != BEAGLE_OP_NONE && !tipStates[sib] && !valid[sib] && !written[sib])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the sibling's buffer was never written");
+        if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
+        written[d] = 1;
+    }
+    std::vector<PreOp> table((size_t) n);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        const int rc = ensurePartials(b.destinationPartials);
+        if (rc) return rc;
+        PreOp& t = table[(size_t) o];
+        std::memset(&t, 0, sizeof t);
+        t.dst = partials[b.destinationPartials];
+        t.parent = partials[b.child1Partials];
+        t.mOwn = matrixPtr(b.child1TransitionMatrix);
+        t.sibKind = -1;
+        if (b.child2Partials != BEAGLE_OP_NONE) {
+            const int sib = b.child2Partials;
+            t.sibKind = tipStates[sib] ? 1 : 0;
+            t.sib = tipStates[sib] ? (const void*) tipStates[sib] : (const void*) partials[sib];
+            t.mSib = matrixPtr(b.child2TransitionMatrix);
+        }
+    }
+    int rc = grow(&d_preTable, &preTableCap, table.size() * sizeof(PreOp));
+    if (rc) return rc;
+    rc = upload(d_preTable, table.data(), table.size() * sizeof(PreOp));
+    if (rc) return rc;
+    if (preOrder.size() != (size_t) nBuffers) preOrder.assign((size_t) nBuffers, 0);
+    std::vector<int> start;
+    pre_order_groups(ops, n, nBuffers, start);
+    PreArgs a;
+    a.g = layoutArgs();
+    for (size_t gI = 0; gI + 1 < start.size(); ++gI) {
+        a.ops = static_cast<const PreOp*>(d_preTable) + start[gI];
+        const int count = start[gI + 1] - start[gI];
+        if (s4) launch_pre_partials<DERIV_S4, float>(stream, a, count);
+        else if (wg) launch_pre_partials<DERIV_WG, float>(stream, a, count);
+        else launch_pre_partials<DERIV_LEVELS, float>(stream, a, count);
+        HIP_TRY(hipGetLastError());
+        pendingLaunches += 1;
+    }
+    for (int o = 0; o < n; ++o) {
+        const int d = ops[o].destinationPartials;
+        valid[d] = 1;
+        preOrder[d] = 1;
+        if (d < (int) finalExpOf.size()) finalExpOf[d] = nullptr;
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// q [K][Ppad] of the latest log-likelihood call's operands as they are now, unless d_q holds it already
+inline int Instance::ensurePosteriors()
+{
+    if (qStamp == lastLnl.stamp && d_q) return BEAGLE_SUCCESS;
+    int cum = lastLnl.cum;
+    int rc = checkIntegrate(&lastLnl.parent, lastLnl.child >= 0 ? &lastLnl.child : nullptr, &lastLnl.prob, &lastLnl.weights, &lastLnl.freqs, &cum, 1);
+    if (rc) return rc;
+    rc = grow((void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double));
+    if (rc) return rc;
+    DerivArgs a;
+    rc = lnlOperands(a, lastLnl.parent, lastLnl.child, lastLnl.prob, lastLnl.weights, lastLnl.freqs, lastLnl.cum);
+    if (rc) return rc;
+    a.site = d_q;
+    auto kernel = s4 ? k_category_posteriors<DERIV_S4, float> : wg ? k_category_posteriors<DERIV_WG, float> : k_category_posteriors<DERIV_LEVELS, float>;
+    MBAMD_LAUNCH(kernel, (unsigned) (Ppad / 64), 64, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    qStamp = lastLnl.stamp;
+    return BEAGLE_SUCCESS;
+}
+
+// beagleCalculateEdgeDerivatives on this engine's patterns: the edges in chunks (gradient_chunk), per chunk one launch of
+// k_edge_gradient and one of k_gradient_sums, then the chunk's results come back through d_tmp.
+inline int Instance::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
+                                  double* sums, double* sumsSq)
+{
+    const char* const who = "beagleCalculateEdgeDerivatives";
+    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
+    if (K > 1) {
+        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
+        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
+    }
+    for (int e = 0; e < count; ++e) {
+        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
+        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
+        if (post[e] < 0 || post[e] >= nBuffers || (!tipStates[post[e]] && !valid[post[e]])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
+        if (dmat[e] < 0 || dmat[e] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
+    }
+    if (count <= 0) return BEAGLE_SUCCESS;
+    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
+    std::vector<GradEdge> table((size_t) count);
+    for (int e = 0; e < count; ++e) {
+        GradEdge& t = table[(size_t) e];
+        std::memset(&t, 0, sizeof t);
+        t.pre = partials[pre[e]];
+        t.postTip = tipStates[post[e]] ? 1 : 0;
+        t.post = tipStates[post[e]] ? (const void*) tipStates[post[e]] : (const void*) partials[post[e]];
+        t.D = matrixPtr(dmat[e]);
+    }
+    int rc = grow(&d_preTable, &preTableCap, table.size() * sizeof(GradEdge));
+    if (rc) return rc;
+    rc = upload(d_preTable, table.data(), table.size() * sizeof(GradEdge));
+    if (rc) return rc;
+    const int nb = Ppad / 64;
+    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
+    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
+    rc = grow(&d_tmp, &tmpCap, (nSite + nBlock + nOut) * sizeof(double));
+    if (rc) return rc;
+    double* const d_site_ = static_cast<double*>(d_tmp);
+    double* const d_block = d_site_ + nSite;
+    double* const d_out = d_block + nBlock;
+    std::vector<double> h(nSite + nOut);
+    GradArgs a;
+    a.g = layoutArgs();
+    a.q = K > 1 ? d_q : nullptr;
+    a.pattern_weights = d_pweights;
+    a.site = sites ? d_site_ : nullptr;
+    a.sums = d_block;
+    a.nb = nb;
+    auto kernel = s4 ? k_edge_gradient<DERIV_S4, float> : wg ? k_edge_gradient<DERIV_WG, float> : k_edge_gradient<DERIV_LEVELS, float>;
+    for (int e0 = 0; e0 < count; e0 += chunk) {
+        const int ne = std::min(chunk, count - e0);
+        a.edges = static_cast<const GradEdge*>(d_preTable) + e0;
+        a.edgeCount = ne;
+        MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, stream, a);
+        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, stream, (const double*) d_block, nb, ne, d_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        syncedClock = launchClock;
+        if (sites) HIP_TRY(hipMemcpy(h.data(), d_site_, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
+        for (int e = 0; e < ne; ++e) {
+            if (sites) std::memcpy(sites + (size_t) (e0 + e) * siteStride, h.data() + (size_t) e * Ppad, (size_t) P * sizeof(double));
+            if (sums) sums[e0 + e] = h[nSite + (size_t) e];
+            if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
+        }
+    }
+    return BEAGLE_SUCCESS;
+}
+
 // Branch-length derivatives over one edge: one launch of k_edge_derivatives on this engine's partials layout, then a wait.  Never the
 // fused path-and-likelihood launch: a held path runs first, like every queued list and matrix job.
 inline int Instance::edgeDerivatives(int parent, int child, int prob, int d1, int d2, int wIdx, int fIdx, int cumIdx, double out3[3])
@@ -2909,35 +3129,15 @@ inline int Instance::edgeDerivatives(int parent, int child, int prob, int d1, in
         HIP_TRY(hipHostMalloc(&h_deriv, (size_t) 3 * (Ppad + nb) * sizeof(double), hipHostMallocDefault));
         HIP_TRY(hipHostGetDevicePointer((void**) &h_deriv_dev, h_deriv, 0));
     }
+    lastLnl.remember(&parent, &child, &prob, &wIdx, &fIdx, &cumIdx, 1);
     DerivArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.parent = partials[parent];
-    a.child_tip = tipStates[child] ? 1 : 0;
-    a.child = tipStates[child] ? (const void*) tipStates[child] : (const void*) partials[child];
-    a.matrix[0] = matrixPtr(prob);
+    rc = lnlOperands(a, parent, child, prob, wIdx, fIdx, cumIdx);
+    if (rc) return rc;
     a.matrix[1] = matrixPtr(d1);
     a.matrix[2] = d2 >= 0 ? matrixPtr(d2) : nullptr;
-    a.weights = d_weights + (size_t) wIdx * K;
-    a.freqs = d_freqs + (size_t) fIdx * S;
-    if (cumIdx != BEAGLE_OP_NONE) {
-        if (arena()) {
-            if (scaleState[cumIdx] != 0) {
-                rc = ensureWide(cumIdx);
-                if (rc) return rc;
-                a.cum = wideScale[cumIdx];
-            }
-        } else {
-            rc = ensureScale(cumIdx);
-            if (rc) return rc;
-            a.cum = scale[cumIdx];
-        }
-    }
     a.pattern_weights = d_pweights;
     a.site = h_deriv_dev;
     a.sums = h_deriv_dev + (size_t) 3 * Ppad;
-    a.pstride = s4 ? (size_t) geom.pstride : (size_t) (wgTileBytes / 4);
-    a.tstride = s4 ? geom.tstride : wgTipTileBytes;
-    a.S = S; a.SP = SP; a.K = K; a.Ppad = Ppad;
     a.first = 0; a.last = P;
     a.sumStride = nb;
     auto kernel = s4 ? k_edge_derivatives<DERIV_S4, float> : wg ? k_edge_derivatives<DERIV_WG, float> : k_edge_derivatives<DERIV_LEVELS, float>;
@@ -3167,6 +3367,7 @@ inline int Instance::finalPass(const MbamdFinalOperation* ops, int count)
         else MBAMD_LAUNCH(k_final_pass<0>, grid, 64, 0, stream, f, S, SP, K, P, (size_t) geom.pstride, (size_t) 0);
         HIP_TRY(hipGetLastError());
         valid[b.destinationPartials] = 1;
+        clearPreOrder(b.destinationPartials);
     }
     return BEAGLE_SUCCESS;
 }

@@ -28,6 +28,7 @@
 #include "mbamd_f64_kernels.h"   // Op64, Walk64Entry / Walk64Args, MatrixJob64, IntegrateArgs64 and the k64_* kernels
 #include "mbamd_walk4_host.h"    // Walk4Builder: the program compiler of the four-state walk
 #include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
+#include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient <DERIV_F64, double>: the pre-order pass and the gradient in all branch lengths
 
 namespace mbamd {
 
@@ -78,6 +79,10 @@ public:
                         const int* cumIdx, const int* partitions, int partitionCount, double* sums);
     bool hasDerivatives() const { return derivValid; }
     const double* siteDerivatives(int order) const { return derivSite.data() + (size_t) order * Ppad; }
+    // The pre-order pass and the gradient in all branch lengths (mbamd_preorder.h; semantics: beagle.h), as on the single-precision
+    // engine: one launch per group of independent operations; the gradient call is synchronous.
+    int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
+    int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq);
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -131,7 +136,16 @@ private:
     struct QueuedOp { BeagleOperation op; int partition, cum; char tip1, tip2; };
     std::vector<QueuedOp> queue;
     std::vector<char> queuedScale;          // [nScale]: an exponent buffer some queued operation reads, writes or accumulates into
-    uint64_t walkLaunches = 0, levelLaunches = 0;
+    uint64_t walkLaunches = 0, levelLaunches = 0, preLaunches = 0;
+    // ---- pre-order pass (mbamd_preorder.h) ----
+    std::vector<char> preOrder;            // per partials buffer: a pre-order operation wrote it and nothing else has since
+    LnlOperands lastLnl;                   // the operands of the latest log-likelihood call: what q is made of
+    uint64_t qStamp = 0;                   // lastLnl.stamp when d_q was computed
+    double* d_q = nullptr;                 // [K][Ppad] posterior category probabilities
+    double* d_grad = nullptr;              // a gradient chunk's per-site values, block sums and sums
+    size_t qCap = 0, gradCap = 0;
+    DerivArgs layoutArgs() const;
+    int ensurePosteriors();
     // ---- matrix updates waiting to run ----
     // Matrix updates are queued like operation lists: MrBayes updates a codon model's eigen parts one call each (src/mbbeagle.c:1475-1486),
     // and three launches of 200 matrices fill the chip worse than one of 600.  Every other entry point flushes (flushQueue); a second
@@ -217,7 +231,7 @@ inline void Engine64::destroy()
     if (!live) return;
     (void) hipSetDevice(device);
     (void) hipStreamSynchronize(stream);
-    void* all[] = {d_partials, d_states, d_matrices, d_eigen, d_freqs, d_weights, d_pweights, d_scale, d_site, d_sums, d_ev, d_stage, d_deriv};
+    void* all[] = {d_partials, d_states, d_matrices, d_eigen, d_freqs, d_weights, d_pweights, d_scale, d_site, d_sums, d_ev, d_stage, d_deriv, d_q, d_grad};
     for (void* p : all)
         if (p) (void) hipFree(p);
     if (d_ring) (void) hipFree(d_ring);
@@ -307,6 +321,7 @@ inline int Engine64::setTipStates(int tip, const int* states)
     for (int c = 0; c < P; ++c) h[c] = (uint8_t) ((states[c] < 0 || states[c] >= S) ? S : states[c]);
     isTip[tip] = 1;
     valid[tip] = 1;
+    if (!preOrder.empty()) preOrder[tip] = 0;
     return upload(statesPtr(tip), h.data(), (size_t) Ppad);
 }
 inline int Engine64::setPartials(int idx, const double* in, bool withCategories)
@@ -320,6 +335,7 @@ inline int Engine64::setPartials(int idx, const double* in, bool withCategories)
                 h[((size_t) k * S + i) * Ppad + c] = in[((size_t) (withCategories ? k : 0) * P + c) * S + i];
     isTip[idx] = 0;
     valid[idx] = 1;
+    if (!preOrder.empty()) preOrder[idx] = 0;
     return upload(partialsPtr(idx), h.data(), bufDoubles * sizeof(double));
 }
 inline int Engine64::getPartials(int idx, double* out)
@@ -535,6 +551,7 @@ inline int Engine64::updatePartialsEx(const void* opsRaw, size_t stride, int n, 
         queue.push_back(e);
         valid[d] = 1;
         isTip[d] = 0;
+        if (!preOrder.empty()) preOrder[d] = 0;              // (no longer the rest-of-tree vector of a pre-order pass)
         if (queuedScale.size() != (size_t) std::max(nScale, 1)) queuedScale.assign((size_t) std::max(nScale, 1), 0);
         if (sw != BEAGLE_OP_NONE) queuedScale[sw] = 1;
         if (sr != BEAGLE_OP_NONE) queuedScale[sr] = 1;
@@ -1054,6 +1071,7 @@ inline int Engine64::logLikelihoods(const int* parent, const int* child, const i
     { const int rcq = flushQueue(); if (rcq) return rcq; }
     if (count < 1 || count > MBAMD_MAX_SUBSETS) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "log-likelihood: more than 8 subsets");
     const int pc = partitions ? partitionCount : 1;
+    if (pc == 1) lastLnl.remember(parent, child, prob, wIdx, fIdx, cumIdx, count);
     const int nblocks = Ppad / 64;
     const size_t nsums = (size_t) nblocks * pc;
     { const int rc = grow_pinned(stream, (void**) &h_sums, &hSumsCap, nsums * sizeof(double), nsums * sizeof(double)); if (rc) return rc; }
@@ -1122,6 +1140,7 @@ inline int Engine64::edgeDerivatives(const int* parent, const int* child, const 
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
     const int pc = partitions ? partitionCount : 1;
+    if (pc == 1) lastLnl.remember(parent, child, prob, wIdx, fIdx, cumIdx, 1);
     const int nblocks = Ppad / 64;
     const size_t nsite = (size_t) 3 * Ppad, nsums = (size_t) pc * 3 * nblocks;
     { const int rc = grow_device(stream, (void**) &d_deriv, &derivCap, (nsite + nsums) * sizeof(double), (nsite + nsums) * sizeof(double)); if (rc) return rc; }
@@ -1181,6 +1200,163 @@ inline int Engine64::edgeDerivatives(const int* parent, const int* child, const 
     derivValid = true;
     return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;
 }
+// ---- the pre-order pass and the gradient in all branch lengths (mbamd_preorder.h), as Instance's ----
+inline DerivArgs Engine64::layoutArgs() const
+{
+    DerivArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.S = S; a.SP = S; a.K = K; a.Ppad = Ppad;
+    a.first = 0; a.last = P;
+    return a;
+}
+inline int Engine64::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx)
+{
+    { const int rcq = flushQueue(); if (rcq) return rcq; }
+    if (n <= 0) return BEAGLE_SUCCESS;
+    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: not on a multi-partition instance");
+    if (cumIdx != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (cumulativeScaleIndex must be BEAGLE_OP_NONE)");
+    std::vector<char> written((size_t) nBuffers, 0);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        if (b.destinationScaleWrite != BEAGLE_OP_NONE || b.destinationScaleRead != BEAGLE_OP_NONE)
+            return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (scale indices must be BEAGLE_OP_NONE)");
+        const int d = b.destinationPartials, p = b.child1Partials, sib = b.child2Partials;
+        if (d < 0 || d >= nBuffers || p < 0 || p >= nBuffers || (sib != BEAGLE_OP_NONE && (sib < 0 || sib >= nBuffers)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: partials index");
+        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
+            (sib != BEAGLE_OP_NONE && (b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: matrix index");
+        if (isTip[d]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination holds compact tip states");
+        if (written[p] ? false : (isTip[p] || !valid[p])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the parent's pre-order buffer holds no partials");
+        if (sib != BEAGLE_OP_NONE && !valid[sib] && !written[sib]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the sibling's buffer was never written");
+        if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
+        written[d] = 1;
+    }
+    std::vector<PreOp> table((size_t) n);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        PreOp& t = table[(size_t) o];
+        std::memset(&t, 0, sizeof t);
+        t.dst = partialsPtr(b.destinationPartials);
+        t.parent = partialsPtr(b.child1Partials);
+        t.mOwn = matrixPtr(b.child1TransitionMatrix);
+        t.sibKind = -1;
+        if (b.child2Partials != BEAGLE_OP_NONE) {
+            const int sib = b.child2Partials;
+            const bool tip = isTip[sib] && !written[sib];
+            t.sibKind = tip ? 1 : 0;
+            t.sib = tip ? (const void*) statesPtr(sib) : (const void*) partialsPtr(sib);
+            t.mSib = matrixPtr(b.child2TransitionMatrix);
+        }
+    }
+    void* d_table = nullptr;
+    { const int rc = stage(table.data(), table.size() * sizeof(PreOp), &d_table); if (rc) return rc; }
+    if (preOrder.size() != (size_t) nBuffers) preOrder.assign((size_t) nBuffers, 0);
+    std::vector<int> start;
+    pre_order_groups(ops, n, nBuffers, start);
+    PreArgs a;
+    a.g = layoutArgs();
+    for (size_t gI = 0; gI + 1 < start.size(); ++gI) {
+        a.ops = static_cast<const PreOp*>(d_table) + start[gI];
+        launch_pre_partials<DERIV_F64, double>(stream, a, start[gI + 1] - start[gI]);
+        HIP_TRY(hipGetLastError());
+        preLaunches++;
+    }
+    for (int o = 0; o < n; ++o) {
+        const int d = ops[o].destinationPartials;
+        valid[d] = 1;
+        isTip[d] = 0;
+        preOrder[d] = 1;
+    }
+    return BEAGLE_SUCCESS;
+}
+inline int Engine64::ensurePosteriors()
+{
+    if (qStamp == lastLnl.stamp && d_q) return BEAGLE_SUCCESS;
+    const LnlOperands& l = lastLnl;
+    if (l.parent < 0 || l.parent >= nBuffers || !valid[l.parent] || isTip[l.parent] || l.weights < 0 || l.weights >= nEigen || l.freqs < 0 || l.freqs >= nEigen ||
+        (l.child >= 0 && (l.child >= nBuffers || !valid[l.child] || l.prob < 0 || l.prob >= nMatrices)) || (l.cum != BEAGLE_OP_NONE && (l.cum < 0 || l.cum >= nScale)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeDerivatives: the operands of the latest log-likelihood call");
+    { const int rc = grow_device(stream, (void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double), (size_t) K * Ppad * sizeof(double)); if (rc) return rc; }
+    DerivArgs a = layoutArgs();
+    a.parent = partialsPtr(l.parent);
+    if (l.child >= 0) {
+        a.child_tip = isTip[l.child] ? 1 : 0;
+        a.child = isTip[l.child] ? (const void*) statesPtr(l.child) : (const void*) partialsPtr(l.child);
+        a.matrix[0] = matrixPtr(l.prob);
+    }
+    a.weights = d_weights + (size_t) l.weights * K;
+    a.freqs = d_freqs + (size_t) l.freqs * S;
+    if (l.cum != BEAGLE_OP_NONE) a.cum = d_scale + (size_t) l.cum * Ppad;
+    a.site = d_q;
+    auto kernel = k_category_posteriors<DERIV_F64, double>;
+    MBAMD_LAUNCH(kernel, (unsigned) (Ppad / 64), 64, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    qStamp = lastLnl.stamp;
+    return BEAGLE_SUCCESS;
+}
+inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq)
+{
+    const char* const who = "beagleCalculateEdgeDerivatives";
+    { const int rcq = flushQueue(); if (rcq) return rcq; }
+    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (K > 1) {
+        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
+        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
+    }
+    for (int e = 0; e < count; ++e) {
+        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
+        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
+        if (post[e] < 0 || post[e] >= nBuffers || !valid[post[e]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
+        if (dmat[e] < 0 || dmat[e] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
+    }
+    if (count <= 0) return BEAGLE_SUCCESS;
+    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
+    std::vector<GradEdge> table((size_t) count);
+    for (int e = 0; e < count; ++e) {
+        GradEdge& t = table[(size_t) e];
+        std::memset(&t, 0, sizeof t);
+        t.pre = partialsPtr(pre[e]);
+        t.postTip = isTip[post[e]] ? 1 : 0;
+        t.post = isTip[post[e]] ? (const void*) statesPtr(post[e]) : (const void*) partialsPtr(post[e]);
+        t.D = matrixPtr(dmat[e]);
+    }
+    void* d_table = nullptr;
+    { const int rc = stage(table.data(), table.size() * sizeof(GradEdge), &d_table); if (rc) return rc; }
+    const int nb = Ppad / 64;
+    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
+    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
+    { const size_t bytes = (nSite + nBlock + nOut) * sizeof(double); const int rc = grow_device(stream, (void**) &d_grad, &gradCap, bytes, bytes); if (rc) return rc; }
+    double* const d_block = d_grad + nSite;
+    double* const d_out = d_block + nBlock;
+    std::vector<double> h(nSite + nOut);
+    GradArgs a;
+    a.g = layoutArgs();
+    a.q = K > 1 ? d_q : nullptr;
+    a.pattern_weights = d_pweights;
+    a.site = sites ? d_grad : nullptr;
+    a.sums = d_block;
+    a.nb = nb;
+    auto kernel = k_edge_gradient<DERIV_F64, double>;
+    for (int e0 = 0; e0 < count; e0 += chunk) {
+        const int ne = std::min(chunk, count - e0);
+        a.edges = static_cast<const GradEdge*>(d_table) + e0;
+        a.edgeCount = ne;
+        MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, stream, a);
+        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, stream, (const double*) d_block, nb, ne, d_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (sites) HIP_TRY(hipMemcpy(h.data(), d_grad, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
+        for (int e = 0; e < ne; ++e) {
+            if (sites) std::memcpy(sites + (size_t) (e0 + e) * P, h.data() + (size_t) e * Ppad, (size_t) P * sizeof(double));
+            if (sums) sums[e0 + e] = h[nSite + (size_t) e];
+            if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
+        }
+    }
+    return BEAGLE_SUCCESS;
+}
 inline int Engine64::getSites(double* out)
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
@@ -1202,8 +1378,8 @@ inline int Engine64::kernelTiming(double* ms, long* launches, int reset)
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
     *ms += 0.0;
-    *launches += (long) (walkLaunches + levelLaunches);
-    if (reset) walkLaunches = levelLaunches = 0;
+    *launches += (long) (walkLaunches + levelLaunches + preLaunches);
+    if (reset) walkLaunches = levelLaunches = preLaunches = 0;
     return BEAGLE_SUCCESS;
 }
 inline const char* Engine64::implName() const

@@ -1,0 +1,334 @@
+// mbamd_preorder.h -- the top-down ("pre-order") pass and the gradient of the log-likelihood in ALL branch lengths (upstream BEAGLE 4's
+// beagleUpdatePrePartials / beagleSetDifferentialMatrix / beagleCalculateEdgeDerivatives; semantics: include/libhmsbeagle/beagle.h,
+// DESIGN 4.4.2).  Included by mbamd_f32.h and mbamd_f64.h; product and TEST-ONLY host emulation compile these same kernels.
+//
+// pre(n), at the child end of n's branch, is the conditional likelihood of the REST of the tree:
+//     tmp[k,c,i]   = pre_parent[k,c,i] * sum_j P_sib,k[i,j] post_sib[k,c,j]         (no sibling: the factor 1)
+//     pre_n[k,c,j] = sum_i P_n,k[i,j] tmp[k,c,i]                                    (the transpose)
+// so that sum_j pre_n[j] post_n[j] is the category's site likelihood at every node.  Every destination column (pattern, category) is
+// brought to [0.5, 1) by its own power of two -- frexp of the column maximum, exact -- and THE EXPONENT IS DISCARDED: per category
+//     g_k(c) = (sum_l pre[l] sum_j D_k[l,j] post[j]) / (sum_l pre[l] post[l]),      D_k = r_k Q
+// is free of any per-(pattern, category) scale of either buffer, and the derivative of the site log-likelihood in the branch length is
+//     d_c = sum_k q_k(c) g_k(c),     q_k(c) = w_k l_k(c) / sum_k' w_k' l_k'(c)
+// with q the posterior category probabilities of the pattern -- the same for every branch, computed once per log-likelihood call by
+// k_category_posteriors from that call's operands (the L-sum of k_edge_derivatives, per-category exponents recombined).  A category
+// whose denominator is zero has underflowed and carries nothing: it is skipped.
+//
+// Arithmetic as everywhere: products in the engine's precision (FMA chains over the states, ascending), sums over states and
+// categories of the read-outs in double, block sums through mbd_wave_sum_store (fixed order).
+#ifndef MBAMD_PREORDER_H_
+#define MBAMD_PREORDER_H_
+
+#include <math.h>
+
+#include "mbamd_host.h"          // beagle.h, <algorithm>, <vector>
+#include "mbamd_derivatives.h"
+
+namespace mbamd {
+
+// one pre-order operation in device pointers.  sibKind: 0 post-order partials, 1 compact tip states, -1 no sibling factor
+struct PreOp {
+    void*       dst;
+    const void* parent;
+    const void* sib;
+    const void* mOwn;
+    const void* mSib;
+    int         sibKind;
+    int         pad_;
+};
+// g: the layout (S, SP, K, Ppad, pstride, tstride; last = the pattern count).  One launch runs ops[0 .. grid) -- operations that
+// neither read nor write what another of them writes.
+struct PreArgs {
+    DerivArgs    g;
+    const PreOp* ops;
+};
+
+// one branch of a gradient call
+struct GradEdge {
+    const void* pre;
+    const void* post;             // post-order partials, or compact tip states (postTip)
+    const void* D;                // the differential matrix, an ordinary matrix buffer
+    int         postTip;
+    int         pad_;
+};
+struct GradArgs {
+    DerivArgs       g;
+    const GradEdge* edges;        // the edges of this launch (grid y)
+    const double*   q;            // [K][Ppad] posterior category probabilities, or null (one category: q = 1)
+    const double*   pattern_weights;
+    double*         site;         // [edges][Ppad] unweighted d_c, or null: block sums only
+    double*         sums;         // [2][edges][nb]: weight_c d_c and weight_c d_c^2, one per 64-pattern block
+    int             nb, edgeCount;
+};
+
+__device__ __forceinline__ int pre_exponent(float mx) { return (mx > 0.0f && mx < 3.0e38f) ? mbd_frexp_exp(mx) : 0; }
+__device__ __forceinline__ int pre_exponent(double mx) { int e = 0; if (mx > 0.0 && mx < 1.0e300) (void) frexp(mx, &e); return e; }
+__device__ __forceinline__ float pre_scaled(float v, int e) { return mbd_ldexp(v, -e); }
+__device__ __forceinline__ double pre_scaled(double v, int e) { return ldexp(v, -e); }
+
+// dynamic LDS of the general kernel: the two matrices [from][to], then two columns [state][thread]
+template <class Real> inline size_t pre_lds_bytes(int S) { return ((size_t) 2 * S * S + (size_t) 2 * S * 64) * sizeof(Real); }
+
+// Four states (DERIV_S4): a thread owns a (pattern, category) column -- one f4 load per operand (bitplanes for a tip sibling), both
+// 4 x 4 matrices in registers (wave-uniform: a wave is one category of one block), one f4 store; no LDS.  Grid (waves / 4, operations).
+// Other layouts: grid (64-pattern blocks, categories, operations), 64 threads; the two matrices of the operation are staged into LDS
+// once per workgroup and a thread walks its own column in LDS, [state][thread] (see k_final_pass: as private arrays indexed at run
+// time these are scratch).  Threads beyond the last pattern only take part in the barrier.
+template <int LAYOUT, class Real>
+__global__ void __launch_bounds__(LAYOUT == DERIV_S4 ? 256 : 64)
+k_pre_partials(PreArgs a)
+{
+    const DerivArgs& g = a.g;
+    if constexpr (LAYOUT == DERIV_S4) {
+        const PreOp op = a.ops[blockIdx.y];
+        const int wave = (int) blockIdx.x * 4 + mbd_wave_index();
+        if (wave >= g.Ppad / 64 * g.K) return;
+        const int b = wave / g.K, k = wave - b * g.K, lane = (int) (threadIdx.x & 63u);
+        if (b * 64 + lane >= g.last) return;
+        const size_t at = (size_t) b * g.pstride + (size_t) k * 64 + lane;
+        f4 t = reinterpret_cast<const f4*>(op.parent)[at];
+        if (op.sibKind >= 0) {
+            float v[4];
+            if (op.sibKind == 1) {
+                const uint64_t* planes = reinterpret_cast<const uint64_t*>(op.sib) + (size_t) b * g.tstride;
+                for (int j = 0; j < 4; ++j) v[j] = (planes[j] >> lane & 1u) ? 1.0f : 0.0f;
+            } else {
+                const f4 q = reinterpret_cast<const f4*>(op.sib)[at];
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            }
+            const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(op.mSib)) + k * 16;      // m[j * 4 + i] = P(i -> j)
+            t.x *= fmaf(m[12], v[3], fmaf(m[8], v[2], fmaf(m[4], v[1], m[0] * v[0])));
+            t.y *= fmaf(m[13], v[3], fmaf(m[9], v[2], fmaf(m[5], v[1], m[1] * v[0])));
+            t.z *= fmaf(m[14], v[3], fmaf(m[10], v[2], fmaf(m[6], v[1], m[2] * v[0])));
+            t.w *= fmaf(m[15], v[3], fmaf(m[11], v[2], fmaf(m[7], v[1], m[3] * v[0])));
+        }
+        const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(op.mOwn)) + k * 16;
+        f4 r;
+        r.x = fmaf(m[3], t.w, fmaf(m[2], t.z, fmaf(m[1], t.y, m[0] * t.x)));
+        r.y = fmaf(m[7], t.w, fmaf(m[6], t.z, fmaf(m[5], t.y, m[4] * t.x)));
+        r.z = fmaf(m[11], t.w, fmaf(m[10], t.z, fmaf(m[9], t.y, m[8] * t.x)));
+        r.w = fmaf(m[15], t.w, fmaf(m[14], t.z, fmaf(m[13], t.y, m[12] * t.x)));
+        const int e = pre_exponent(fmaxf(fmaxf(r.x, r.y), fmaxf(r.z, r.w)));
+        r.x = pre_scaled(r.x, e); r.y = pre_scaled(r.y, e); r.z = pre_scaled(r.z, e); r.w = pre_scaled(r.w, e);
+        reinterpret_cast<f4*>(op.dst)[at] = r;
+    } else {
+        const int S = g.S;
+        const PreOp op = a.ops[blockIdx.z];
+        const int c = (int) blockIdx.x * 64 + (int) threadIdx.x, k = (int) blockIdx.y;
+        Real* const mOwn = mbd_dyn_lds<Real>();
+        Real* const mSib = mOwn + (size_t) S * S;
+        Real* const colA = mSib + (size_t) S * S + threadIdx.x;       // element i of this thread's column: colA[i * 64]
+        Real* const colB = colA + (size_t) S * 64;
+        for (int e = (int) threadIdx.x; e < S * S; e += 64) {
+            // (in storage order: the fp32 engine keeps matrices transposed)
+            const int i = LAYOUT == DERIV_F64 ? e / S : e % S, j = LAYOUT == DERIV_F64 ? e % S : e / S;
+            mOwn[i * S + j] = deriv_matrix<LAYOUT, Real>(op.mOwn, g, k, i, j);
+            if (op.sibKind >= 0) mSib[i * S + j] = deriv_matrix<LAYOUT, Real>(op.mSib, g, k, i, j);
+        }
+        MBAMD_SYNC();
+        if (c >= g.last) return;
+        unsigned tip = 0;
+        if (op.sibKind == 1) tip = deriv_tip<LAYOUT>(op.sib, g, c);
+        else if (op.sibKind == 0)
+            for (int j = 0; j < S; ++j) colA[j * 64] = deriv_partial<LAYOUT, Real>(op.sib, g, k, j, c);
+        for (int i = 0; i < S; ++i) {
+            Real f = (Real) 1;
+            if (op.sibKind == 1) {
+                if (tip < (unsigned) S) f = mSib[i * S + (int) tip];
+            } else if (op.sibKind == 0) {
+                f = (Real) 0;
+                for (int j = 0; j < S; ++j) f = deriv_fma(mSib[i * S + j], colA[j * 64], f);
+            }
+            colB[i * 64] = deriv_partial<LAYOUT, Real>(op.parent, g, k, i, c) * f;
+        }
+        Real mx = (Real) 0;
+        for (int j = 0; j < S; ++j) {
+            Real r = (Real) 0;
+            for (int i = 0; i < S; ++i) r = deriv_fma(mOwn[i * S + j], colB[i * 64], r);
+            colA[j * 64] = r;
+            mx = r > mx ? r : mx;
+        }
+        const int e = pre_exponent(mx);
+        Real* const dst = reinterpret_cast<Real*>(op.dst);
+        for (int j = 0; j < S; ++j) {
+            const Real r = pre_scaled(colA[j * 64], e);
+            if constexpr (LAYOUT == DERIV_F64) dst[((size_t) k * S + j) * (size_t) g.Ppad + c] = r;
+            else if constexpr (LAYOUT == DERIV_WG) dst[wg_index(S, g.pstride, k, j, c)] = r;
+            else dst[gen_index(g.K, S, k, j, c)] = r;
+        }
+    }
+}
+
+// q[k][c]: the posterior probability of category k at pattern c under the operands of a log-likelihood call (a: as for
+// k_edge_derivatives -- parent, child or null, matrix[0], weights, freqs, cum; site = q, [K][Ppad]).  One thread per pattern.
+template <int LAYOUT, class Real>
+__global__ void __launch_bounds__(64)
+k_category_posteriors(DerivArgs a)
+{
+    constexpr bool PER_CATEGORY = LAYOUT == DERIV_S4 || LAYOUT == DERIV_WG;
+    const int S = a.S, K = a.K;
+    const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
+    if (c >= a.last) return;
+    int emax = 0;
+    if (a.cum != nullptr && PER_CATEGORY) {
+        emax = -2147483647;
+        for (int k = 0; k < K; ++k) { const int e = a.cum[(size_t) k * a.Ppad + c]; emax = e > emax ? e : emax; }
+    }
+    const unsigned tip = a.child_tip ? deriv_tip<LAYOUT>(a.child, a, c) : 0u;
+    double L = 0.0;
+    for (int k = 0; k < K; ++k) {
+        double cat = 0.0;
+        for (int i = 0; i < S; ++i) {
+            Real f = (Real) 1;
+            if (a.child != nullptr) {
+                if (a.child_tip && LAYOUT != DERIV_S4) {
+                    if (tip < (unsigned) S) f = deriv_matrix<LAYOUT, Real>(a.matrix[0], a, k, i, (int) tip);
+                } else {
+                    f = (Real) 0;
+                    for (int j = 0; j < S; ++j) {
+                        const Real v = a.child_tip ? ((tip >> j & 1u) ? (Real) 1 : (Real) 0) : deriv_partial<LAYOUT, Real>(a.child, a, k, j, c);
+                        f = deriv_fma(deriv_matrix<LAYOUT, Real>(a.matrix[0], a, k, i, j), v, f);
+                    }
+                }
+            }
+            cat += (double) (deriv_partial<LAYOUT, Real>(a.parent, a, k, i, c) * f) * a.freqs[i];
+        }
+        double l = cat * a.weights[k];
+        if constexpr (PER_CATEGORY) l = ldexp(l, (a.cum != nullptr ? a.cum[(size_t) k * a.Ppad + c] : 0) - emax);
+        a.site[(size_t) k * a.Ppad + c] = l;
+        L += l;
+    }
+    for (int k = 0; k < K; ++k) a.site[(size_t) k * a.Ppad + c] = L > 0.0 ? a.site[(size_t) k * a.Ppad + c] / L : 0.0;
+}
+
+// d_c of every edge of the launch: grid (64-pattern blocks, edges), one thread per pattern, looping over the categories.
+template <int LAYOUT, class Real>
+__global__ void __launch_bounds__(64)
+k_edge_gradient(GradArgs a)
+{
+    const DerivArgs& g = a.g;
+    const int S = g.S, K = g.K;
+    const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
+    const GradEdge ed = a.edges[blockIdx.y];
+    double d = 0.0, pw = 0.0;
+    if (c < g.last) {
+        const unsigned tip = ed.postTip ? deriv_tip<LAYOUT>(ed.post, g, c) : 0u;
+        for (int k = 0; k < K; ++k) {
+            double num = 0.0, den = 0.0;
+            if constexpr (LAYOUT == DERIV_S4) {
+                const size_t at = blk_index(c, g.pstride) + (size_t) k * 64;
+                const f4 p4 = reinterpret_cast<const f4*>(ed.pre)[at];
+                const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+                float v[4];
+                if (ed.postTip) {
+                    for (int j = 0; j < 4; ++j) v[j] = (tip >> j & 1u) ? 1.0f : 0.0f;
+                } else {
+                    const f4 q4 = reinterpret_cast<const f4*>(ed.post)[at];
+                    v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
+                }
+                const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(ed.D)) + k * 16;          // m[j * 4 + l] = D(l -> j)
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    const float f = fmaf(m[12 + l], v[3], fmaf(m[8 + l], v[2], fmaf(m[4 + l], v[1], m[l] * v[0])));
+                    num += (double) (p[l] * f);
+                    den += (double) (p[l] * v[l]);
+                }
+            } else {
+                for (int l = 0; l < S; ++l) {
+                    const Real p = deriv_partial<LAYOUT, Real>(ed.pre, g, k, l, c);
+                    Real f = (Real) 0, v;
+                    if (ed.postTip) {
+                        // (a missing state is the vector of ones: the rows of D sum to zero)
+                        v = (tip >= (unsigned) S || tip == (unsigned) l) ? (Real) 1 : (Real) 0;
+                        if (tip < (unsigned) S) f = deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, (int) tip);
+                    } else {
+                        for (int j = 0; j < S; ++j)
+                            f = deriv_fma(deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, j), deriv_partial<LAYOUT, Real>(ed.post, g, k, j, c), f);
+                        v = deriv_partial<LAYOUT, Real>(ed.post, g, k, l, c);
+                    }
+                    num += (double) (p * f);
+                    den += (double) (p * v);
+                }
+            }
+            if (den > 0.0) d += (a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0) * (num / den);
+        }
+        if (a.site != nullptr) a.site[(size_t) blockIdx.y * g.Ppad + c] = d;
+        pw = a.pattern_weights[c];
+    }
+    mbd_wave_sum_store(pw * d, a.sums + (size_t) blockIdx.y * a.nb + blockIdx.x);
+    mbd_wave_sum_store(pw * d * d, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
+}
+
+// out[q * edges + e] = the sum of the nb block sums of (q, e), in a fixed order: grid (edges, 2), one wave each
+__global__ void __launch_bounds__(64)
+k_gradient_sums(const double* __restrict__ sums, int nb, int edges, double* __restrict__ out)
+{
+    const size_t row = (size_t) blockIdx.y * edges + blockIdx.x;
+    double s = 0.0;
+    for (int b = (int) threadIdx.x; b < nb; b += 64) s += sums[row * nb + b];
+    mbd_wave_sum_store(s, out + row);
+}
+
+// ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
+
+// What an engine remembers of its latest beagleCalculate{Root,Edge}LogLikelihoods call (integers only): the operands q is made of.
+struct LnlOperands {
+    uint64_t stamp = 0;           // bumped by every such call
+    int count = 0;                // its subset count (0: no call yet)
+    int parent = -1, child = -1, prob = -1, weights = -1, freqs = -1, cum = -1;      // of subset 0 (child < 0: a root call)
+    void remember(const int* p, const int* ch, const int* pr, const int* w, const int* f, const int* cu, int n)
+    {
+        ++stamp;
+        count = n;
+        parent = p[0]; child = ch ? ch[0] : -1; prob = ch ? pr[0] : -1; weights = w[0]; freqs = f[0]; cum = cu ? cu[0] : -1;
+    }
+};
+
+// A pre-order list cut into launches: start[g] .. start[g + 1] are the operations of launch g.  A new launch begins where an operation
+// reads or writes a buffer the current launch writes, or writes a buffer the current launch reads.
+inline void pre_order_groups(const BeagleOperation* ops, int n, int nBuffers, std::vector<int>& start)
+{
+    const int maxOps = 32768;                    // (the operation index is a grid dimension)
+    std::vector<char> reads((size_t) nBuffers, 0), writes((size_t) nBuffers, 0);
+    start.assign(1, 0);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        const int d = b.destinationPartials, p = b.child1Partials, s = b.child2Partials;
+        const bool cut = writes[p] || (s >= 0 && writes[s]) || writes[d] || reads[d] || o - start.back() >= maxOps;
+        if (cut && o > start.back()) {
+            std::fill(reads.begin(), reads.end(), 0);
+            std::fill(writes.begin(), writes.end(), 0);
+            start.push_back(o);
+        }
+        reads[p] = 1;
+        if (s >= 0) reads[s] = 1;
+        writes[d] = 1;
+    }
+    start.push_back(n);
+}
+
+template <int LAYOUT, class Real>
+inline void launch_pre_partials(hipStream_t stream, const PreArgs& a, int count)
+{
+    auto kernel = k_pre_partials<LAYOUT, Real>;
+    if constexpr (LAYOUT == DERIV_S4) {
+        const unsigned waves = (unsigned) (a.g.Ppad / 64 * a.g.K);
+        MBAMD_LAUNCH(kernel, dim3((waves + 3) / 4, (unsigned) count), 256, 0, stream, a);
+    } else {
+        const size_t lds = pre_lds_bytes<Real>(a.g.S);
+        if (lds > (size_t) 48 * 1024 && hipFuncSetAttribute((const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess)
+            (void) hipGetLastError();
+        MBAMD_LAUNCH_BARRIER(kernel, dim3((unsigned) (a.g.Ppad / 64), (unsigned) a.g.K, (unsigned) count), 64, lds, stream, a);
+    }
+}
+
+// edges of a gradient call per launch: the staging behind one launch ([edges][Ppad] per-site values if asked for, [2][edges][nb] block
+// sums, [2][edges] sums) stays within 4 Mi doubles
+inline int gradient_chunk(int count, int Ppad, bool sites)
+{
+    const size_t per = (size_t) 2 * (Ppad / 64) + 2 + (sites ? (size_t) Ppad : 0);
+    return (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
+}
+
+}  // namespace mbamd
+#endif

@@ -39,8 +39,9 @@ class BeagleDivision:
 
     def __init__(self, div: Division, lib: Optional[bg.BeagleLibrary] = None, nchains: int = 1,
                  scaling: int = MB_BEAGLE_SCALE_ALWAYS, resource: Optional[int] = None, device_eigen: bool = False,
-                 double_precision: bool = False):
+                 double_precision: bool = False, pre_order: bool = False):
         self.div = div
+        self.pre_order = pre_order                      # reserve the buffers of BranchGradient (behind every existing one)
         self.double_precision = double_precision        # `set beagleprecision=double` (src/command.c:6765-6766): a preference flag
         self.device_eigen = device_eigen and div.rate_matrices is not None and bool(np.all(np.asarray(div.pi) > 0))
         self.lib = lib or bg.library()
@@ -78,6 +79,14 @@ class BeagleDivision:
         self.numScalers = (nchains + 1) * (nInt + 1)
         self.cijkIndex = [c * step for c in range(nchains)]
         self.cijkScratchIndex = nchains * step
+        # --- pre-order buffers (BranchGradient): one partials buffer per node and one for the start vector, one matrix for D
+        self.numPreOrder = self.numDiffMatrices = 0
+        if pre_order:
+            self.preOrderIndex = [(self.numCondLikes + i) * step for i in range(nNodes)]
+            self.preOrderStartIndex = (self.numCondLikes + nNodes) * step
+            self.numPreOrder = nNodes + 1
+            self.diffMatrixIndex = self.numTiProbs * step
+            self.numDiffMatrices = 1
         # --- dirty flags ("touch" state), per chain ----------------------------------------------
         self.upDateCl = [[True] * nNodes for _ in range(nchains)]
         self.upDateTi = [[True] * nNodes for _ in range(nchains)]
@@ -98,8 +107,8 @@ class BeagleDivision:
         num_part_ambig = sum(part_ambig)
         req = bg.BEAGLE_FLAG_SCALERS_LOG if self.scaling == MB_BEAGLE_SCALE_ALWAYS else 0   # src/mbbeagle.c:191-194
         self.inst = bg.BeagleInstance(
-            self.lib, self.N, self.numCondLikes * self.step, self.N - num_part_ambig, d.nstates, d.npatterns,
-            (self.nchains + 1) * self.step, self.numTiProbs * self.step, d.ncat, self.numScalers * self.step,
+            self.lib, self.N, (self.numCondLikes + self.numPreOrder) * self.step, self.N - num_part_ambig, d.nstates, d.npatterns,
+            (self.nchains + 1) * self.step, (self.numTiProbs + self.numDiffMatrices) * self.step, d.ncat, self.numScalers * self.step,
             resource=resource, requirement_flags=req,
             preference_flags=bg.BEAGLE_FLAG_PRECISION_DOUBLE if self.double_precision else bg.BEAGLE_FLAG_PRECISION_SINGLE)
         for i in range(self.N):                                           # src/mbbeagle.c:123-167
@@ -377,6 +386,57 @@ class BeagleDivision:
                 break
             self.rescaleFreq[chain] = rescaleFreqNew
         return lnl
+
+    # ---- the gradient in all branch lengths (no counterpart in src/mbbeagle.c) ------------------------------------------
+    def PreOrderOperations(self, chain):
+        """The pre-order list of the whole tree, top-down and level by level (the engine runs operations that do not depend on one
+        another in one launch, and cuts the list where they do): the top interior node hangs from the start vector without a
+        sibling factor, every other node from its parent's pre-order buffer with its sibling's post-order buffer."""
+        t = self.div.tree
+        top = t.root_left
+        ops = [[self.preOrderIndex[top], bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderStartIndex, self.tiProbsIndex[chain][top],
+                bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE]]
+        level = [top]
+        while level:
+            below = []
+            for p in level:
+                for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
+                    ops.append([self.preOrderIndex[n], bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderIndex[p], self.tiProbsIndex[chain][n],
+                                self.condLikeIndex[chain][sib], self.tiProbsIndex[chain][sib]])
+                    if t.left[n] >= 0:
+                        below.append(n)
+            level = below
+        return np.asarray(ops, dtype=np.int32)
+
+    def BranchGradient(self, chain=0, sites=False):
+        """{node: d lnL / d t_node} for all 2N-3 branches of the chain's current tree, after LogLike: the start vector
+        pi_i tip_root[c,i] and D_k = r_k Q are set, the pre-order list of the whole tree is issued and ONE
+        calculate_edge_gradient call reads every branch.  sites=True: (that, {node: per-site derivatives})."""
+        if not self.pre_order:
+            raise ValueError("BranchGradient needs BeagleDivision(..., pre_order=True)")
+        if self.step != 1:
+            raise NotImplementedError("BranchGradient: one eigen-system part per division")
+        d, t = self.div, self.div.tree
+        S, K, P = d.nstates, d.ncat, d.npatterns
+        tip = np.ones((P, S))
+        if d.tip_states[t.root] is not None:
+            st = np.asarray(d.tip_states[t.root])
+            ok = (st >= 0) & (st < S)
+            tip[ok] = 0.0
+            tip[np.arange(P)[ok], st[ok]] = 1.0
+        else:
+            tip = np.asarray(d.tip_partials[t.root], dtype=np.float64).reshape(P, S)
+        start = tip * np.asarray(d.pi, dtype=np.float64)[None, :]
+        self.inst.set_partials(self.preOrderStartIndex, np.broadcast_to(start, (K, P, S)))
+        es = d.eigen[0]
+        q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
+        self.inst.set_differential_matrix(self.diffMatrixIndex, np.asarray(d.cat_rates, dtype=np.float64)[:, None, None] * q[None, :, :])
+        self.inst.update_pre_partials(self.PreOrderOperations(chain))
+        nodes = list(t.all_down_pass)
+        rc, per, sums, _ = self.inst.calculate_edge_gradient([self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes],
+                                                             [self.diffMatrixIndex] * len(nodes), [self.cijkIndex[chain]] * len(nodes), sites=sites)
+        grad = {n: float(sums[i]) for i, n in enumerate(nodes)}
+        return (grad, {n: per[i] for i, n in enumerate(nodes)}) if sites else grad
 
     def LogLike(self, chain=0):
         """One full evaluation of a chain from its current dirty flags; clears them afterwards."""
