@@ -2,6 +2,9 @@
 // mrbayes_amd/csrc/device/mbamd_dev_base.h, found first on the include path of the host-emulation build.  Never part of the product.
 #ifndef MBAMD_DEV_BASE_H_
 #define MBAMD_DEV_BASE_H_
+#include <map>
+#include <cstdio>
+#include <cstdlib>
 #include <cmath>
 #define MBAMD_AS_GLOBAL
 #define MBAMD_AS_CONST
@@ -59,12 +62,35 @@ inline double mbd_shfl_down_32(double v, int off)                  // (a wave-wi
     return (src >> 5) == (lane >> 5) ? __builtin_bit_cast(double, x.a[src]) : v;
 }
 template <class T> inline T* mbd_dyn_lds() { return reinterpret_cast<T*>(mbamd_emu_dyn_lds()); }
-// (threads of a block run one after the other between barriers: thread 0 comes first)
+// The product's order: six halving steps (v += the value 32, 16, ... 1 lanes up), lane 0's result -- a serial sum would round 63
+// times where the device rounds six times, and tests/test_operation_bounds.py holds the returned sums to rounding level.
+struct EmuLaneValues { double v[64] = {}; unsigned arrived = 0; };
+inline double emu_wave_tree_sum(double (&t)[64])
+{
+    for (unsigned off = 32; off > 0; off >>= 1)
+        for (unsigned l = 0; l < off; ++l) t[l] += t[l + off];
+    return t[0];
+}
+// (threads of a block run one after the other between barriers, thread 0 first: a 64-thread block's values are kept until the last
+//  thread brings its own; other block shapes add up as they come)
 // (as fibers the lanes of a wave reach this point in any order -- whoever completed the last collective runs on first: the lanes'
-//  values meet in a wave-wide exchange and the first thread adds them up in lane order)
+//  values meet in a wave-wide exchange and the first thread adds them up)
 inline void mbd_wave_sum_store(double v, double* slot)
 {
     if (emu_fibers().current < 0) {
+        if (blockDim.x == 64u && blockDim.y == 1u && blockDim.z == 1u) {
+            // PRECONDITION (as on the device, where the sum is a wave-wide exchange): all 64 threads of the block call, for a given
+            // destination in the order 0 ... 63 -- a kernel whose lanes return before the sum has no result here.  Checked below.
+            static thread_local std::map<double*, EmuLaneValues> kept;      // (by destination: a thread may bring several sums in a row)
+            EmuLaneValues& mine = kept[slot];
+            if (mine.arrived != threadIdx.x) {
+                std::fprintf(stderr, "host emulation: mbd_wave_sum_store: thread %u arrived where thread %u was due\n", threadIdx.x, mine.arrived);
+                std::abort();
+            }
+            mine.v[mine.arrived++] = v;
+            if (threadIdx.x == 63u) { *slot = emu_wave_tree_sum(mine.v); kept.erase(slot); }
+            return;
+        }
         if (threadIdx.x == 0) *slot = 0.0;
         *slot += v;
         return;
@@ -73,10 +99,10 @@ inline void mbd_wave_sum_store(double v, double* slot)
     std::memcpy(&bits, &v, sizeof bits);
     const EmuExchange x = mbamd_emu_exchange(bits, 0);
     if (threadIdx.x != 0) return;
-    double total = 0.0;
+    double t[64];
     const unsigned n = blockDim.x < 64u ? blockDim.x : 64u;
-    for (unsigned l = 0; l < n; ++l) { double t; std::memcpy(&t, &x.a[l], sizeof t); total += t; }
-    *slot = total;
+    for (unsigned l = 0; l < 64u; ++l) { t[l] = 0.0; if (l < n) std::memcpy(&t[l], &x.a[l], sizeof(double)); }
+    *slot = emu_wave_tree_sum(t);
 }
 inline void mbd_block_sum2_256(double off, double diag, double* red, int tid, double& o4, double& d4)
 {
