@@ -15,6 +15,7 @@ absolute values of D1_c's addends (A2_c likewise),
     |d2 - d2_ref| <= (S + 8) u [(A2_c + |D2_c|) / L_c + 2 |d1_c| (A1_c + |D1_c|) / L_c]
 u = 2^-24 (single precision); u = 2^-53 kappa on the double-precision engine, kappa the cancellation inside the spectral sum of
 the matrices (computed below from the eigen-system).  The weighted sums get sum_c weight_c times the per-site bounds.
+(The matrices P, P', P'' themselves are held to a tighter bound, in double roundoffs, by tests/test_matrix_bounds.py.)
 """
 import ctypes as C
 
