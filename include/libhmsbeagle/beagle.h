@@ -427,6 +427,10 @@ BEAGLE_DLLEXPORT int mbamdGetKernelTiming(int instance, double* outMilliseconds,
  * log-likelihood behind them as one launch, out[4] lists compiled for the tree-walk kernel, out[5] their operations.  (Counters for
  * tests and MBAMD_STATS; a facade or a double-precision instance reports zeros.) */
 BEAGLE_DLLEXPORT int mbamdGetListCounts(int instance, long* out6);
+/* Launches of the 4-state tree-walk kernel since the instance was made: out[0] on its plain instantiation (whole-tree lists: one
+ * wave, every entry an operation, no prefetch, wait, barrier or stored exponent), out[1] on the generic one.  (As above: for tests;
+ * a facade or a double-precision instance reports zeros; a null pointer is BEAGLE_ERROR_OUT_OF_RANGE.) */
+BEAGLE_DLLEXPORT int mbamdGetWalkCounts(int instance, long* out2);
 /* While the timing is on: device time (ms) of whole evaluations -- from the first kernel launched after a
  * Calculate*LogLikelihoods call to the end of the next integration kernel, i.e. every kernel of a step (transition matrices,
  * partials, integration) and the gaps between them -- and how many such spans were closed. */

@@ -64,7 +64,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
-    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
+    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
@@ -150,6 +150,7 @@ class BeagleLibrary:
         L.beagleCalculateEdgeDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetStepTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdUpdateFinalPartials.argtypes = [C.c_int, C.c_void_p, C.c_int]
         L.mbamdGetScaledPartials.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -504,6 +505,12 @@ class BeagleInstance:
         """(lists, paths, forked paths, paths fused with their log-likelihood, tree walks, their operations) of the lists (4-state calls; 20- and 60-63-state queue flushes)."""
         out = (C.c_long * 6)()
         self._chk(self.lib.mbamdGetListCounts(self.id, out), "mbamdGetListCounts")
+        return tuple(int(v) for v in out)
+
+    def get_walk_counts(self):
+        """(launches of the 4-state walk kernel's plain instantiation, launches of the generic one)"""
+        out = (C.c_long * 2)()
+        self._chk(self.lib.mbamdGetWalkCounts(self.id, out), "mbamdGetWalkCounts")
         return tuple(int(v) for v in out)
 
     # ---- reports (include/libhmsbeagle/mbamd_reports.h) --------------------------------------------

@@ -1049,6 +1049,15 @@ int mbamdGetListCounts(int instance, long* out6)
     in->listCounts(out6);
     return BEAGLE_SUCCESS;
 }
+int mbamdGetWalkCounts(int instance, long* out2)
+{
+    GET_INSTANCE(instance);
+    if (!out2) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetWalkCounts: null output");
+    out2[0] = out2[1] = 0;
+    if (!in) return BEAGLE_SUCCESS;              // (counted by the one single-precision engine only)
+    in->walkCounts(out2);
+    return BEAGLE_SUCCESS;
+}
 // Device time of whole evaluations while mbamdKernelTiming is on: from the first kernel launched after a log-likelihood
 // call to the end of the next integration kernel -- every kernel of a step and the gaps between them (HIP events on the
 // engine's stream).  Children: the largest among them.

@@ -71,6 +71,7 @@ struct Plan {
     size_t cap = 0;                  // bytes allocated for d_table
     struct Segment {                             // tree-walk path: one launch per hazard-free segment
         size_t first; int W, entries, nslots, tail = 2;
+        bool plain = false, peel = false;        // 4-state walk: nothing rare in it (Walk4Template::plain / peel) -- k_walk4_t<Walk4Args, true>
     };
     std::vector<Segment> segments;               // (Walk4Entry index of its program in d_table, geometry)
     std::vector<Walk4Entry> inlineProg;          // 4-state walk: a short single-segment program travels in the kernel arguments instead
@@ -164,6 +165,7 @@ struct Instance {
     int kernelTiming(double* ms, long* launches, int reset);
     int stepTiming(double* ms, long* steps, int reset);
     void listCounts(long out6[6]) const { const long c[6] = {listsTotal, listsPath, forkedPaths, fusedPaths, listsWalked, opsWalked}; std::copy(c, c + 6, out6); }
+    void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of k_walk4_t<Walk4Args, true> / of the generic instantiations
     int walkTrace(long long* out, int maxSteps, int* outSteps, int* outWaves);
 
 private:
@@ -379,6 +381,7 @@ private:
     uint64_t planClock = 0;
     int layoutEpoch = 0;             // bumped whenever a buffer changes between compact-tip and partials form
     long planHits = 0, planMisses = 0, fusedPaths = 0, heldPaths = 0, forkedPaths = 0, listsTotal = 0, listsPath = 0, opsWalked = 0, listsWalked = 0;
+    long walksPlain = 0, walksGeneric = 0;       // k_walk4_t launches: the plain instantiation / the generic ones (mbamdGetWalkCounts)
 
     // ---- helpers ----------------------------------------------------------------------------
     int grow(void** p, size_t* cap, size_t bytes) { return grow_device(stream, p, cap, bytes, std::max(bytes, *cap * 2)); }
@@ -701,6 +704,7 @@ inline int Instance::configureWalk()
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) numCU = prop.multiProcessorCount;
     const int maxLds = 160 * 1024;
     if (s4 && (hipFuncSetAttribute((const void*) k_walk4_t<Walk4Args>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
+               hipFuncSetAttribute((const void*) k_walk4_t<Walk4Args, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
                hipFuncSetAttribute((const void*) k_walk4_t<Walk4ArgsInline>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess))
         (void) hipGetLastError();
     if (wg) {
@@ -1611,6 +1615,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         Plan::Segment sg;
         sg.first = w4table.size();
         sg.W = t.W; sg.entries = t.entries; sg.nslots = t.nslots; sg.tail = t.tail;
+        sg.plain = t.plain && !wg; sg.peel = t.peel;
         plan.segments.push_back(sg);
         w4table.resize(sg.first + t.prog.size());
         // bytes per buffer inside a block / tile, bytes per LDS slot
@@ -1970,15 +1975,24 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
         a.nslots = sg.nslots;
         a.cumFresh = (walkCumFresh && &sg == &plan.segments.front()) ? 1 : 0;
         a.tail = sg.tail;
+        bool plainHere = false;
         if (!plan.inlineProg.empty()) {
             auto kernel = k_walk4_t<Walk4ArgsInline>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_lds_bytes(sg.W, sg.nslots), stream, ai);
+        } else if (sg.plain && !sw.noPlainWalk) {
+            // nothing rare in the program (a whole-tree list): the instantiation without that code; an odd operation count's padding entry joins the tail
+            a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
+            a.tail = sg.tail + (sg.peel ? 1 : 0);
+            auto kernel = k_walk4_t<Walk4Args, true>;
+            MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, sg.nslots), stream, a);
+            plainHere = true;
         } else {
             a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
             auto kernel = k_walk4_t<Walk4Args>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_lds_bytes(sg.W, sg.nslots), stream, a);
         }
         HIP_TRY(hipGetLastError());
+        ++(plainHere ? walksPlain : walksGeneric);
         pendingLaunches += 1;
     }
     return BEAGLE_SUCCESS;

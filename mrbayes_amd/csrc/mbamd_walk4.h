@@ -154,7 +154,16 @@ namespace mbamd {
 //     test of the entry's flags (MBAMD_W4_RARE; the host marks the entry in front of a SCALE_READ entry with NEXT_READS);
 //   * the copy of a result into the forwarding registers (results alternate between two register sets with the loop's two halves);
 //   * per-entry address arithmetic of the program (a running pointer, one add per two entries).
-template <class ARGS>
+//
+// PLAIN = true: the instantiation for programs in which every entry in front of the read-ahead tail is an operation on one wave
+// with nothing rare about it -- a whole-tree list that rescales everywhere, at chosen nodes or nowhere (the host decides:
+// Walk4Template::plain; only the device-buffer form is instantiated: programs in the kernel arguments are short partial updates).  The
+// MBAMD_W4_RARE block, the stored exponent `er` and the no-op tests are compiled out; the arithmetic of an operation is the same
+// source: the same bits.  Why it is more than a few scalar instructions: `er` may come from an LDS read, lgkmcnt counts LDS reads
+// and scalar loads alike, so the generic loop waits for the scalar-load burst it has just issued -- lgkmcnt(0) in front of
+// e = ew | er -- with its two stores not yet issued.  Here nothing between the burst and the stores reads LDS or a loaded scalar.
+// `entries - tail` may be odd (the host counts the padding entry of an odd operation count to the tail): the last entry is peeled.
+template <class ARGS, bool PLAIN = false>
 __global__ void __launch_bounds__(64 * MBAMD_W4_MAXW)
 k_walk4_t(ARGS AA)
 {
@@ -187,7 +196,7 @@ k_walk4_t(ARGS AA)
     Walk4Mat M2 = walk4_load_matrix(walk4_at(M0, DA.m2));
     Walk4Planes T1 = walk4_load_planes(walk4_at(T0, (DA.ctl & MBAMD_W4_TIP1) ? DA.c1 : 0u));
     Walk4Planes T2 = walk4_load_planes(walk4_at(T0, (DA.ctl & MBAMD_W4_TIP2) ? DA.c2 : 0u));
-    if (DA.ctl & MBAMD_W4_READS) MBAMD_W4_EXPS(DA.eread, 0);
+    if constexpr (!PLAIN) { if (DA.ctl & MBAMD_W4_READS) MBAMD_W4_EXPS(DA.eread, 0); }
     int cum_e = 0;
     f4 RA = {0.0f, 0.0f, 0.0f, 0.0f}, RB = RA;     // results of the even / odd entries (a no-op entry passes the previous one through): a FWD child reads the other set
 
@@ -202,7 +211,7 @@ k_walk4_t(ARGS AA)
     auto step = [&](Walk4Entry& cur, const Walk4Entry& nxt, const Walk4Entry* after, int parity, f4& out, const f4& prev) {
         const unsigned ctl = cur.ctl;
         int er = 0;
-        if (ctl & MBAMD_W4_RARE) {
+        if (!PLAIN && (ctl & MBAMD_W4_RARE)) {
             if (ctl & MBAMD_W4_PF0) {
                 // PF entry: children of later operations that live in HBM -> LDS slots
                 MBAMD_W4_PREFETCH(cur.dst, cur.c1);
@@ -214,7 +223,7 @@ k_walk4_t(ARGS AA)
             if (ctl & MBAMD_W4_READS) er = stage[64 * parity + lane];
         }
         f4 o = prev;                                   // (a no-op entry passes the result of the operation executed last through)
-        if (!(ctl & MBAMD_W4_NOP)) {
+        if (PLAIN || !(ctl & MBAMD_W4_NOP)) {
             f4 a, b;
             if (ctl & MBAMD_W4_TIP1) a = walk4_tip_vector(T1, lane);
             else if (ctl & MBAMD_W4_FWD1) a = prev;
@@ -234,7 +243,7 @@ k_walk4_t(ARGS AA)
         T1 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP1) ? nxt.c1 : 0u));
         T2 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP2) ? nxt.c2 : 0u));
         cur = walk4_load_entry(after);
-        if (!(ctl & MBAMD_W4_NOP)) {
+        if (PLAIN || !(ctl & MBAMD_W4_NOP)) {
             // SCALE_WRITE: this column's own power of two; SCALE_READ (rare path): the stored one; else 2^0 (exact: no branch)
             const int wm = (int) (ctl << 23) >> 31;                                    // mode bit 8 (SCALE_WRITE) -> all ones
             const int ew = scale_exponent(max4(o)) & wm;
@@ -250,18 +259,19 @@ k_walk4_t(ARGS AA)
         }
         out = o;
     };
-    for (int j = 0; j < n; j += 2) {
+    for (int j = 0; j + (PLAIN ? 1 : 0) < n; j += 2) {
         step(DA, DB, pp + 2, 0, RA, RB);
         step(DB, DA, pp + 3, 1, RB, RA);
         pp += 2;
     }
+    if constexpr (PLAIN) { if (n & 1) step(DA, DB, pp + 2, 0, RA, RB); }      // (its successor is the padding entry: valid offsets, nothing executed)
 #undef MBAMD_W4_EXPS
 #undef MBAMD_W4_PREFETCH
     // cumulative exponents of this workgroup's 64 columns: the waves' sums meet in LDS, wave 0 owns the memory update
     // (nobody else touches these 64 entries: no atomics; a fresh buffer is simply stored)
     if (A.cum != nullptr) {
         const int W = (int) (blockDim.x >> 6);
-        if (W > 1) {
+        if (!PLAIN && W > 1) {
             stage[lane] = cum_e;
             walk4_barrier();
             if (wave != 0) return;

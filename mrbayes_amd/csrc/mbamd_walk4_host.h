@@ -57,6 +57,10 @@ struct Walk4Template {
     std::vector<Entry> prog;                       // [W][entries]
     int phases = 1, reloads = 0, externals = 0;
     int evictions = 0;                             // results evicted from a wave's slots and re-read by the same wave
+    // 4-state walk: one wave, and every entry in front of the tail is an operation that carries nothing of MBAMD_W4_RARE (no prefetch,
+    // wait, barrier or stored exponent) -- the shape of a whole-tree list; such a program runs on k_walk4_t<Walk4Args, true>.  `peel`:
+    // the operation count is odd, the last entry in front of the tail is the padding no-op and counts to the tail there.
+    bool plain = false, peel = false;
 };
 
 struct Walk4Scratch {
@@ -596,6 +600,15 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
     for (Walk4Template::Entry& e : t.prog) e.flags = MBAMD_W4_NOP;
     for (int w = 0; w < W; ++w) std::copy(fin[w].begin(), fin[w].end(), t.prog.begin() + (size_t) w * entries + leadNops);
     t.nslots = slotsUsed;
+    // plain (see Walk4Template): part of the structure -- which entries divide by stored exponents is in the caller's structural key
+    t.plain = t.peel = false;
+    if (memSlots && W == 1 && leadNops == 0 && unroll == 2 && tail == 2) {
+        bool plain = true;
+        for (const Walk4Template::Entry& e : fin[0])
+            if (e.op < 0 || e.flags != 0 || e.pfOp[0] >= 0 || e.vmwait != 0xFF || (ops[e.op].scaleRead >= 0 && ops[e.op].scaleWrite < 0)) plain = false;
+        t.plain = plain;
+        t.peel = plain && (int) fin[0].size() == body - 1;
+    }
     return true;
 }
 
