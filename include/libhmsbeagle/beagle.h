@@ -431,6 +431,12 @@ BEAGLE_DLLEXPORT int mbamdGetListCounts(int instance, long* out6);
  * wave, every entry an operation, no prefetch, wait, barrier or stored exponent), out[1] on the generic one.  (As above: for tests;
  * a facade or a double-precision instance reports zeros; a null pointer is BEAGLE_ERROR_OUT_OF_RANGE.) */
 BEAGLE_DLLEXPORT int mbamdGetWalkCounts(int instance, long* out2);
+/* Tip pairs (operations on two compact tips) of whole-tree 4-state lists are not stored by the plain tree-walk kernel: the buffer keeps
+ * a recipe and is recomputed, bit for bit, before the first call that reads it (MBAMD_STORE_TIP_PAIRS=1 stores everything).  Since the
+ * instance was made: out[0] buffers launches left unstored, out[1] buffers materialised since, out[2] launches that materialised them.
+ * (For tests: the sums over the engines behind the instance; a double-precision instance reports zeros; a null pointer is
+ * BEAGLE_ERROR_OUT_OF_RANGE.) */
+BEAGLE_DLLEXPORT int mbamdGetRecomputeCounts(int instance, long* out3);
 /* While the timing is on: device time (ms) of whole evaluations -- from the first kernel launched after a
  * Calculate*LogLikelihoods call to the end of the next integration kernel, i.e. every kernel of a step (transition matrices,
  * partials, integration) and the gaps between them -- and how many such spans were closed. */

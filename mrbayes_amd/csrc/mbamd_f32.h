@@ -75,6 +75,10 @@ struct Plan {
     };
     std::vector<Segment> segments;               // (Walk4Entry index of its program in d_table, geometry)
     std::vector<Walk4Entry> inlineProg;          // 4-state walk: a short single-segment program travels in the kernel arguments instead
+    // 4-state walk: the TIP PAIRS (both children compact tips) of a list that is ONE plain segment in a device buffer -- their entries
+    // carry MBAMD_W4_NOSTORE, their destinations are left unstored with a recipe (Instance::leaveUnstored); empty for every other plan
+    struct TipPair { int entry, dst, tip1, tip2, mode; };
+    std::vector<TipPair> tipPairs;
     bool path = false;                           // 4-state walk: the list is a root-ward path -- inlineProg holds k_path4's entries
     bool forked = false;                         // ... of several arms that join (the list of a topology move)
     bool pathG = false;                          // 20/61-state walk: every list is a root-ward path of the same length -- inlineProg holds k_pathg's entries
@@ -167,6 +171,8 @@ struct Instance {
     void listCounts(long out6[6]) const { const long c[6] = {listsTotal, listsPath, forkedPaths, fusedPaths, listsWalked, opsWalked}; std::copy(c, c + 6, out6); }
     void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of k_walk4_t<Walk4Args, true> / of the generic instantiations
     int walkTrace(long long* out, int maxSteps, int* outSteps, int* outWaves);
+    // tip-pair buffers launches left unstored / buffers materialised since / launches that materialised them (mbamdGetRecomputeCounts)
+    void recomputeCounts(long out3[3]) const { out3[0] += leftUnstored; out3[1] += materialised; out3[2] += materialiseLaunches; }
 
 private:
     friend int new_engine(std::unique_ptr<Instance>&, const Dims&, int, int, const Switches&);
@@ -195,6 +201,29 @@ private:
     std::vector<char> scaleState;    // 0 = never written (zero), 1 = node exponents in the arena, 2 = cumulative (wide)
     int lastWalkW = 0, lastWalkSlots = 0, lastWalkEntries = 0, lastWalkPhases = 0;
     bool walkCumFresh = false;       // the cumulative buffer of the list being submitted holds nothing yet (store, do not add)
+    // ---- tip pairs a whole-tree launch did not store (MBAMD_W4_NOSTORE, mbamd_walk4.h).  Such a buffer stays `valid`: it carries a RECIPE
+    // -- its two compact tips, its scale mode, and its slot (its own index) in a device table of MATRIX SNAPSHOTS float [buffer][2][K][16],
+    // copied by k_walk4_snapshot behind the integration launch (off the critical path) or, at the latest, before anything overwrites a
+    // matrix or reads a recipe (flushSnapshot) -- so a recipe never depends on a matrix buffer the client may overwrite.  Every reader of
+    // partials calls ensureStored first: the unstored buffers among those it names are recomputed into their arena slices by ONE launch of
+    // the generic k_walk4_t (same source, same bits; exponent bytes go to the scratch rows, the real scale buffers were written by the
+    // original launch).  Any write to a buffer drops its recipe; overwriting a tip materialises the recipes that use it first.
+    struct Recipe { int tip1 = -1, tip2 = -1, mode = 0; };
+    std::vector<char> unstored;      // per partials buffer: 1 = valid, not in the arena, recipes[idx] says how to make it
+    std::vector<Recipe> recipes;
+    int nUnstored = 0;               // every hook is one comparison while this is zero
+    float* d_snap = nullptr;         // the matrix snapshots, allocated with the first unstored buffer
+    Plan* snapPlan = nullptr;        // the plan whose tip-pair matrices are still to be copied there
+    void* d_storeProg = nullptr;     size_t storeProgCap = 0;       // a materialising program too long for the kernel arguments
+    std::vector<int> storeList;      // scratch
+    std::vector<Walk4Entry> storeProg;
+    long leftUnstored = 0, materialised = 0, materialiseLaunches = 0;
+    int leaveUnstored(const Plan& plan);
+    int flushSnapshot();
+    int ensureStored(const int* bufs, int n);
+    int ensureStored(int a, int b = -1) { const int v[2] = {a, b}; return nUnstored ? ensureStored(v, 2) : BEAGLE_SUCCESS; }
+    int storeUsersOfTip(int tip);
+    void dropRecipe(int idx) { if (nUnstored && unstored[(size_t) idx]) { unstored[(size_t) idx] = 0; --nUnstored; } }
     // ---- 20/61-state tree walk: lists are deferred and merged (MrBayes submits one list per eigen-system part of a codon
     // model, reference src/mbbeagle.c:1095-1104; together they are ONE forest for the program compiler)
     std::vector<BeagleOperation> wgOps;          // operations of the deferred lists, concatenated
@@ -596,6 +625,8 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
         HIP_TRY(hipMemsetAsync(arenaExp, 0, eBytes, stream));
         wideScale.assign(scale.size(), nullptr);
         scaleState.assign(scale.size(), 0);
+        unstored.assign((size_t) nBuffers, 0);
+        recipes.assign((size_t) nBuffers, Recipe());
         if (sw.verbose)
             std::fprintf(stderr, "[mbamd] arenas: partials %p +%zu, tips %p +%zu, exponents %p +%zu\n",
                          (void*) arenaPartials, pBytes, (void*) arenaTips, tBytes, (void*) arenaExp, eBytes);
@@ -678,7 +709,7 @@ inline Instance::~Instance()
     for (Plan* pl : plans) { if (pl->d_table) (void) hipFree(pl->d_table); delete pl; }
     plans.clear();
     void* bufs[] = {matrices, d_eigen, d_freqs, d_weights, d_rates, d_pweights, d_site,
-                    d_ev, d_tmp, d_trace, d_q, d_preTable};
+                    d_ev, d_tmp, d_trace, d_q, d_preTable, d_snap, d_storeProg};
     for (void* b : bufs) if (b) (void) hipFree(b);
     if (h_sums) (void) hipHostFree(h_sums);
     wait.destroy();
@@ -781,6 +812,11 @@ inline int Instance::setTipMasks(int tip, const std::vector<uint8_t>& h)
     for (int c = 0; c < Ppad; ++c)
         for (int i = 0; i < 4; ++i)
             if (h[c] >> i & 1u) planes[(size_t) (c >> 6) * 4 + i] |= (uint64_t) 1 << (c & 63);
+    if (nUnstored) {                             // recipes that read this tip are made first; whatever the buffer held is gone
+        const int src = storeUsersOfTip(tip);
+        if (src) return src;
+        dropRecipe(tip);
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipMemcpy2D(arenaTips + (size_t) tip * 4, (size_t) geom.tstride * 8, planes.data(), 32, 32, nb, hipMemcpyHostToDevice));
     if (!tipStates[tip]) layoutEpoch++;
@@ -832,6 +868,11 @@ inline int Instance::importPartials(int idx, const double* in, bool hasCategorie
     }
     int rc = ensurePartials(idx);
     if (rc) return rc;
+    if (nUnstored) {                             // (a tip that switches to partials form: its recipes are made first)
+        rc = storeUsersOfTip(idx);
+        if (rc) return rc;
+        dropRecipe(idx);
+    }
     const size_t nIn = (size_t) (hasCategories ? K : 1) * P * S;
     rc = grow(&d_tmp, &tmpCap, nIn * sizeof(double));
     if (rc) return rc;
@@ -858,6 +899,8 @@ inline int Instance::getPartials(int idx, double* out)
     if (idx < 0 || idx >= nBuffers || !valid[idx]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleGetPartials: buffer");
     const size_t total = (size_t) K * P * S;
     int rc = grow(&d_tmp, &tmpCap, total * sizeof(double));
+    if (rc) return rc;
+    rc = ensureStored(idx);
     if (rc) return rc;
     const unsigned blocks = (unsigned) ((total + 255) / 256);
     if (s4) MBAMD_LAUNCH(k_export_partials<1>, blocks, 256, 0, stream, (const float*) partials[idx], S, K, P, Ppad, (size_t) geom.pstride, (double*) d_tmp);
@@ -1013,6 +1056,7 @@ inline int Instance::updateMatrices(int eigenIndex, const int* probIdx, const do
 inline int Instance::flushMatrices()
 {
     if (pendingJobs.empty()) return BEAGLE_SUCCESS;
+    if (snapPlan) { int src = flushSnapshot(); if (src) return src; }     // (the matrices a recipe needs are copied before any is overwritten)
     { int src = spanBegin(); if (src) return src; }
     // one launch per derivative order (MatrixJob::pad_ holds a job's order: 0 -- all there is on MrBayes' path -- 1 or 2)
     bool derivatives = false;
@@ -1094,6 +1138,7 @@ inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
 inline int Instance::setMatrix(int idx, const double* in)
 {
     if (idx < 0 || idx >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTransitionMatrix: matrix index");
+    if (snapPlan) { int src = flushSnapshot(); if (src) return src; }
     std::vector<float> h(matrixFloats, 0.0f);
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < S; ++i)
@@ -1514,6 +1559,21 @@ inline int Instance::prepareCumulative(int idx, bool& fresh)
 inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumIdx)
 {
     if (heldPath) { int prc = runHeldPath(); if (prc) return prc; }      // (a list behind a held path: the path runs first)
+    if (snapPlan) { int src = flushSnapshot(); if (src) return src; }    // (no integration followed the launch; this call may recompile the plan)
+    if (nUnstored) {
+        // children from outside the list that an earlier launch left unstored: made now, before a path is held -- the launch runs
+        // while the host compiles or looks up the list
+        std::vector<int>& ext = w4segList;
+        std::vector<char>& written = w4written;
+        ext.clear();
+        written.assign((size_t) nBuffers, 0);
+        for (int o = 0; o < n; ++o) {
+            for (const int c : {ops[o].child1Partials, ops[o].child2Partials})
+                if (c >= 0 && c < nBuffers && unstored[(size_t) c] && !written[(size_t) c]) ext.push_back(c);
+            if (ops[o].destinationPartials >= 0 && ops[o].destinationPartials < nBuffers) written[(size_t) ops[o].destinationPartials] = 1;
+        }
+        if (!ext.empty()) { int src = ensureStored(ext.data(), (int) ext.size()); if (src) return src; }
+    }
     int32_t* cumPtr = nullptr;
     walkCumFresh = false;
     if (cumIdx != BEAGLE_OP_NONE) {
@@ -1528,6 +1588,7 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
         if (rc == BEAGLE_SUCCESS) {
             StatTimer st_(ST_PLAN);
             plan->path = plan->forked = false;
+            plan->tipPairs.clear();
             rc = buildPath4(*plan, ops, n) ? BEAGLE_SUCCESS : buildWalk(*plan, ops, n);
         }
         if (planBuilt(*plan, rc)) return rc;
@@ -1535,6 +1596,7 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
     // bookkeeping the list implies, whether compiled now or before: destinations valid, exponent buffers in node form
     for (int o = 0; o < n; ++o) {
         valid[ops[o].destinationPartials] = 1;
+        dropRecipe(ops[o].destinationPartials);  // (overwritten; the launch leaves its own tip pairs unstored afresh, runWalk)
         if (ops[o].destinationScaleWrite != BEAGLE_OP_NONE) scaleState[ops[o].destinationScaleWrite] = 1;
     }
     int mrc = flushMatrices();
@@ -1565,6 +1627,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
     written.assign((size_t) nBuffers, 0);
     w4table.clear();
     plan.segments.clear();
+    plan.tipPairs.clear();
     std::vector<Walk4Op>& seg = w4ops;
     seg.clear();
     // segment state: buffers / exponent buffers the current segment has read or written
@@ -1687,6 +1750,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                 mode = op.scaleWrite >= 0 ? SCALE_WRITE : (op.scaleRead >= 0 ? SCALE_READ : SCALE_NONE);
                 if (op.scaleWrite >= 0) e.ewrite = (uint32_t) op.scaleWrite * ebuf;
                 if (op.scaleRead >= 0) e.eread = (uint32_t) op.scaleRead * ebuf;
+                if (op.tip1 && op.tip2) plan.tipPairs.push_back(Plan::TipPair{(int) (sg.first + i), op.dst, op.c1, op.c2, (int) mode});   // (kept or dropped below)
             }
             if (te.vmwait != 0xFF) flags |= MBAMD_W4_VMWAIT;
             // the entry in front of a SCALE_READ entry of the same wave fetches that entry's stored exponents (mbamd_walk4.h)
@@ -1748,7 +1812,15 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                      n, plan.segments.size(), lastWalkW, lastWalkEntries, lastWalkSlots, phases, reloads, externals);
     // a short program goes out with the launch itself (k_walk4_t<Walk4ArgsInline>, k_walkg<..., WalkGArgsInline>)
     plan.inlineProg.clear();
-    if (!sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE) {
+    const bool inlineForm = !sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE;
+    // Tip pairs are not stored where nothing can read the HBM copy in the launch that makes them: the list is ONE segment and that
+    // segment runs on the plain kernel (one wave, no prefetch: every child is a tip, a slot or the forwarded result).  Lists cut over
+    // several waves or segments, programs in the kernel arguments and the generic / path kernels store everything.
+    if (s4 && !sw.storeTipPairs && !sw.noPlainWalk && !inlineForm && plan.segments.size() == 1 && plan.segments[0].plain)
+        for (const Plan::TipPair& tp : plan.tipPairs) w4table[(size_t) tp.entry].ctl |= MBAMD_W4_NOSTORE;
+    else
+        plan.tipPairs.clear();
+    if (inlineForm) {
         plan.inlineProg = w4table;
         return BEAGLE_SUCCESS;
     }
@@ -1986,6 +2058,7 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
             auto kernel = k_walk4_t<Walk4Args, true>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, sg.nslots), stream, a);
             plainHere = true;
+            if (!plan.tipPairs.empty()) { const int urc = leaveUnstored(plan); if (urc) return urc; }
         } else {
             a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
             auto kernel = k_walk4_t<Walk4Args>;
@@ -1996,6 +2069,119 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
         pendingLaunches += 1;
     }
     return BEAGLE_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tip pairs a whole-tree launch did not store (see the members: Recipe, unstored, d_snap).
+// ---------------------------------------------------------------------------------------------
+// behind a launch of the plain kernel whose program carries MBAMD_W4_NOSTORE entries: their destinations hold recipes from now on
+inline int Instance::leaveUnstored(const Plan& plan)
+{
+    if (!d_snap) HIP_TRY(hipMalloc(&d_snap, (size_t) nBuffers * 2 * K * 16 * sizeof(float)));
+    if (snapPlan && snapPlan != &plan) { int rc = flushSnapshot(); if (rc) return rc; }     // (the matrices are what they were at that launch: nothing overwrote one since)
+    for (const Plan::TipPair& tp : plan.tipPairs) {
+        if (!unstored[(size_t) tp.dst]) ++nUnstored;
+        unstored[(size_t) tp.dst] = 1;
+        Recipe& r = recipes[(size_t) tp.dst];
+        r.tip1 = tp.tip1; r.tip2 = tp.tip2; r.mode = tp.mode;
+    }
+    leftUnstored += (long) plan.tipPairs.size();
+    snapPlan = const_cast<Plan*>(&plan);
+    return BEAGLE_SUCCESS;
+}
+
+// the waiting copy of a launch's tip-pair matrices into the snapshot table, now (k_walk4_snapshot reads the plan's own program)
+inline int Instance::flushSnapshot()
+{
+    Plan* const plan = snapPlan;
+    snapPlan = nullptr;
+    if (!plan || plan->segments.size() != 1 || !plan->d_table) return BEAGLE_SUCCESS;
+    const Plan::Segment& sg = plan->segments[0];
+    plan->lastLaunch = ++launchClock;            // (the program must stay what it is until this launch has run: planTable)
+    MBAMD_LAUNCH(k_walk4_snapshot, (unsigned) (sg.entries - sg.tail), 64, 0, stream, reinterpret_cast<const Walk4Entry*>(plan->d_table) + sg.first,
+                 (unsigned) ((size_t) (Ppad / 64) * K), (const float*) matrices, d_snap, K);
+    HIP_TRY(hipGetLastError());
+    return BEAGLE_SUCCESS;
+}
+
+// Every reader of partials, before its launch: the unstored buffers among `bufs` (indices out of range, tips and stored buffers are
+// passed over) are recomputed into the arena by one launch of the generic k_walk4_t -- entries with both children tips, matrices from
+// the snapshot table, no cumulative buffer, the exponent byte to the scratch rows -- and drop their recipes.
+inline int Instance::ensureStored(const int* bufs, int n)
+{
+    if (nUnstored == 0) return BEAGLE_SUCCESS;
+    std::vector<int>& list = storeList;
+    list.clear();
+    for (int i = 0; i < n; ++i) {
+        const int b = bufs[i];
+        if (b < 0 || b >= nBuffers || unstored[(size_t) b] != 1) continue;
+        unstored[(size_t) b] = 2;                // (named twice: listed once)
+        list.push_back(b);
+    }
+    for (int b : list) unstored[(size_t) b] = 1;
+    if (list.empty()) return BEAGLE_SUCCESS;
+    int rc = flushSnapshot();
+    if (rc) return rc;
+    const int m = (int) list.size(), entries = (m + 1) / 2 * 2 + 2;              // the kernel's loop runs two entries a turn and reads two ahead
+    const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
+    const uint32_t scratch = (uint32_t) scale.size();
+    storeProg.resize((size_t) entries);
+    for (int i = 0; i < entries; ++i) {
+        Walk4Entry& e = storeProg[(size_t) i];
+        std::memset(&e, 0, sizeof e);
+        e.ctl = MBAMD_W4_NOP;
+        e.ewrite = (scratch + (uint32_t) (i % MBAMD_W4_SCRATCH_ROWS)) * ebuf;
+        e.eread = scratch * ebuf;
+        if (i >= m) continue;
+        const uint32_t b = (uint32_t) list[(size_t) i];
+        const Recipe& r = recipes[b];
+        e.ctl = MBAMD_W4_TIP1 | MBAMD_W4_TIP2 | ((uint32_t) r.mode << 8);
+        e.dst = b * pbuf;
+        e.c1 = (uint32_t) r.tip1 * 32u;
+        e.c2 = (uint32_t) r.tip2 * 32u;
+        e.m1 = (2u * b) * mbuf;
+        e.m2 = (2u * b + 1u) * mbuf;
+    }
+    Walk4ArgsInline ai;
+    Walk4Args& a = ai.a;
+    a = walk4Args();
+    a.matrices = d_snap;
+    a.cum = nullptr;
+    a.cumFresh = 0;
+    a.entries = entries;
+    a.nslots = 1;
+    a.tail = 2;
+    ++launchClock;
+    if (entries <= MBAMD_W4_INLINE) {
+        std::memcpy(ai.inl, storeProg.data(), (size_t) entries * sizeof(Walk4Entry));
+        auto kernel = k_walk4_t<Walk4ArgsInline>;
+        MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, 1), stream, ai);
+    } else {
+        const size_t bytes = (size_t) entries * sizeof(Walk4Entry);
+        rc = grow(&d_storeProg, &storeProgCap, bytes);
+        if (rc) return rc;
+        rc = upload(d_storeProg, storeProg.data(), bytes);
+        if (rc) return rc;
+        a.prog = static_cast<const Walk4Entry*>(d_storeProg);
+        auto kernel = k_walk4_t<Walk4Args>;
+        MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, 1), stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    for (int b : list) unstored[(size_t) b] = 0;
+    nUnstored -= m;
+    materialised += m;
+    materialiseLaunches += 1;
+    return BEAGLE_SUCCESS;
+}
+
+// a compact tip is about to change (new states, or partials in its place): the unstored buffers made from it are stored first
+inline int Instance::storeUsersOfTip(int tip)
+{
+    if (nUnstored == 0) return BEAGLE_SUCCESS;
+    std::vector<int> users;
+    for (int b = 0; b < nBuffers; ++b)
+        if (unstored[(size_t) b] && (recipes[(size_t) b].tip1 == tip || recipes[(size_t) b].tip2 == tip)) users.push_back(b);
+    return users.empty() ? BEAGLE_SUCCESS : ensureStored(users.data(), (int) users.size());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2789,6 +2975,12 @@ inline int Instance::integrate(const int* parent, const int* child, const int* p
         return rc;
     }
     lastLnl.remember(parent, child, prob, wIdx, fIdx, cumIdx, count);
+    if (nUnstored) {                             // (an edge call over a tip pair, a tree of three tips: made before the launch that reads it)
+        std::vector<int> ops(parent, parent + count);
+        if (child) ops.insert(ops.end(), child, child + count);
+        rc = ensureStored(ops.data(), (int) ops.size());
+        if (rc) return rc;
+    }
     armSums(launchOnly);
     if (!arena()) {
         rc = integrateLevels(parent, child, prob, wIdx, fIdx, cumIdx, count);
@@ -2802,6 +2994,8 @@ inline int Instance::integrate(const int* parent, const int* child, const int* p
     rc = spanEnd();
     if (rc) return rc;
     postResultFlag();
+    // the matrices of the tip pairs the evaluation left unstored are copied behind the integration: nobody waits for that launch
+    if (snapPlan) { rc = flushSnapshot(); if (rc) return rc; }
     haveSite = true;
     derivValid = false;
     pendingResult = true;
@@ -2995,6 +3189,13 @@ inline int Instance::updatePrePartials(const BeagleOperation* ops, int n, int cu
         if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
         written[d] = 1;
     }
+    if (nUnstored) {                             // the post-order buffers the pass reads; what it writes holds no recipe afterwards
+        std::vector<int> reads;
+        for (int o = 0; o < n; ++o) { reads.push_back(ops[o].child1Partials); reads.push_back(ops[o].child2Partials); }
+        const int src = ensureStored(reads.data(), (int) reads.size());
+        if (src) return src;
+        for (int o = 0; o < n; ++o) dropRecipe(ops[o].destinationPartials);
+    }
     std::vector<PreOp> table((size_t) n);
     for (int o = 0; o < n; ++o) {
         const BeagleOperation& b = ops[o];
@@ -3049,6 +3250,8 @@ inline int Instance::ensurePosteriors()
     if (rc) return rc;
     rc = grow((void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double));
     if (rc) return rc;
+    rc = ensureStored(lastLnl.parent, lastLnl.child);
+    if (rc) return rc;
     DerivArgs a;
     rc = lnlOperands(a, lastLnl.parent, lastLnl.child, lastLnl.prob, lastLnl.weights, lastLnl.freqs, lastLnl.cum);
     if (rc) return rc;
@@ -3079,6 +3282,12 @@ inline int Instance::edgeGradient(const int* post, const int* pre, const int* dm
         if (dmat[e] < 0 || dmat[e] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
     }
     if (count <= 0) return BEAGLE_SUCCESS;
+    if (nUnstored) {
+        std::vector<int> reads(post, post + count);
+        reads.insert(reads.end(), pre, pre + count);
+        const int src = ensureStored(reads.data(), (int) reads.size());
+        if (src) return src;
+    }
     if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
     std::vector<GradEdge> table((size_t) count);
     for (int e = 0; e < count; ++e) {
@@ -3144,6 +3353,8 @@ inline int Instance::edgeDerivatives(int parent, int child, int prob, int d1, in
         HIP_TRY(hipHostGetDevicePointer((void**) &h_deriv_dev, h_deriv, 0));
     }
     lastLnl.remember(&parent, &child, &prob, &wIdx, &fIdx, &cumIdx, 1);
+    rc = ensureStored(parent, child);
+    if (rc) return rc;
     DerivArgs a;
     rc = lnlOperands(a, parent, child, prob, wIdx, fIdx, cumIdx);
     if (rc) return rc;
@@ -3348,6 +3559,12 @@ inline int Instance::finalPass(const MbamdFinalOperation* ops, int count)
         if (tipStates[b.destinationPartials]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdUpdateFinalPartials: the destination holds compact tip states");
         int rc = ensurePartials(b.destinationPartials);
         if (rc) return rc;
+        if (nUnstored) {
+            const int reads[3] = {b.downPartials, b.ancestorFinal, b.rootTip};
+            rc = ensureStored(reads, 3);
+            if (rc) return rc;
+            dropRecipe(b.destinationPartials);
+        }
         // the exponents of the final pass: written by the top node's launch, inherited by everything below it
         if (finalExpOf.size() != (size_t) nBuffers) finalExpOf.assign((size_t) nBuffers, nullptr);
         if (b.ancestorFinal < 0) {
@@ -3406,6 +3623,8 @@ inline int Instance::getScaledPartials(int idx, int cumIdx, float* out, float* o
     }
     const size_t total = (size_t) K * P * S;
     int rc = grow(&d_tmp, &tmpCap, (total + (size_t) Ppad) * sizeof(float));
+    if (rc) return rc;
+    rc = ensureStored(idx);
     if (rc) return rc;
     float* d_out = static_cast<float*>(d_tmp);
     float* d_ln = d_out + total;

@@ -57,6 +57,13 @@ namespace mbamd {
 #define MBAMD_W4_FWD2     0x02000000u
 #define MBAMD_W4_READS      0x00000200u  // (= ScaleMode SCALE_READ in [9:8]) this entry divides by stored exponents: they were fetched into the landing area
 #define MBAMD_W4_NEXT_READS 0x04000000u  // the NEXT entry of this wave is SCALE_READ: fetch its stored exponents now (4-state walk; set by the host)
+// A TIP PAIR (both children compact tips) of a whole-tree list on the plain instantiation: the 1 KiB result is NOT stored -- its parent reads
+// the LDS slot or the forwarding registers, and it is a pure function of 64 bytes of tip planes and two matrices: whoever needs it later has
+// it recomputed (the host keeps a recipe and a snapshot of the matrices, Instance::ensureStored).  Exponent byte, slot, cum_e: as ever.
+// Honoured by k_walk4_t<Walk4Args, true> only; the host sets it nowhere else.
+#define MBAMD_W4_NOSTORE  0x20000000u
+#define MBAMD_W4_NOSTORE_BIT 29
+static_assert(MBAMD_W4_NOSTORE == 1u << MBAMD_W4_NOSTORE_BIT, "the kernel tests the bit by its number");
 #define MBAMD_W4_RARE     (MBAMD_W4_NOP | MBAMD_W4_BARRIER | MBAMD_W4_PF0 | MBAMD_W4_VMWAIT | MBAMD_W4_READS | MBAMD_W4_NEXT_READS)
 // (Round 6: a ring of eight landing areas with the exponents requested six entries ahead was built on the hypothesis that the wait for
 //  the DMA is a wait for the previous entry's stores -- it was not the reason SCALE_READ evaluations were slow (the scratch row was,
@@ -67,7 +74,7 @@ namespace mbamd {
 // One step of a wave's program (wave-uniform; fetched with one s_load_dwordx8).  Addresses are ready-made byte
 // offsets from a base the wave computes once (scalar adds only, no multiplications in the loop).
 struct alignas(32) Walk4Entry {
-    uint32_t ctl;      // [7:0] flags   [9:8] ScaleMode   [15:10] vmwait   [23:16] slot that keeps the result (flag KEEP)   [25:24] FWD1 / FWD2   [26] NEXT_READS
+    uint32_t ctl;      // [7:0] flags   [9:8] ScaleMode   [15:10] vmwait   [23:16] slot that keeps the result (flag KEEP)   [25:24] FWD1 / FWD2   [26] NEXT_READS   [29] NOSTORE
     uint32_t dst;      // destination partials buffer: byte offset inside this wave's (block, category) column set
     uint32_t c1;       // child 1: tip -> byte offset of its 4 bitplanes inside the block's tip area; else LDS byte offset of its slot
     uint32_t c2;
@@ -107,6 +114,7 @@ struct Walk4Planes { uint64_t p[4]; };
 
 }  // namespace mbamd
 #include <mbamd_dev_walk4.h>     // Walk4Mat, walk4_load_* / walk4_tip_vector / walk4_dma* / walk4_wait_vm / walk4_barrier / walk4_matvec / ... (csrc/device/)
+#include <mbamd_dev_walk4_store.h>   // walk4_store_unless: the plain walk's store pair (csrc/device/)
 namespace mbamd {
 
 // the values walk4_wait_vm implements, for the host: the largest supported count <= n
@@ -255,7 +263,11 @@ k_walk4_t(ARGS AA)
             // (two stores, always: a branch around the second cost the SCALE_WRITE walk 5 % (call 31).  An entry that records no exponents writes its
             //  byte to one of MBAMD_W4_SCRATCH_ROWS scratch rows, in rotation: every entry of a SCALE_READ evaluation writing to ONE row
             //  made such an evaluation a third slower -- same-address stores, profiles/r06_scale_read.txt)
-            walk4_store(walk4_at_kib(P0, dst), walk4_at(E0, ewrite), lane, o, e);
+            // (PLAIN: a tip pair's partials stay out of HBM -- MBAMD_W4_NOSTORE: a wave-uniform branch around the first store, inside
+            //  the primitive.  As an `if` in this source it cost the loop its registers: the partials base went to a VGPR lane and came
+            //  back per entry behind an lgkmcnt(0) in front of the stores, profiles/walk4_tip_pairs.txt)
+            if constexpr (PLAIN) walk4_store_unless(walk4_at_kib(P0, dst), walk4_at(E0, ewrite), lane, o, e, ctl);
+            else walk4_store(walk4_at_kib(P0, dst), walk4_at(E0, ewrite), lane, o, e);
         }
         out = o;
     };
@@ -285,6 +297,21 @@ k_walk4_t(ARGS AA)
     }
 }
 
+// The matrices of a program's MBAMD_W4_NOSTORE entries -> the snapshot table float [buffer][2][K][16], slot = the entry's destination
+// buffer: what a recipe recomputes an unstored tip pair from, whatever the client does to the matrix buffers afterwards.  One workgroup
+// per entry of a single-wave program; `kibPerBuffer` = KiB of a partials buffer (the unit of Walk4Entry::dst).
+__global__ void __launch_bounds__(64)
+k_walk4_snapshot(const Walk4Entry* prog, unsigned kibPerBuffer, const float* matrices, float* snap, int K)
+{
+    const Walk4Entry* const e = prog + blockIdx.x;
+    if (!(e->ctl & MBAMD_W4_NOSTORE)) return;
+    const unsigned n = (unsigned) K * 16u;
+    float* const dst = snap + (size_t) (e->dst / kibPerBuffer) * 2u * n;
+    for (unsigned i = threadIdx.x; i < 2u * n; i += 64u) {
+        const unsigned c = i / n, j = i - c * n;
+        dst[i] = matrices[(size_t) ((c ? e->m2 : e->m1) >> 2) + j];
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // k_path4 -- a ROOT-WARD PATH (round 5): the list of a move that dirtied one branch.  Every operation has the previous result as one
