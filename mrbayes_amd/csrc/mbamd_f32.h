@@ -1759,6 +1759,13 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                 if (tn.op >= 0 && seg[tn.op].scaleWrite < 0 && seg[tn.op].scaleRead >= 0) flags |= MBAMD_W4_NEXT_READS;
             }
             e.ctl = flags | (mode << 8) | ((uint32_t) (te.vmwait == 0xFF ? 0 : te.vmwait) << 10) | (keep << 16);
+            // a segment for the plain kernel: every operation says once what pair of child kinds it is (MBAMD_W4_KIND_*: the loop body it
+            // runs in), and every entry -- the read-ahead tail included -- carries child 1's "plane offset or 0" ready-made in `eread`,
+            // which nothing else reads in such a program (no entry divides by stored exponents)
+            if (sg.plain) {
+                if (te.op >= 0) e.ctl |= walk4_kind_of(flags);
+                e.eread = (flags & MBAMD_W4_TIP1) ? e.c1 : 0u;
+            }
         }
         lastWalkW = t.W; lastWalkSlots = t.nslots; lastWalkEntries = t.entries; lastWalkPhases = t.phases;
         seg.clear();

@@ -64,6 +64,31 @@ namespace mbamd {
 #define MBAMD_W4_NOSTORE  0x20000000u
 #define MBAMD_W4_NOSTORE_BIT 29
 static_assert(MBAMD_W4_NOSTORE == 1u << MBAMD_W4_NOSTORE_BIT, "the kernel tests the bit by its number");
+// The PAIR OF CHILD KINDS of an operation entry in a plan that runs on the plain instantiation, set by the host beside TIP / FWD (which
+// stay what they are: the generic kernel, k_walk4_snapshot and the emulation read those).  A child is a compact tip, the forwarded
+// result or an LDS slot, and the scheduler forwards the last interior child of every operation, so five pairs make up a whole-tree
+// list; each has a body of its own in k_walk4_t<Walk4Args, true>, everything else (the same buffer as both children, two slots,
+// ...) runs the general one, which tests TIP / FWD as the generic kernel does.  The number is ONE bit of [15:10] -- the wait count,
+// which a plain program does not have -- and the bit of its GROUP (27, 28, 30): the kernel's dispatch is wave-uniform `if`s without
+// `else` (two scalar instructions each; every `else` costs the compiler three more, profiles/walk4_kinds.txt), three groups on every
+// entry and two members inside the entry's own.  Honoured by the plain instantiation only (27 / 28 are START / JOIN in a k_path4
+// program); an operation the host did not mark would compute nothing there: Instance::buildWalk marks every one.
+#define MBAMD_W4_GROUP_FWD2    0x08000000u   // child 2 is the forwarded result: (tip, fwd) (slot, fwd)
+#define MBAMD_W4_GROUP_FWD1    0x10000000u   // child 1 is: (fwd, tip) (fwd, slot)
+#define MBAMD_W4_GROUP_OTHER   0x40000000u   // neither: (tip, tip), general
+#define MBAMD_W4_IS_TIP_TIP    0x00000400u
+#define MBAMD_W4_IS_TIP_FWD    0x00000800u
+#define MBAMD_W4_IS_FWD_TIP    0x00001000u
+#define MBAMD_W4_IS_SLOT_FWD   0x00002000u
+#define MBAMD_W4_IS_FWD_SLOT   0x00004000u
+#define MBAMD_W4_IS_GENERAL    0x00008000u
+#define MBAMD_W4_KIND_TIP_TIP  (MBAMD_W4_GROUP_OTHER | MBAMD_W4_IS_TIP_TIP)
+#define MBAMD_W4_KIND_TIP_FWD  (MBAMD_W4_GROUP_FWD2 | MBAMD_W4_IS_TIP_FWD)
+#define MBAMD_W4_KIND_FWD_TIP  (MBAMD_W4_GROUP_FWD1 | MBAMD_W4_IS_FWD_TIP)
+#define MBAMD_W4_KIND_SLOT_FWD (MBAMD_W4_GROUP_FWD2 | MBAMD_W4_IS_SLOT_FWD)
+#define MBAMD_W4_KIND_FWD_SLOT (MBAMD_W4_GROUP_FWD1 | MBAMD_W4_IS_FWD_SLOT)
+#define MBAMD_W4_KIND_GENERAL  (MBAMD_W4_GROUP_OTHER | MBAMD_W4_IS_GENERAL)
+#define MBAMD_W4_KIND_MASK     0x5800FC00u
 #define MBAMD_W4_RARE     (MBAMD_W4_NOP | MBAMD_W4_BARRIER | MBAMD_W4_PF0 | MBAMD_W4_VMWAIT | MBAMD_W4_READS | MBAMD_W4_NEXT_READS)
 // (Round 6: a ring of eight landing areas with the exponents requested six entries ahead was built on the hypothesis that the wait for
 //  the DMA is a wait for the previous entry's stores -- it was not the reason SCALE_READ evaluations were slow (the scratch row was,
@@ -74,7 +99,7 @@ static_assert(MBAMD_W4_NOSTORE == 1u << MBAMD_W4_NOSTORE_BIT, "the kernel tests 
 // One step of a wave's program (wave-uniform; fetched with one s_load_dwordx8).  Addresses are ready-made byte
 // offsets from a base the wave computes once (scalar adds only, no multiplications in the loop).
 struct alignas(32) Walk4Entry {
-    uint32_t ctl;      // [7:0] flags   [9:8] ScaleMode   [15:10] vmwait   [23:16] slot that keeps the result (flag KEEP)   [25:24] FWD1 / FWD2   [26] NEXT_READS   [29] NOSTORE
+    uint32_t ctl;      // [7:0] flags   [9:8] ScaleMode   [15:10] vmwait   [23:16] slot that keeps the result (flag KEEP)   [25:24] FWD1 / FWD2   [26] NEXT_READS   [29] NOSTORE   [30] [28:27] [15:10] pair of child kinds (plain plans: MBAMD_W4_KIND_*)
     uint32_t dst;      // destination partials buffer: byte offset inside this wave's (block, category) column set
     uint32_t c1;       // child 1: tip -> byte offset of its 4 bitplanes inside the block's tip area; else LDS byte offset of its slot
     uint32_t c2;
@@ -115,6 +140,7 @@ struct Walk4Planes { uint64_t p[4]; };
 }  // namespace mbamd
 #include <mbamd_dev_walk4.h>     // Walk4Mat, walk4_load_* / walk4_tip_vector / walk4_dma* / walk4_wait_vm / walk4_barrier / walk4_matvec / ... (csrc/device/)
 #include <mbamd_dev_walk4_store.h>   // walk4_store_unless: the plain walk's store pair (csrc/device/)
+#include <mbamd_dev_walk4_kinds.h>   // walk4_product: behind the plain walk's per-kind bodies (csrc/device/)
 namespace mbamd {
 
 // the values walk4_wait_vm implements, for the host: the largest supported count <= n
@@ -125,6 +151,24 @@ __host__ __device__ inline unsigned walk4_round_wait(long n)
     for (unsigned v : ok) if ((long) v <= n) r = v;
     return r;
 }
+
+// the kind number of an operation entry's flags (the host, for plans on the plain instantiation)
+__host__ __device__ inline uint32_t walk4_kind_of(uint32_t flags)
+{
+    const bool t1 = (flags & MBAMD_W4_TIP1) != 0, t2 = (flags & MBAMD_W4_TIP2) != 0;
+    const bool f1 = !t1 && (flags & MBAMD_W4_FWD1) != 0, f2 = !t2 && (flags & MBAMD_W4_FWD2) != 0;
+    const bool s1 = !t1 && !f1, s2 = !t2 && !f2;
+    if (t1 && t2) return MBAMD_W4_KIND_TIP_TIP;
+    if (t1 && f2) return MBAMD_W4_KIND_TIP_FWD;
+    if (f1 && t2) return MBAMD_W4_KIND_FWD_TIP;
+    if (s1 && f2) return MBAMD_W4_KIND_SLOT_FWD;
+    if (f1 && s2) return MBAMD_W4_KIND_FWD_SLOT;
+    return MBAMD_W4_KIND_GENERAL;
+}
+// what a loop body of the plain instantiation knows about a child at compile time
+enum { W4K_ANY = 0, W4K_TIP = 1, W4K_FWD = 2, W4K_SLOT = 3 };
+template <int V> struct Walk4Kind { static constexpr int value = V; };
+struct Walk4Factors { f4 f1, f2; };          // M1 a and M2 b: the entry's result is their element-wise product, rescaled
 
 // byte-offset addressing helpers (wave-uniform base + 32-bit offset: two scalar adds)
 // (partials: the arena is BUFFER-major -- a buffer is P_pad/64 x K KiB, up to several MB -- and the entries hold its offset in KiB)
@@ -202,6 +246,7 @@ k_walk4_t(ARGS AA)
     // inputs of entry 0
     Walk4Mat M1 = walk4_load_matrix(walk4_at(M0, DA.m1));
     Walk4Mat M2 = walk4_load_matrix(walk4_at(M0, DA.m2));
+    static_assert(MBAMD_W4_TIP2 == 1u << 6, "the plain loop masks child 2's plane offset with ctl bit 6");
     Walk4Planes T1 = walk4_load_planes(walk4_at(T0, (DA.ctl & MBAMD_W4_TIP1) ? DA.c1 : 0u));
     Walk4Planes T2 = walk4_load_planes(walk4_at(T0, (DA.ctl & MBAMD_W4_TIP2) ? DA.c2 : 0u));
     if constexpr (!PLAIN) { if (DA.ctl & MBAMD_W4_READS) MBAMD_W4_EXPS(DA.eread, 0); }
@@ -216,6 +261,35 @@ k_walk4_t(ARGS AA)
     // next one, and cur's registers receive entry j + 2.  ALL scalar loads of an iteration (next entry's matrices and tip
     // planes, the entry after next) are issued in one burst as soon as this entry's matrix products are done, and are
     // consumed after the next iteration's LDS reads: one lgkmcnt(0) per iteration covers both.
+    // The two factors of an entry's product: both children fetched, the two matrix-vector products.  `k1` / `k2` say at
+    // compile time what child 1 / 2 is (Walk4Kind<W4K_TIP / W4K_FWD / W4K_SLOT>): a slot child's LDS read goes first, a forwarded child
+    // is `prev` itself (no copy), a tip child is four v_cndmask_b32, and nothing tests TIP or FWD.  Walk4Kind<W4K_ANY> tests the entry's
+    // flags: the general form, and the only one of the generic instantiations.
+    auto factors = [&](auto k1, auto k2, const Walk4Entry& cur, const f4& prev) {
+        constexpr int C1 = decltype(k1)::value, C2 = decltype(k2)::value;
+        const unsigned ctl = cur.ctl;
+        f4 a, b;
+        if constexpr (C1 == W4K_SLOT) a = *reinterpret_cast<const f4*>(slots + cur.c1);
+        if constexpr (C2 == W4K_SLOT) b = *reinterpret_cast<const f4*>(slots + cur.c2);
+        if constexpr (C1 == W4K_TIP) a = walk4_tip_vector(T1, lane);
+        if constexpr (C1 == W4K_FWD) a = prev;
+        if constexpr (C1 == W4K_ANY) {
+            if (ctl & MBAMD_W4_TIP1) a = walk4_tip_vector(T1, lane);
+            else if (ctl & MBAMD_W4_FWD1) a = prev;
+            else a = *reinterpret_cast<const f4*>(slots + cur.c1);
+        }
+        if constexpr (C2 == W4K_TIP) b = walk4_tip_vector(T2, lane);
+        if constexpr (C2 == W4K_FWD) b = prev;
+        if constexpr (C2 == W4K_ANY) {
+            if (ctl & MBAMD_W4_TIP2) b = walk4_tip_vector(T2, lane);
+            else if (ctl & MBAMD_W4_FWD2) b = prev;
+            else b = *reinterpret_cast<const f4*>(slots + cur.c2);
+        }
+        Walk4Factors f;
+        f.f1 = walk4_matvec(M1, a);
+        f.f2 = walk4_matvec(M2, b);
+        return f;
+    };
     auto step = [&](Walk4Entry& cur, const Walk4Entry& nxt, const Walk4Entry* after, int parity, f4& out, const f4& prev) {
         const unsigned ctl = cur.ctl;
         int er = 0;
@@ -231,25 +305,48 @@ k_walk4_t(ARGS AA)
             if (ctl & MBAMD_W4_READS) er = stage[64 * parity + lane];
         }
         f4 o = prev;                                   // (a no-op entry passes the result of the operation executed last through)
-        if (PLAIN || !(ctl & MBAMD_W4_NOP)) {
-            f4 a, b;
-            if (ctl & MBAMD_W4_TIP1) a = walk4_tip_vector(T1, lane);
-            else if (ctl & MBAMD_W4_FWD1) a = prev;
-            else a = *reinterpret_cast<const f4*>(slots + cur.c1);
-            if (ctl & MBAMD_W4_TIP2) b = walk4_tip_vector(T2, lane);
-            else if (ctl & MBAMD_W4_FWD2) b = prev;
-            else b = *reinterpret_cast<const f4*>(slots + cur.c2);
-            const f4 f1 = walk4_matvec(M1, a);
-            const f4 f2 = walk4_matvec(M2, b);
-            o.x = f1.x * f2.x; o.y = f1.y * f2.y; o.z = f1.z * f2.z; o.w = f1.w * f2.w;
+        Walk4Factors f;
+        constexpr Walk4Kind<W4K_ANY> any{};
+        if constexpr (PLAIN) {
+            // ONE dispatch per entry, on the kind number the host gave it (MBAMD_W4_KIND_*): a body per pair of child kinds that a
+            // whole-tree list is made of, the general one for everything else -- `if`s without `else`: three groups, two members in
+            // the entry's own.  What follows the factors -- their product, the scalar burst, the rescaling, the KEEP write, the stores
+            // -- is one copy for all of them: with the burst inside every body the loop's 56 loaded scalar registers met in different
+            // registers at the bodies' end (387 SGPR spills, profiles/walk4_kinds.txt)
+            constexpr Walk4Kind<W4K_TIP> tip{};
+            constexpr Walk4Kind<W4K_FWD> fwd{};
+            constexpr Walk4Kind<W4K_SLOT> slot{};
+            if (ctl & MBAMD_W4_GROUP_FWD2) {
+                if (ctl & MBAMD_W4_IS_TIP_FWD) f = factors(tip, fwd, cur, prev);
+                if (ctl & MBAMD_W4_IS_SLOT_FWD) f = factors(slot, fwd, cur, prev);
+            }
+            if (ctl & MBAMD_W4_GROUP_FWD1) {
+                if (ctl & MBAMD_W4_IS_FWD_TIP) f = factors(fwd, tip, cur, prev);
+                if (ctl & MBAMD_W4_IS_FWD_SLOT) f = factors(fwd, slot, cur, prev);
+            }
+            if (ctl & MBAMD_W4_GROUP_OTHER) {
+                if (ctl & MBAMD_W4_IS_TIP_TIP) f = factors(tip, tip, cur, prev);
+                if (ctl & MBAMD_W4_IS_GENERAL) f = factors(any, any, cur, prev);
+            }
+        } else {
+            if (!(ctl & MBAMD_W4_NOP)) f = factors(any, any, cur, prev);
         }
+        if constexpr (PLAIN) o = walk4_product(f.f1, f.f2);
+        else if (!(ctl & MBAMD_W4_NOP)) { o.x = f.f1.x * f.f2.x; o.y = f.f1.y * f.f2.y; o.z = f.f1.z * f.f2.z; o.w = f.f1.w * f.f2.w; }
         // the scalar-load burst for the next entry (the registers of this entry's matrices / planes are free now); a
         // child that is not a tip reads the planes at offset 0 -- a valid address, the value is not used
         const unsigned dst = cur.dst, ewrite = cur.ewrite;
         M1 = walk4_load_matrix(walk4_at(M0, nxt.m1));
         M2 = walk4_load_matrix(walk4_at(M0, nxt.m2));
-        T1 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP1) ? nxt.c1 : 0u));
-        T2 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP2) ? nxt.c2 : 0u));
+        if constexpr (PLAIN) {
+            // (child 1's "plane offset or 0" comes ready-made in `eread`, which a plain program has no other use for; child 2's is a mask,
+            //  not a select: as a select its condition was kept as a boolean for the next entry's general body, two more scalar instructions)
+            T1 = walk4_load_planes(walk4_at(T0, nxt.eread));
+            T2 = walk4_load_planes(walk4_at(T0, nxt.c2 & (unsigned) ((int) (nxt.ctl << 25) >> 31)));
+        } else {
+            T1 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP1) ? nxt.c1 : 0u));
+            T2 = walk4_load_planes(walk4_at(T0, (nxt.ctl & MBAMD_W4_TIP2) ? nxt.c2 : 0u));
+        }
         cur = walk4_load_entry(after);
         if (PLAIN || !(ctl & MBAMD_W4_NOP)) {
             // SCALE_WRITE: this column's own power of two; SCALE_READ (rare path): the stored one; else 2^0 (exact: no branch)
