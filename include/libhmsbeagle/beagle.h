@@ -331,6 +331,28 @@ BEAGLE_DLLEXPORT int beagleCalculateEdgeDerivatives(int instance, const int* pos
                                                     int count, double* outDerivatives, double* outSumDerivatives,
                                                     double* outSumSquaredDerivatives);
 
+/* The gradient in the rate matrix (upstream's name and argument order): the S x S cross-product matrix a client contracts with
+ * dQ / d theta.  Edge e = 0 .. count-1 names postBufferIndices[e] and preBufferIndices[e] exactly as
+ * beagleCalculateEdgeDerivatives does (a post-order buffer may hold partials or compact tip states: a tip is its indicator
+ * vector, a missing state the vector of ones).  outSumDerivatives holds stateCount * stateCount doubles, row-major [i * S + j],
+ * row i the state on the pre-order side ("from"), column j the state on the post-order side ("to"); it is OVERWRITTEN:
+ *     den_e,k(c) = sum_l pre_e[k,c,l] post_e[k,c,l]
+ *     X[i,j]     = sum_e t_e sum_c weight_c sum_k q_k(c) r_k pre_e[k,c,i] post_e[k,c,j] / den_e,k(c)
+ * with t_e = edgeLengths[e], r_k the category rates of categoryRateIndices[e] (beagleSetCategoryRates[WithIndex]), q_k(c) the
+ * posterior category probabilities of beagleCalculateEdgeDerivatives (1 with one category) and weight_c the pattern weights.  A
+ * category whose den is not positive has underflowed and is skipped.  Every scale factor of either buffer cancels per (pattern,
+ * category).  This is upstream's quantity: sum_ij X[i,j] M[i,j] is exactly d lnL / d epsilon for Q -> Q + epsilon M whenever M
+ * commutes with Q (M = Q gives sum_e t_e d lnL / d t_e), and upstream's approximation otherwise.
+ * outSumSquaredDerivatives must be NULL (BEAGLE_ERROR_NO_IMPLEMENTATION otherwise: upstream's implementations do not fill it
+ * either); not served on a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).  With more than one category the rules of
+ * beagleCalculateEdgeDerivatives on the latest log-likelihood call and on categoryWeightsIndices hold.  A pre index that is no
+ * pre-order buffer, an invalid post buffer, an unknown rates index, a NULL array, an edge length that is negative or not finite:
+ * BEAGLE_ERROR_OUT_OF_RANGE.  count == 0 writes zeros.  The call is synchronous. */
+BEAGLE_DLLEXPORT int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                                           const int* categoryRateIndices, const int* categoryWeightsIndices,
+                                                           const double* edgeLengths, int count, double* outSumDerivatives,
+                                                           double* outSumSquaredDerivatives);
+
 /* ---------------------------------------------------------------------------------------------
  * engine extensions (not part of the upstream API; used by bench.py / the multi-GPU driver)
  * ------------------------------------------------------------------------------------------- */

@@ -63,7 +63,7 @@ EXPORTS = [
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
-    "beagleCalculateEdgeDerivatives", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -148,6 +148,7 @@ class BeagleLibrary:
         L.beagleUpdatePrePartials.argtypes = [C.c_int, C.POINTER(BeagleOperation), C.c_int, C.c_int]
         L.beagleSetDifferentialMatrix.argtypes = [C.c_int, C.c_int, _dp]
         L.beagleCalculateEdgeDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp]
+        L.beagleCalculateCrossProductDerivative.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -407,6 +408,20 @@ class BeagleInstance:
                                                      sums.ctypes.data_as(_dp), sq.ctypes.data_as(_dp))
         self._chk(rc, "beagleCalculateEdgeDerivatives")
         return rc, per, sums, sq
+
+    def calculate_cross_products(self, posts, pres, rates, weights, edge_lengths, squared=False):
+        """The cross-product matrix of the gradient in the rate matrix over every listed branch in one call
+        (beagleCalculateCrossProductDerivative).  Returns (rc, X [states][states]), row = the state on the pre-order side; an error
+        code raises.  squared=True passes a buffer for the sums of squares, which the engine refuses."""
+        po, pr, ra, w, t = _i(posts), _i(pres), _i(rates), _i(weights), _d(edge_lengths)
+        n, S = len(po), self.state_count
+        x = np.empty((S, S))
+        sq = np.empty((S, S)) if squared else None
+        rc = self.lib.beagleCalculateCrossProductDerivative(self.id, po.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), ra.ctypes.data_as(_ip),
+                                                            w.ctypes.data_as(_ip), t.ctypes.data_as(_dp), n, x.ctypes.data_as(_dp),
+                                                            sq.ctypes.data_as(_dp) if squared else None)
+        self._chk(rc, "beagleCalculateCrossProductDerivative")
+        return rc, x
 
     # ---- BEAGLE v3: multi-partition instances (reference src/mbbeagle.c:1500-3010) -------------------------------
     def child_count(self) -> int:

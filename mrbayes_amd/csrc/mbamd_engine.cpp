@@ -1011,6 +1011,36 @@ int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, c
     return BEAGLE_SUCCESS;
 }
 
+// the cross-product matrix of the gradient in the rate matrix (mbamd_crossproducts.h; semantics: beagle.h)
+int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryRateIndices,
+                                          const int* categoryWeightsIndices, const double* edgeLengths, int count, double* outSumDerivatives,
+                                          double* outSumSquaredDerivatives)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("beagleCalculateCrossProductDerivative(count=%d)", count);
+    const char* const who = "beagleCalculateCrossProductDerivative";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (outSumSquaredDerivatives) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "outSumSquaredDerivatives must be NULL (a per-pattern square is an S x S matrix per pattern)");
+    if (count < 0 || !outSumDerivatives ||
+        (count > 0 && (!postBufferIndices || !preBufferIndices || !categoryRateIndices || !categoryWeightsIndices || !edgeLengths)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null array");
+    if (h->f64)
+        return h->f64->crossProducts(postBufferIndices, preBufferIndices, categoryRateIndices, categoryWeightsIndices, edgeLengths, count, outSumDerivatives);
+    // pattern shards: the children's matrices are added, in child order
+    const size_t SS = (size_t) h->dim.stateCount * h->dim.stateCount;
+    std::vector<double> sum(SS, 0.0), part(SS);
+    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span&) -> int {
+        const int crc = c->crossProducts(postBufferIndices, preBufferIndices, categoryRateIndices, categoryWeightsIndices, edgeLengths, count, part.data());
+        if (crc) return crc;
+        for (size_t ij = 0; ij < SS; ++ij) sum[ij] += part[ij];
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    std::copy(sum.begin(), sum.end(), outSumDerivatives);
+    return BEAGLE_SUCCESS;
+}
+
 // ---- engine extensions ---------------------------------------------------------------------
 int mbamdSynchronize(int instance)
 {

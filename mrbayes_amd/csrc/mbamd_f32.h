@@ -17,6 +17,7 @@
 #include "mbamd_kernels_mfma.h"
 #include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient: the pre-order pass and the gradient in all branch lengths
+#include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 
 namespace mbamd {
 
@@ -163,6 +164,8 @@ struct Instance {
     int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
     int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
                      double* sums, double* sumsSq);
+    // crossProducts (beagleCalculateCrossProductDerivative on this engine's patterns): synchronous; out[S * S] is overwritten
+    int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -3343,6 +3346,81 @@ inline int Instance::edgeGradient(const int* post, const int* pre, const int* dm
             if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
         }
     }
+    return BEAGLE_SUCCESS;
+}
+
+// beagleCalculateCrossProductDerivative on this engine's patterns (mbamd_crossproducts.h): the edge table -- GradEdge and, behind
+// the edges, t_e r_k as doubles -- goes to d_preTable; the edges are cut into chunks (cross_chunks), one launch (the plain kernel
+// beyond 256 entries: one per 256) leaves a matrix per (block, chunk) in d_tmp, k_cross_product_sums adds them and S * S doubles
+// come back.
+inline int Instance::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
+{
+    const char* const who = "beagleCalculateCrossProductDerivative";
+    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
+    if (K > 1) {
+        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
+        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
+    }
+    for (int e = 0; e < count; ++e) {
+        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
+        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
+        if (post[e] < 0 || post[e] >= nBuffers || (!tipStates[post[e]] && !valid[post[e]])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
+        if (!rateSets.has(rateIdx[e])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category rates index");
+    }
+    { const int lrc = cross_check_lengths(who, lengths, count); if (lrc) return lrc; }
+    const size_t SS = (size_t) S * S;
+    std::fill_n(out, SS, 0.0);
+    if (count <= 0) return BEAGLE_SUCCESS;
+    if (nUnstored) {
+        std::vector<int> reads(post, post + count);
+        reads.insert(reads.end(), pre, pre + count);
+        const int src = ensureStored(reads.data(), (int) reads.size());
+        if (src) return src;
+    }
+    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
+    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
+    std::vector<unsigned char> table(edgeBytes + (size_t) count * K * sizeof(double), 0);
+    GradEdge* const te = reinterpret_cast<GradEdge*>(table.data());
+    double* const tr = reinterpret_cast<double*>(table.data() + edgeBytes);
+    for (int e = 0; e < count; ++e) {
+        te[e].pre = partials[pre[e]];
+        te[e].postTip = tipStates[post[e]] ? 1 : 0;
+        te[e].post = tipStates[post[e]] ? (const void*) tipStates[post[e]] : (const void*) partials[post[e]];
+        for (int k = 0; k < K; ++k) tr[(size_t) e * K + k] = lengths[e] * rateSets[rateIdx[e]].r[k];
+    }
+    int rc = grow(&d_preTable, &preTableCap, table.size());
+    if (rc) return rc;
+    rc = upload(d_preTable, table.data(), table.size());
+    if (rc) return rc;
+    const int nb = Ppad / 64;
+    const int chunks = cross_chunks(count, nb, S);
+    rc = grow(&d_tmp, &tmpCap, ((size_t) chunks * nb + 1) * SS * sizeof(double));
+    if (rc) return rc;
+    CrossArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.g = layoutArgs();
+    a.edges = static_cast<const GradEdge*>(d_preTable);
+    a.tr = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_preTable) + edgeBytes);
+    a.q = K > 1 ? d_q : nullptr;
+    a.pattern_weights = d_pweights;
+    a.partial = static_cast<double*>(d_tmp);
+    a.nb = nb;
+    a.edgeCount = count;
+    a.perChunk = (count + chunks - 1) / chunks;
+    const int used = (count + a.perChunk - 1) / a.perChunk;          // (the last chunks may be empty: not launched)
+    double* const d_out = a.partial + (size_t) used * nb * SS;
+    const bool mfma = S >= 16 && S <= 64 && !sw.xprodGeneric;
+    int launches;
+    if (s4) launches = launch_cross_products<DERIV_S4, float>(stream, a, used, false);
+    else if (wg) launches = launch_cross_products<DERIV_WG, float>(stream, a, used, mfma);
+    else launches = launch_cross_products<DERIV_LEVELS, float>(stream, a, used, mfma);
+    MBAMD_LAUNCH(k_cross_product_sums, (unsigned) SS, 64, 0, stream, (const double*) a.partial, used * nb, (int) SS, d_out);
+    HIP_TRY(hipGetLastError());
+    pendingLaunches += launches + 1;
+    HIP_TRY(hipStreamSynchronize(stream));
+    syncedClock = launchClock;
+    HIP_TRY(hipMemcpy(out, d_out, SS * sizeof(double), hipMemcpyDeviceToHost));
     return BEAGLE_SUCCESS;
 }
 

@@ -29,6 +29,7 @@
 #include "mbamd_walk4_host.h"    // Walk4Builder: the program compiler of the four-state walk
 #include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient <DERIV_F64, double>: the pre-order pass and the gradient in all branch lengths
+#include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
 
 namespace mbamd {
 
@@ -83,6 +84,7 @@ public:
     // engine: one launch per group of independent operations; the gradient call is synchronous.
     int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
     int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq);
+    int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -1355,6 +1357,64 @@ inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dm
             if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
         }
     }
+    return BEAGLE_SUCCESS;
+}
+// beagleCalculateCrossProductDerivative (mbamd_crossproducts.h), as Instance's: the plain kernel in double precision
+inline int Engine64::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
+{
+    const char* const who = "beagleCalculateCrossProductDerivative";
+    { const int rcq = flushQueue(); if (rcq) return rcq; }
+    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (K > 1) {
+        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
+        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
+    }
+    for (int e = 0; e < count; ++e) {
+        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
+        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
+        if (post[e] < 0 || post[e] >= nBuffers || !valid[post[e]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
+        if (!rateSets.has(rateIdx[e])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category rates index");
+    }
+    { const int lrc = cross_check_lengths(who, lengths, count); if (lrc) return lrc; }
+    const size_t SS = (size_t) S * S;
+    std::fill_n(out, SS, 0.0);
+    if (count <= 0) return BEAGLE_SUCCESS;
+    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
+    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
+    std::vector<unsigned char> table(edgeBytes + (size_t) count * K * sizeof(double), 0);
+    GradEdge* const te = reinterpret_cast<GradEdge*>(table.data());
+    double* const tr = reinterpret_cast<double*>(table.data() + edgeBytes);
+    for (int e = 0; e < count; ++e) {
+        te[e].pre = partialsPtr(pre[e]);
+        te[e].postTip = isTip[post[e]] ? 1 : 0;
+        te[e].post = isTip[post[e]] ? (const void*) statesPtr(post[e]) : (const void*) partialsPtr(post[e]);
+        for (int k = 0; k < K; ++k) tr[(size_t) e * K + k] = lengths[e] * rateSets[rateIdx[e]].r[k];
+    }
+    void* d_table = nullptr;
+    { const int rc = stage(table.data(), table.size(), &d_table); if (rc) return rc; }
+    const int nb = Ppad / 64;
+    const int chunks = cross_chunks(count, nb, S);
+    { const size_t bytes = ((size_t) chunks * nb + 1) * SS * sizeof(double); const int rc = grow_device(stream, (void**) &d_grad, &gradCap, bytes, bytes); if (rc) return rc; }
+    CrossArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.g = layoutArgs();
+    a.edges = static_cast<const GradEdge*>(d_table);
+    a.tr = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_table) + edgeBytes);
+    a.q = K > 1 ? d_q : nullptr;
+    a.pattern_weights = d_pweights;
+    a.partial = d_grad;
+    a.nb = nb;
+    a.edgeCount = count;
+    a.perChunk = (count + chunks - 1) / chunks;
+    const int used = (count + a.perChunk - 1) / a.perChunk;          // (the last chunks may be empty: not launched)
+    double* const d_out = d_grad + (size_t) used * nb * SS;
+    const int launches = launch_cross_products<DERIV_F64, double>(stream, a, used, false);
+    MBAMD_LAUNCH(k_cross_product_sums, (unsigned) SS, 64, 0, stream, (const double*) d_grad, used * nb, (int) SS, d_out);
+    HIP_TRY(hipGetLastError());
+    preLaunches += (uint64_t) launches + 1;
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(out, d_out, SS * sizeof(double), hipMemcpyDeviceToHost));
     return BEAGLE_SUCCESS;
 }
 inline int Engine64::getSites(double* out)

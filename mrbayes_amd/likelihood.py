@@ -408,14 +408,12 @@ class BeagleDivision:
             level = below
         return np.asarray(ops, dtype=np.int32)
 
-    def BranchGradient(self, chain=0, sites=False):
-        """{node: d lnL / d t_node} for all 2N-3 branches of the chain's current tree, after LogLike: the start vector
-        pi_i tip_root[c,i] and D_k = r_k Q are set, the pre-order list of the whole tree is issued and ONE
-        calculate_edge_gradient call reads every branch.  sites=True: (that, {node: per-site derivatives})."""
+    def _PreOrderPass(self, chain, who):
+        """the start vector pi_i tip_root[c,i], then the pre-order list of the whole tree"""
         if not self.pre_order:
-            raise ValueError("BranchGradient needs BeagleDivision(..., pre_order=True)")
+            raise ValueError(who + " needs BeagleDivision(..., pre_order=True)")
         if self.step != 1:
-            raise NotImplementedError("BranchGradient: one eigen-system part per division")
+            raise NotImplementedError(who + ": one eigen-system part per division")
         d, t = self.div, self.div.tree
         S, K, P = d.nstates, d.ncat, d.npatterns
         tip = np.ones((P, S))
@@ -428,15 +426,34 @@ class BeagleDivision:
             tip = np.asarray(d.tip_partials[t.root], dtype=np.float64).reshape(P, S)
         start = tip * np.asarray(d.pi, dtype=np.float64)[None, :]
         self.inst.set_partials(self.preOrderStartIndex, np.broadcast_to(start, (K, P, S)))
+        self.inst.update_pre_partials(self.PreOrderOperations(chain))
+
+    def BranchGradient(self, chain=0, sites=False):
+        """{node: d lnL / d t_node} for all 2N-3 branches of the chain's current tree, after LogLike: the start vector
+        pi_i tip_root[c,i] and D_k = r_k Q are set, the pre-order list of the whole tree is issued and ONE
+        calculate_edge_gradient call reads every branch.  sites=True: (that, {node: per-site derivatives})."""
+        self._PreOrderPass(chain, "BranchGradient")
+        d, t = self.div, self.div.tree
         es = d.eigen[0]
         q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
         self.inst.set_differential_matrix(self.diffMatrixIndex, np.asarray(d.cat_rates, dtype=np.float64)[:, None, None] * q[None, :, :])
-        self.inst.update_pre_partials(self.PreOrderOperations(chain))
         nodes = list(t.all_down_pass)
         rc, per, sums, _ = self.inst.calculate_edge_gradient([self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes],
                                                              [self.diffMatrixIndex] * len(nodes), [self.cijkIndex[chain]] * len(nodes), sites=sites)
         grad = {n: float(sums[i]) for i, n in enumerate(nodes)}
         return (grad, {n: per[i] for i, n in enumerate(nodes)}) if sites else grad
+
+    def RateMatrixCrossProducts(self, chain=0):
+        """X [S][S], the cross-product matrix of the gradient in the rate matrix, for the chain's current tree after LogLike: the same
+        steps as BranchGradient (start vector, pre-order list of the whole tree), then ONE calculate_cross_products call over all
+        2N-3 branches with their current lengths.  sum_ij X[i,j] dQ[i,j] / d theta is the gradient in a rate-matrix parameter."""
+        t = self.div.tree
+        self._PreOrderPass(chain, "RateMatrixCrossProducts")
+        nodes = list(t.all_down_pass)
+        lengths = [min(max(t.length[n], BRLENS_MIN), BRLENS_MAX) for n in nodes]
+        _, x = self.inst.calculate_cross_products([self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes],
+                                                  [0] * len(nodes), [self.cijkIndex[chain]] * len(nodes), lengths)
+        return x
 
     def LogLike(self, chain=0):
         """One full evaluation of a chain from its current dirty flags; clears them afterwards."""

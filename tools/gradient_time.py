@@ -1,9 +1,16 @@
 """Wall time of one whole branch-length gradient -- the pre-order list of the tree plus ONE beagleCalculateEdgeDerivatives call over
 all 2N-3 branches without per-site values -- at a BASELINE shape, next to the full-tree evaluation of the same run and a byte model
 (DESIGN 4.4.2).  usage: gradient_time.py [case] [repeats]   (MBAMD_LIBRARY selects the library)
+A case is a name under tests/golden or kind:taxa:patterns:categories, a synthetic division (gen61:100:5000:3 is the shape of the codon
+workload with its three classes as rate categories: the golden codon case keeps them as three eigen-systems, which the gradient calls
+do not serve).
 
 The byte model: a pre-order operation reads two partials buffers and writes one, the derivative call reads two per branch, a
-buffer is 4 S bytes per (pattern, category); divided by 8 TB/s."""
+buffer is 4 S bytes per (pattern, category); divided by 8 TB/s.
+
+A second line times ONE beagleCalculateCrossProductDerivative call over the same branches (the gradient in the rate matrix, DESIGN
+4.4.3; MBAMD_XPROD_GENERIC=1 selects the plain kernel) next to the same byte model -- two partials buffers per branch -- and, from 16
+states, the matrix-core flop model 2 (32 TILES)^2 x patterns x categories x branches at 157.3 TFLOP/s."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -12,7 +19,12 @@ from tests.engine_checks import division_from_golden
 case = sys.argv[1] if len(sys.argv) > 1 else "bench_c4"
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 lib = bg.BeagleLibrary()
-div = division_from_golden(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"), case)
+if ":" in case:
+    from mrbayes_amd.division import synthetic_division
+    kind, ntaxa, npat, ncat = case.split(":")
+    div = synthetic_division(kind, int(ntaxa), int(npat), seed=11, tree_seed=5, alpha=0.7, ncat=int(ncat))
+else:
+    div = division_from_golden(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"), case)
 bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, pre_order=True)
 try:
     inst, t = bd.inst, div.tree
@@ -54,5 +66,28 @@ try:
           "read-out %.3f ms (byte model %.3f ms: %.0f %%), together %.3f ms = %.1f evaluations; |gradient| max %.3f" %
           (case, inst.details.implName.decode(), lnl, eval_ms, len(nodes), pre, launches, model_pre, 100.0 * model_pre / pre, read, model_read,
            100.0 * model_read / read, pre + read, (pre + read) / eval_ms, max(abs(v) for v in grad.values())))
+    lengths = [min(max(t.length[n], lk.BRLENS_MIN), lk.BRLENS_MAX) for n in nodes]
+    cx = dict(posts=ix["posts"], pres=ix["pres"], rates=[0] * len(nodes), weights=ix["weights"], edge_lengths=lengths)
+    rc, X = inst.calculate_cross_products(**cx)                  # (warm-up)
+    inst.get_kernel_timing(reset=True)
+    cross_ms = []
+    for i in range(repeats):
+        t0 = time.perf_counter()
+        rc, X1 = inst.calculate_cross_products(**cx)
+        cross_ms.append((time.perf_counter() - t0) * 1e3)
+    _, launches = inst.get_kernel_timing(reset=True)
+    assert rc == 0 and np.array_equal(X, X1)
+    es = div.eigen[0]
+    Q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
+    lhs, rhs = float((Q * X).sum()), sum(tl * grad[n] for n, tl in zip(nodes, lengths))
+    cross = float(np.median(cross_ms))
+    S = div.nstates
+    tiles = 0 if S < 16 or S > 64 else (1 if S <= 32 else 2)
+    flops = 2.0 * (32 * tiles) ** 2 * div.npatterns * div.ncat * len(nodes)
+    model_flop = flops / 157.3e12 * 1e3
+    print("%s: cross products of %d branches (%s): %.3f ms in %d launches a call (byte model %.3f ms: %.0f %%%s); sum Q X = %.6f against sum t g = %.6f" %
+          (case, len(nodes), "plain kernel" if os.environ.get("MBAMD_XPROD_GENERIC") and tiles else "matrix core" if tiles else "plain kernel",
+           cross, launches // repeats, model_read, 100.0 * model_read / cross,
+           "; flop model %.3f ms: %.0f %%" % (model_flop, 100.0 * model_flop / cross) if tiles else "", lhs, rhs))
 finally:
     bd.finalize()
