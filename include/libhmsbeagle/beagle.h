@@ -459,6 +459,10 @@ BEAGLE_DLLEXPORT int mbamdGetWalkCounts(int instance, long* out2);
  * (For tests: the sums over the engines behind the instance; a double-precision instance reports zeros; a null pointer is
  * BEAGLE_ERROR_OUT_OF_RANGE.) */
 BEAGLE_DLLEXPORT int mbamdGetRecomputeCounts(int instance, long* out3);
+/* The same three counters for the subtrees of three and four compact tips that such a launch leaves unstored as well
+ * (MBAMD_UNSTORED_TIPS=<T>, 2 ... 4: the largest subtree left unstored; 2 = tip pairs only, and zeros here).  mbamdGetRecomputeCounts
+ * counts tip pairs only; out[2] here: launches that materialised at least one such subtree.  Same error codes. */
+BEAGLE_DLLEXPORT int mbamdGetSubtreeRecomputeCounts(int instance, long* out3);
 /* While the timing is on: device time (ms) of whole evaluations -- from the first kernel launched after a
  * Calculate*LogLikelihoods call to the end of the next integration kernel, i.e. every kernel of a step (transition matrices,
  * partials, integration) and the gaps between them -- and how many such spans were closed. */

@@ -64,7 +64,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
-    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
+    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
@@ -153,6 +153,7 @@ class BeagleLibrary:
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdGetSubtreeRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetStepTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdUpdateFinalPartials.argtypes = [C.c_int, C.c_void_p, C.c_int]
         L.mbamdGetScaledPartials.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -533,6 +534,12 @@ class BeagleInstance:
         """(tip-pair buffers that whole-tree launches left unstored, buffers materialised since, launches that materialised them)"""
         out = (C.c_long * 3)()
         self._chk(self.lib.mbamdGetRecomputeCounts(self.id, out), "mbamdGetRecomputeCounts")
+        return tuple(int(v) for v in out)
+
+    def get_subtree_recompute_counts(self):
+        """the same three counters for the subtrees of three and four compact tips (MBAMD_UNSTORED_TIPS)"""
+        out = (C.c_long * 3)()
+        self._chk(self.lib.mbamdGetSubtreeRecomputeCounts(self.id, out), "mbamdGetSubtreeRecomputeCounts")
         return tuple(int(v) for v in out)
 
     # ---- reports (include/libhmsbeagle/mbamd_reports.h) --------------------------------------------

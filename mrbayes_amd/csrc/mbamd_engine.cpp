@@ -1096,6 +1096,14 @@ int mbamdGetRecomputeCounts(int instance, long* out3)
     if (h->f64) return BEAGLE_SUCCESS;
     EACH_ENGINE(false, (c->recomputeCounts(out3), BEAGLE_SUCCESS));       // (children: the sums over them)
 }
+int mbamdGetSubtreeRecomputeCounts(int instance, long* out3)
+{
+    GET_INSTANCE_NOFLUSH(instance);
+    if (!out3) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetSubtreeRecomputeCounts: null output");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (h->f64) return BEAGLE_SUCCESS;
+    EACH_ENGINE(false, (c->subtreeRecomputeCounts(out3), BEAGLE_SUCCESS));       // (children: the sums over them)
+}
 // Device time of whole evaluations while mbamdKernelTiming is on: from the first kernel launched after a log-likelihood
 // call to the end of the next integration kernel -- every kernel of a step and the gaps between them (HIP events on the
 // engine's stream).  Children: the largest among them.

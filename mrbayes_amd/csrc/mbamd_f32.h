@@ -60,6 +60,22 @@ static void raise_walkg_lds(int maxLds)
         (void) hipGetLastError();
 }
 
+// 4-state walk: how an unstored result is made again from compact tips alone (Instance::ensureStored) -- the one to three operations of
+// its subtree in post-order, the last one its own.  A child is a compact tip (its buffer index) or, `in` set, the result of an earlier
+// operation of the same recipe (that operation's number): no buffer of an inner node is named.  Matrices, in the buffer's slot of the
+// snapshot table: places 0 and 1 for its own operation (as a tip pair's), 2 + 2 j and 3 + 2 j for inner operation j (k_walk4_snapshot).
+// (MBAMD_W4_UNSTORED_TIPS_MAX and MBAMD_W4_SNAP, the matrices of a slot: mbamd_walk4.h, beside k_walk4_snapshot)
+#define MBAMD_W4_UNSTORED_TIPS_DEFAULT 4
+struct Walk4Recipe {
+    int nops = 0;
+    struct Op { int c1, c2, mode; bool in1, in2; } op[MBAMD_W4_UNSTORED_TIPS_MAX - 1];
+    bool usesTip(int tip) const
+    {
+        for (int j = 0; j < nops; ++j) if ((!op[j].in1 && op[j].c1 == tip) || (!op[j].in2 && op[j].c2 == tip)) return true;
+        return false;
+    }
+};
+
 // A compiled operation list: the device-resident table a partials kernel walks, cached under the exact
 // BeagleOperation array it was built from.  MrBayes re-issues the same lists all the time (every move
 // that dirties the whole tree alternates between the two buffer-flip states), so the host-side
@@ -76,10 +92,13 @@ struct Plan {
     };
     std::vector<Segment> segments;               // (Walk4Entry index of its program in d_table, geometry)
     std::vector<Walk4Entry> inlineProg;          // 4-state walk: a short single-segment program travels in the kernel arguments instead
-    // 4-state walk: the TIP PAIRS (both children compact tips) of a list that is ONE plain segment in a device buffer -- their entries
-    // carry MBAMD_W4_NOSTORE, their destinations are left unstored with a recipe (Instance::leaveUnstored); empty for every other plan
-    struct TipPair { int entry, dst, tip1, tip2, mode; };
-    std::vector<TipPair> tipPairs;
+    // 4-state walk: the SMALL SUBTREES (compact tips and operations of the list alone, at most MBAMD_UNSTORED_TIPS tips: tip pairs, and
+    // subtrees of three and four tips) of a list that is ONE plain segment in a device buffer -- their entries carry MBAMD_W4_NOSTORE,
+    // their destinations are left unstored with a recipe (Instance::leaveUnstored); empty for every other plan.  `inner`: the program
+    // entries of the recipe's inner operations, which k_walk4_snapshot copies the matrices of (the side table behind the program)
+    struct Unstored { int entry, dst; Walk4Recipe r; int inner[MBAMD_W4_UNSTORED_TIPS_MAX - 2]; };
+    std::vector<Unstored> unstoredSubtrees;
+    size_t sideFirst = 0; int sideCount = 0;     // the side table: Walk4Entry index in d_table, records (one per subtree of more than two tips)
     bool path = false;                           // 4-state walk: the list is a root-ward path -- inlineProg holds k_path4's entries
     bool forked = false;                         // ... of several arms that join (the list of a topology move)
     bool pathG = false;                          // 20/61-state walk: every list is a root-ward path of the same length -- inlineProg holds k_pathg's entries
@@ -174,8 +193,10 @@ struct Instance {
     void listCounts(long out6[6]) const { const long c[6] = {listsTotal, listsPath, forkedPaths, fusedPaths, listsWalked, opsWalked}; std::copy(c, c + 6, out6); }
     void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of k_walk4_t<Walk4Args, true> / of the generic instantiations
     int walkTrace(long long* out, int maxSteps, int* outSteps, int* outWaves);
-    // tip-pair buffers launches left unstored / buffers materialised since / launches that materialised them (mbamdGetRecomputeCounts)
+    // tip-pair buffers launches left unstored / buffers materialised since / launches that materialised them (mbamdGetRecomputeCounts);
+    // the same for the subtrees of three and four tips (mbamdGetSubtreeRecomputeCounts)
     void recomputeCounts(long out3[3]) const { out3[0] += leftUnstored; out3[1] += materialised; out3[2] += materialiseLaunches; }
+    void subtreeRecomputeCounts(long out3[3]) const { out3[0] += leftUnstoredSub; out3[1] += materialisedSub; out3[2] += materialiseLaunchesSub; }
 
 private:
     friend int new_engine(std::unique_ptr<Instance>&, const Dims&, int, int, const Switches&);
@@ -204,14 +225,17 @@ private:
     std::vector<char> scaleState;    // 0 = never written (zero), 1 = node exponents in the arena, 2 = cumulative (wide)
     int lastWalkW = 0, lastWalkSlots = 0, lastWalkEntries = 0, lastWalkPhases = 0;
     bool walkCumFresh = false;       // the cumulative buffer of the list being submitted holds nothing yet (store, do not add)
-    // ---- tip pairs a whole-tree launch did not store (MBAMD_W4_NOSTORE, mbamd_walk4.h).  Such a buffer stays `valid`: it carries a RECIPE
-    // -- its two compact tips, its scale mode, and its slot (its own index) in a device table of MATRIX SNAPSHOTS float [buffer][2][K][16],
+    // ---- small subtrees a whole-tree launch did not store (MBAMD_W4_NOSTORE, mbamd_walk4.h).  Such a buffer stays `valid`: it carries a RECIPE
+    // -- its compact tips, its one to three operations with their scale modes (Walk4Recipe: a closure, no inner buffer is named), and its
+    // slot (its own index) in a device table of MATRIX SNAPSHOTS float [buffer][MBAMD_W4_SNAP][K][16],
     // copied by k_walk4_snapshot behind the integration launch (off the critical path) or, at the latest, before anything overwrites a
     // matrix or reads a recipe (flushSnapshot) -- so a recipe never depends on a matrix buffer the client may overwrite.  Every reader of
     // partials calls ensureStored first: the unstored buffers among those it names are recomputed into their arena slices by ONE launch of
     // the generic k_walk4_t (same source, same bits; exponent bytes go to the scratch rows, the real scale buffers were written by the
-    // original launch).  Any write to a buffer drops its recipe; overwriting a tip materialises the recipes that use it first.
-    struct Recipe { int tip1 = -1, tip2 = -1, mode = 0; };
+    // original launch).  A subtree of three or four tips runs its two or three operations on the plain instantiation instead, the inner
+    // ones with MBAMD_W4_NOSTORE: only the named buffer is written.  Any write to a buffer drops its recipe; overwriting a tip
+    // materialises the recipes that use it first.
+    typedef Walk4Recipe Recipe;
     std::vector<char> unstored;      // per partials buffer: 1 = valid, not in the arena, recipes[idx] says how to make it
     std::vector<Recipe> recipes;
     int nUnstored = 0;               // every hook is one comparison while this is zero
@@ -220,10 +244,14 @@ private:
     void* d_storeProg = nullptr;     size_t storeProgCap = 0;       // a materialising program too long for the kernel arguments
     std::vector<int> storeList;      // scratch
     std::vector<Walk4Entry> storeProg;
-    long leftUnstored = 0, materialised = 0, materialiseLaunches = 0;
+    long leftUnstored = 0, materialised = 0, materialiseLaunches = 0;                 // tip pairs
+    long leftUnstoredSub = 0, materialisedSub = 0, materialiseLaunchesSub = 0;        // subtrees of three and four tips
+    int unstoredTips() const { return std::max(2, std::min(MBAMD_W4_UNSTORED_TIPS_MAX, sw.unstoredTips.value_or(MBAMD_W4_UNSTORED_TIPS_DEFAULT))); }
+    std::vector<int> w4subTips, w4subOps, w4entryOf;                // buildWalk scratch: per operation of the segment, its subtree
     int leaveUnstored(const Plan& plan);
     int flushSnapshot();
     int ensureStored(const int* bufs, int n);
+    int ensureStoredSubtrees();
     int ensureStored(int a, int b = -1) { const int v[2] = {a, b}; return nUnstored ? ensureStored(v, 2) : BEAGLE_SUCCESS; }
     int storeUsersOfTip(int tip);
     void dropRecipe(int idx) { if (nUnstored && unstored[(size_t) idx]) { unstored[(size_t) idx] = 0; --nUnstored; } }
@@ -413,7 +441,7 @@ private:
     uint64_t planClock = 0;
     int layoutEpoch = 0;             // bumped whenever a buffer changes between compact-tip and partials form
     long planHits = 0, planMisses = 0, fusedPaths = 0, heldPaths = 0, forkedPaths = 0, listsTotal = 0, listsPath = 0, opsWalked = 0, listsWalked = 0;
-    long walksPlain = 0, walksGeneric = 0;       // k_walk4_t launches: the plain instantiation / the generic ones (mbamdGetWalkCounts)
+    long walksPlain = 0, walksGeneric = 0;       // k_walk4_t launches: the plain instantiation / the generic ones (mbamdGetWalkCounts); materialising launches (ensureStored) are not counted
 
     // ---- helpers ----------------------------------------------------------------------------
     int grow(void** p, size_t* cap, size_t bytes) { return grow_device(stream, p, cap, bytes, std::max(bytes, *cap * 2)); }
@@ -1591,7 +1619,7 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
         if (rc == BEAGLE_SUCCESS) {
             StatTimer st_(ST_PLAN);
             plan->path = plan->forked = false;
-            plan->tipPairs.clear();
+            plan->unstoredSubtrees.clear();
             rc = buildPath4(*plan, ops, n) ? BEAGLE_SUCCESS : buildWalk(*plan, ops, n);
         }
         if (planBuilt(*plan, rc)) return rc;
@@ -1630,7 +1658,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
     written.assign((size_t) nBuffers, 0);
     w4table.clear();
     plan.segments.clear();
-    plan.tipPairs.clear();
+    plan.unstoredSubtrees.clear();
     std::vector<Walk4Op>& seg = w4ops;
     seg.clear();
     // segment state: buffers / exponent buffers the current segment has read or written
@@ -1648,6 +1676,25 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         key.push_back(w4.prefetchDistance * 2 + (w4.safeWaits ? 1 : 0));
         {
             std::vector<int>& writer = w4writer;          // buffer -> operation of this segment that writes it (-1 outside this block)
+            // (4-state walk) per operation: the tips of its subtree if that is compact tips and operations of this segment alone and has at
+            // most MBAMD_W4_UNSTORED_TIPS_MAX of them, else 0; and the subtree's operations in list order, its own last
+            constexpr int RO = MBAMD_W4_UNSTORED_TIPS_MAX - 1;
+            w4subTips.assign(wg ? 0 : seg.size(), 0);
+            w4subOps.assign(wg ? 0 : seg.size() * RO, -1);
+            for (size_t o = 0; o < seg.size() && !wg; ++o) {
+                const Walk4Op& op = seg[o];
+                const int w1 = op.tip1 ? -1 : writer[op.c1], w2 = op.tip2 ? -1 : writer[op.c2];
+                const int t1 = op.tip1 ? 1 : (w1 >= 0 ? w4subTips[(size_t) w1] : 0), t2 = op.tip2 ? 1 : (w2 >= 0 ? w4subTips[(size_t) w2] : 0);
+                if (t1 && t2 && t1 + t2 <= MBAMD_W4_UNSTORED_TIPS_MAX && (op.tip1 || op.tip2 || op.c1 != op.c2)) {
+                    w4subTips[o] = t1 + t2;
+                    int below = 0, *mine = &w4subOps[o * RO];
+                    for (const int w : {std::min(w1, w2), std::max(w1, w2)})          // (two inner children: two tip pairs, list order)
+                        for (int j = 0; w >= 0 && j < RO && w4subOps[(size_t) w * RO + j] >= 0; ++j) mine[below++] = w4subOps[(size_t) w * RO + j];
+                    mine[below] = (int) o;
+                }
+                writer[op.dst] = (int) o;
+            }
+            for (size_t o = 0; o < seg.size() && !wg; ++o) writer[seg[o].dst] = -1;
             for (size_t o = 0; o < seg.size(); ++o) {
                 key.push_back(seg[o].tip1 ? -1 : writer[seg[o].c1]);
                 key.push_back(seg[o].tip2 ? -1 : writer[seg[o].c2]);
@@ -1690,6 +1737,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         const uint32_t pbuf = wg ? (uint32_t) K * slotb : (uint32_t) ((size_t) (Ppad / 64) * K);
         const uint32_t ebuf = (uint32_t) K * 64u, mbuf = wg ? (uint32_t) (matrixFloats * 4) : (uint32_t) K * 64u;
         int prevKept = -1;                           // (20/61-state walk) slot the previous operation of the same program kept its result in
+        w4entryOf.assign(seg.size(), -1);            // (4-state walk) operation -> its entry, for the recipes of a one-wave plain program
         for (size_t i = 0; i < t.prog.size(); ++i) {
             const Walk4Template::Entry& te = t.prog[i];
             Walk4Entry& e = w4table[sg.first + i];
@@ -1753,7 +1801,31 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                 mode = op.scaleWrite >= 0 ? SCALE_WRITE : (op.scaleRead >= 0 ? SCALE_READ : SCALE_NONE);
                 if (op.scaleWrite >= 0) e.ewrite = (uint32_t) op.scaleWrite * ebuf;
                 if (op.scaleRead >= 0) e.eread = (uint32_t) op.scaleRead * ebuf;
-                if (op.tip1 && op.tip2) plan.tipPairs.push_back(Plan::TipPair{(int) (sg.first + i), op.dst, op.c1, op.c2, (int) mode});   // (kept or dropped below)
+                w4entryOf[(size_t) te.op] = (int) (sg.first + i);
+                const int subTips = w4subTips[(size_t) te.op];
+                if (sg.plain && t.W == 1 && subTips >= 2 && subTips <= unstoredTips()) {     // (kept or dropped below)
+                    // the recipe: the subtree's operations with their children as tips or as operations of the recipe; every one of them
+                    // ran earlier in this program (a child runs before its parent), so its entry is known
+                    constexpr int RO = MBAMD_W4_UNSTORED_TIPS_MAX - 1;
+                    const int* const sub = &w4subOps[(size_t) te.op * RO];
+                    Plan::Unstored u;
+                    u.entry = (int) (sg.first + i); u.dst = op.dst;
+                    for (int& x : u.inner) x = -1;
+                    bool placed = true;
+                    for (int j = 0; j < RO && sub[j] >= 0; ++j) {
+                        const Walk4Op& so = seg[(size_t) sub[j]];
+                        Walk4Recipe::Op& ro = u.r.op[u.r.nops++];
+                        ro.mode = so.scaleWrite >= 0 ? SCALE_WRITE : (so.scaleRead >= 0 ? SCALE_READ : SCALE_NONE);
+                        ro.in1 = !so.tip1; ro.in2 = !so.tip2;
+                        ro.c1 = so.c1; ro.c2 = so.c2;
+                        for (int q = 0; q < j; ++q) {
+                            if (ro.in1 && seg[(size_t) sub[q]].dst == so.c1) ro.c1 = q;
+                            if (ro.in2 && seg[(size_t) sub[q]].dst == so.c2) ro.c2 = q;
+                        }
+                        if (sub[j] != te.op) { u.inner[j] = w4entryOf[(size_t) sub[j]]; placed = placed && u.inner[j] >= 0; }
+                    }
+                    if (placed) plan.unstoredSubtrees.push_back(u);
+                }
             }
             if (te.vmwait != 0xFF) flags |= MBAMD_W4_VMWAIT;
             // the entry in front of a SCALE_READ entry of the same wave fetches that entry's stored exponents (mbamd_walk4.h)
@@ -1823,13 +1895,26 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
     // a short program goes out with the launch itself (k_walk4_t<Walk4ArgsInline>, k_walkg<..., WalkGArgsInline>)
     plan.inlineProg.clear();
     const bool inlineForm = !sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE;
-    // Tip pairs are not stored where nothing can read the HBM copy in the launch that makes them: the list is ONE segment and that
+    // Small subtrees are not stored where nothing can read the HBM copy in the launch that makes them: the list is ONE segment and that
     // segment runs on the plain kernel (one wave, no prefetch: every child is a tip, a slot or the forwarded result).  Lists cut over
     // several waves or segments, programs in the kernel arguments and the generic / path kernels store everything.
-    if (s4 && !sw.storeTipPairs && !sw.noPlainWalk && !inlineForm && plan.segments.size() == 1 && plan.segments[0].plain)
-        for (const Plan::TipPair& tp : plan.tipPairs) w4table[(size_t) tp.entry].ctl |= MBAMD_W4_NOSTORE;
-    else
-        plan.tipPairs.clear();
+    plan.sideFirst = 0; plan.sideCount = 0;
+    if (s4 && !sw.storeTipPairs && !sw.noPlainWalk && !inlineForm && plan.segments.size() == 1 && plan.segments[0].plain) {
+        for (const Plan::Unstored& u : plan.unstoredSubtrees) w4table[(size_t) u.entry].ctl |= MBAMD_W4_NOSTORE;
+        // the side table k_walk4_snapshot reads, behind the program: per subtree of more than two tips its own entry and its inner ones
+        plan.sideFirst = w4table.size();
+        for (const Plan::Unstored& u : plan.unstoredSubtrees) {
+            if (u.r.nops < 2) continue;
+            Walk4Entry side;
+            std::memset(&side, 0, sizeof side);
+            side.ctl = (uint32_t) u.entry; side.dst = (uint32_t) (u.r.nops - 1);
+            side.c1 = (uint32_t) u.inner[0]; side.c2 = (uint32_t) (u.r.nops > 2 ? u.inner[1] : u.inner[0]);
+            w4table.push_back(side);
+            plan.sideCount++;
+        }
+    } else {
+        plan.unstoredSubtrees.clear();
+    }
     if (inlineForm) {
         plan.inlineProg = w4table;
         return BEAGLE_SUCCESS;
@@ -2068,7 +2153,7 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
             auto kernel = k_walk4_t<Walk4Args, true>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, sg.nslots), stream, a);
             plainHere = true;
-            if (!plan.tipPairs.empty()) { const int urc = leaveUnstored(plan); if (urc) return urc; }
+            if (!plan.unstoredSubtrees.empty()) { const int urc = leaveUnstored(plan); if (urc) return urc; }
         } else {
             a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
             auto kernel = k_walk4_t<Walk4Args>;
@@ -2082,25 +2167,25 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Tip pairs a whole-tree launch did not store (see the members: Recipe, unstored, d_snap).
+// Small subtrees -- tip pairs, and subtrees of three and four compact tips -- that a whole-tree launch did not store (see the
+// members: Recipe, unstored, d_snap).
 // ---------------------------------------------------------------------------------------------
 // behind a launch of the plain kernel whose program carries MBAMD_W4_NOSTORE entries: their destinations hold recipes from now on
 inline int Instance::leaveUnstored(const Plan& plan)
 {
-    if (!d_snap) HIP_TRY(hipMalloc(&d_snap, (size_t) nBuffers * 2 * K * 16 * sizeof(float)));
+    if (!d_snap) HIP_TRY(hipMalloc(&d_snap, (size_t) nBuffers * MBAMD_W4_SNAP * K * 16 * sizeof(float)));
     if (snapPlan && snapPlan != &plan) { int rc = flushSnapshot(); if (rc) return rc; }     // (the matrices are what they were at that launch: nothing overwrote one since)
-    for (const Plan::TipPair& tp : plan.tipPairs) {
-        if (!unstored[(size_t) tp.dst]) ++nUnstored;
-        unstored[(size_t) tp.dst] = 1;
-        Recipe& r = recipes[(size_t) tp.dst];
-        r.tip1 = tp.tip1; r.tip2 = tp.tip2; r.mode = tp.mode;
+    for (const Plan::Unstored& u : plan.unstoredSubtrees) {
+        if (!unstored[(size_t) u.dst]) ++nUnstored;
+        unstored[(size_t) u.dst] = 1;
+        recipes[(size_t) u.dst] = u.r;
+        ++(u.r.nops > 1 ? leftUnstoredSub : leftUnstored);
     }
-    leftUnstored += (long) plan.tipPairs.size();
     snapPlan = const_cast<Plan*>(&plan);
     return BEAGLE_SUCCESS;
 }
 
-// the waiting copy of a launch's tip-pair matrices into the snapshot table, now (k_walk4_snapshot reads the plan's own program)
+// the waiting copy of the matrices of a launch's unstored subtrees into the snapshot table, now (k_walk4_snapshot reads the plan's own program)
 inline int Instance::flushSnapshot()
 {
     Plan* const plan = snapPlan;
@@ -2108,15 +2193,17 @@ inline int Instance::flushSnapshot()
     if (!plan || plan->segments.size() != 1 || !plan->d_table) return BEAGLE_SUCCESS;
     const Plan::Segment& sg = plan->segments[0];
     plan->lastLaunch = ++launchClock;            // (the program must stay what it is until this launch has run: planTable)
-    MBAMD_LAUNCH(k_walk4_snapshot, (unsigned) (sg.entries - sg.tail), 64, 0, stream, reinterpret_cast<const Walk4Entry*>(plan->d_table) + sg.first,
-                 (unsigned) ((size_t) (Ppad / 64) * K), (const float*) matrices, d_snap, K);
+    const unsigned nprog = (unsigned) (sg.entries - sg.tail);
+    MBAMD_LAUNCH(k_walk4_snapshot, nprog + (unsigned) plan->sideCount, 64, 0, stream, reinterpret_cast<const Walk4Entry*>(plan->d_table) + sg.first,
+                 nprog, reinterpret_cast<const Walk4Entry*>(plan->d_table) + plan->sideFirst, (unsigned) ((size_t) (Ppad / 64) * K), (const float*) matrices, d_snap, K);
     HIP_TRY(hipGetLastError());
     return BEAGLE_SUCCESS;
 }
 
 // Every reader of partials, before its launch: the unstored buffers among `bufs` (indices out of range, tips and stored buffers are
 // passed over) are recomputed into the arena by one launch of the generic k_walk4_t -- entries with both children tips, matrices from
-// the snapshot table, no cumulative buffer, the exponent byte to the scratch rows -- and drop their recipes.
+// the snapshot table, no cumulative buffer, the exponent byte to the scratch rows -- and drop their recipes.  With a subtree of three or
+// four tips among them the one launch is of the plain instantiation, through a device buffer (ensureStoredSubtrees).
 inline int Instance::ensureStored(const int* bufs, int n)
 {
     if (nUnstored == 0) return BEAGLE_SUCCESS;
@@ -2132,6 +2219,7 @@ inline int Instance::ensureStored(const int* bufs, int n)
     if (list.empty()) return BEAGLE_SUCCESS;
     int rc = flushSnapshot();
     if (rc) return rc;
+    for (int b : list) if (recipes[(size_t) b].nops > 1) return ensureStoredSubtrees();
     const int m = (int) list.size(), entries = (m + 1) / 2 * 2 + 2;              // the kernel's loop runs two entries a turn and reads two ahead
     const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
     const uint32_t scratch = (uint32_t) scale.size();
@@ -2145,12 +2233,12 @@ inline int Instance::ensureStored(const int* bufs, int n)
         if (i >= m) continue;
         const uint32_t b = (uint32_t) list[(size_t) i];
         const Recipe& r = recipes[b];
-        e.ctl = MBAMD_W4_TIP1 | MBAMD_W4_TIP2 | ((uint32_t) r.mode << 8);
+        e.ctl = MBAMD_W4_TIP1 | MBAMD_W4_TIP2 | ((uint32_t) r.op[0].mode << 8);
         e.dst = b * pbuf;
-        e.c1 = (uint32_t) r.tip1 * 32u;
-        e.c2 = (uint32_t) r.tip2 * 32u;
-        e.m1 = (2u * b) * mbuf;
-        e.m2 = (2u * b + 1u) * mbuf;
+        e.c1 = (uint32_t) r.op[0].c1 * 32u;
+        e.c2 = (uint32_t) r.op[0].c2 * 32u;
+        e.m1 = ((uint32_t) MBAMD_W4_SNAP * b) * mbuf;
+        e.m2 = ((uint32_t) MBAMD_W4_SNAP * b + 1u) * mbuf;
     }
     Walk4ArgsInline ai;
     Walk4Args& a = ai.a;
@@ -2184,13 +2272,87 @@ inline int Instance::ensureStored(const int* bufs, int n)
     return BEAGLE_SUCCESS;
 }
 
+// storeList (every buffer in it unstored, the matrices snapshot) holds a subtree of three or four tips: ONE launch of the plain
+// instantiation k_walk4_t<Walk4Args, true> -- the kernel and the entry kinds of the original launch: the same bits -- over the recipes'
+// operations in post-order.  An inner operation carries MBAMD_W4_NOSTORE: its result reaches its parent through the forwarding
+// registers or LDS slot 0 (the first tip pair of a balanced four) and lands nowhere else -- the arena slice of the inner buffer may
+// hold something else by now.  Matrices from the buffer's snapshot slots, exponent bytes to the scratch rows, no cumulative buffer.
+// A plain program has no form in the kernel arguments: it goes through d_storeProg, however short.
+inline int Instance::ensureStoredSubtrees()
+{
+    const std::vector<int>& list = storeList;
+    const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
+    const uint32_t scratch = (uint32_t) scale.size();
+    storeProg.clear();
+    int pairs = 0, subtrees = 0;
+    for (int b : list) {
+        const Recipe& r = recipes[(size_t) b];
+        ++(r.nops > 1 ? subtrees : pairs);
+        for (int j = 0; j < r.nops; ++j) {
+            const Recipe::Op& o = r.op[j];
+            Walk4Entry e;
+            std::memset(&e, 0, sizeof e);
+            const bool last = j == r.nops - 1;
+            // matrices: the buffer's own operation in snapshot slots 0 and 1, inner operation j in 2 + 2 j and 3 + 2 j
+            const uint32_t mslot = (uint32_t) MBAMD_W4_SNAP * (uint32_t) b + (last ? 0u : 2u + 2u * (uint32_t) j);
+            uint32_t flags = 0;
+            // a child made by the operation in front is forwarded; one made two in front (the first tip pair of a balanced four) waits in slot 0
+            if (!o.in1) { flags |= MBAMD_W4_TIP1; e.c1 = (uint32_t) o.c1 * 32u; }
+            else if (o.c1 == j - 1) flags |= MBAMD_W4_FWD1;
+            if (!o.in2) { flags |= MBAMD_W4_TIP2; e.c2 = (uint32_t) o.c2 * 32u; }
+            else if (o.c2 == j - 1) flags |= MBAMD_W4_FWD2;
+            for (int q = j + 2; q < r.nops; ++q)
+                if ((r.op[q].in1 && r.op[q].c1 == j) || (r.op[q].in2 && r.op[q].c2 == j)) flags |= MBAMD_W4_KEEP;   // (slot 0: [23:16] stays zero)
+            e.ctl = flags | ((uint32_t) o.mode << 8) | walk4_kind_of(flags) | (last ? 0u : MBAMD_W4_NOSTORE);
+            e.dst = last ? (uint32_t) b * pbuf : 0u;
+            e.m1 = mslot * mbuf;
+            e.m2 = (mslot + 1u) * mbuf;
+            e.ewrite = (scratch + (uint32_t) (storeProg.size() % MBAMD_W4_SCRATCH_ROWS)) * ebuf;
+            e.eread = (flags & MBAMD_W4_TIP1) ? e.c1 : 0u;                   // (a plain program: child 1's plane offset or 0, Instance::buildWalk)
+            storeProg.push_back(e);
+        }
+    }
+    const int nops = (int) storeProg.size(), entries = (nops + 1) / 2 * 2 + 2;   // the read-ahead tail: valid offsets, nothing executed
+    for (int i = nops; i < entries; ++i) {
+        Walk4Entry e;
+        std::memset(&e, 0, sizeof e);
+        e.ctl = MBAMD_W4_NOP;
+        e.ewrite = (scratch + (uint32_t) (i % MBAMD_W4_SCRATCH_ROWS)) * ebuf;
+        storeProg.push_back(e);
+    }
+    Walk4Args a = walk4Args();
+    a.matrices = d_snap;
+    a.cum = nullptr;
+    a.cumFresh = 0;
+    a.entries = entries;
+    a.nslots = 1;
+    a.tail = entries - nops;
+    ++launchClock;
+    const size_t bytes = (size_t) entries * sizeof(Walk4Entry);
+    int rc = grow(&d_storeProg, &storeProgCap, bytes);
+    if (rc) return rc;
+    rc = upload(d_storeProg, storeProg.data(), bytes);
+    if (rc) return rc;
+    a.prog = static_cast<const Walk4Entry*>(d_storeProg);
+    auto kernel = k_walk4_t<Walk4Args, true>;
+    MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64, walk4_lds_bytes(1, 1), stream, a);
+    HIP_TRY(hipGetLastError());
+    for (int b : list) unstored[(size_t) b] = 0;
+    nUnstored -= (int) list.size();
+    materialised += pairs;
+    materialiseLaunches += pairs ? 1 : 0;
+    materialisedSub += subtrees;
+    materialiseLaunchesSub += 1;
+    return BEAGLE_SUCCESS;
+}
+
 // a compact tip is about to change (new states, or partials in its place): the unstored buffers made from it are stored first
 inline int Instance::storeUsersOfTip(int tip)
 {
     if (nUnstored == 0) return BEAGLE_SUCCESS;
     std::vector<int> users;
     for (int b = 0; b < nBuffers; ++b)
-        if (unstored[(size_t) b] && (recipes[(size_t) b].tip1 == tip || recipes[(size_t) b].tip2 == tip)) users.push_back(b);
+        if (unstored[(size_t) b] && recipes[(size_t) b].usesTip(tip)) users.push_back(b);
     return users.empty() ? BEAGLE_SUCCESS : ensureStored(users.data(), (int) users.size());
 }
 

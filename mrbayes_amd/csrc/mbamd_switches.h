@@ -28,6 +28,7 @@ struct Switches {
     bool noInlinePrograms = false;         // MBAMD_NO_INLINE_PROGRAMS: every walk program through a device buffer
     bool noPlainWalk = false;              // MBAMD_NO_PLAIN_WALK: whole-tree 4-state lists on the generic k_walk4_t instead of its plain instantiation
     bool storeTipPairs = false;            // MBAMD_STORE_TIP_PAIRS: whole-tree 4-state lists store the results of tip pairs too (no recipes, no recomputation)
+    std::optional<int> unstoredTips;       // MBAMD_UNSTORED_TIPS=<T>: such lists leave subtrees of up to T compact tips unstored (clamped to 2 ... 4; 2 = tip pairs only)
     bool noPath4 = false;                  // MBAMD_NO_PATH4: 4-state root-ward paths through k_walk4_t instead of k_path4
     bool noFusePath = false;               // MBAMD_NO_FUSE_PATH: a 4-state path and its log-likelihood as two launches
     bool noForkPath = false;               // MBAMD_NO_FORK_PATH: paths that join through the tree-walk scheduler
@@ -70,7 +71,7 @@ inline Switches read_switches()
     if (const char* e = std::getenv("MBAMD_MPI_RANK")) s.mpiRank = e;
     s.forceGeneric = on("MBAMD_FORCE_GENERIC"); s.noWalkG = on("MBAMD_NO_WALKG"); s.noMfma = on("MBAMD_NO_MFMA"); s.mfmaWhole = on("MBAMD_MFMA_WHOLE");
     s.noDefer = on("MBAMD_NO_DEFER"); s.noInlinePrograms = on("MBAMD_NO_INLINE_PROGRAMS"); s.noPath4 = on("MBAMD_NO_PATH4");
-    s.noPlainWalk = on("MBAMD_NO_PLAIN_WALK"); s.storeTipPairs = on("MBAMD_STORE_TIP_PAIRS");
+    s.noPlainWalk = on("MBAMD_NO_PLAIN_WALK"); s.storeTipPairs = on("MBAMD_STORE_TIP_PAIRS"); s.unstoredTips = num("MBAMD_UNSTORED_TIPS");
     s.noFusePath = on("MBAMD_NO_FUSE_PATH"); s.noForkPath = on("MBAMD_NO_FORK_PATH"); s.noPathG = on("MBAMD_NO_PATHG");
     s.mfmaSerial = num("MBAMD_MFMA_SERIAL"); s.noSpine = on("MBAMD_NO_SPINE"); s.spineWidth = num("MBAMD_SPINE_WIDTH"); s.noPoll = on("MBAMD_NO_POLL");
     s.walkWaves = num("MBAMD_WALK_WAVES"); s.maxLdsSlots = num("MBAMD_MAX_LDS_SLOTS"); s.walkSmallPhase = num("MBAMD_WALK_SMALL_PHASE");

@@ -57,7 +57,7 @@ namespace mbamd {
 #define MBAMD_W4_FWD2     0x02000000u
 #define MBAMD_W4_READS      0x00000200u  // (= ScaleMode SCALE_READ in [9:8]) this entry divides by stored exponents: they were fetched into the landing area
 #define MBAMD_W4_NEXT_READS 0x04000000u  // the NEXT entry of this wave is SCALE_READ: fetch its stored exponents now (4-state walk; set by the host)
-// A TIP PAIR (both children compact tips) of a whole-tree list on the plain instantiation: the 1 KiB result is NOT stored -- its parent reads
+// A SMALL SUBTREE (compact tips alone below it: a tip pair, or three or four tips, MBAMD_UNSTORED_TIPS) of a whole-tree list on the plain instantiation: the 1 KiB result is NOT stored -- its parent reads
 // the LDS slot or the forwarding registers, and it is a pure function of 64 bytes of tip planes and two matrices: whoever needs it later has
 // it recomputed (the host keeps a recipe and a snapshot of the matrices, Instance::ensureStored).  Exponent byte, slot, cum_e: as ever.
 // Honoured by k_walk4_t<Walk4Args, true> only; the host sets it nowhere else.
@@ -394,16 +394,31 @@ k_walk4_t(ARGS AA)
     }
 }
 
-// The matrices of a program's MBAMD_W4_NOSTORE entries -> the snapshot table float [buffer][2][K][16], slot = the entry's destination
-// buffer: what a recipe recomputes an unstored tip pair from, whatever the client does to the matrix buffers afterwards.  One workgroup
-// per entry of a single-wave program; `kibPerBuffer` = KiB of a partials buffer (the unit of Walk4Entry::dst).
+// The matrices of a program's MBAMD_W4_NOSTORE entries -> the snapshot table float [buffer][SNAP][K][16], slot = the entry's destination
+// buffer: what a recipe recomputes an unstored subtree from, whatever the client does to the matrix buffers afterwards.  The entry's own
+// two matrices go to places 0 and 1 of its slot: one workgroup per entry of a single-wave program (the first `nprog` workgroups).  A
+// subtree of more than two tips carries its whole closure: workgroup nprog + r takes record r of the SIDE TABLE the host put behind the
+// program -- ctl = the subtree's entry, dst = its inner operations (1 or 2), c1 / c2 = their entries -- and copies inner operation q's
+// matrices to places 2 + 2 q and 3 + 2 q.  `kibPerBuffer` = KiB of a partials buffer (the unit of Walk4Entry::dst).
+#define MBAMD_W4_UNSTORED_TIPS_MAX 4                                   // the largest subtree that may stay unstored (MBAMD_UNSTORED_TIPS)
+#define MBAMD_W4_SNAP (2u * (MBAMD_W4_UNSTORED_TIPS_MAX - 1))          // matrices per slot: two per operation of such a subtree
 __global__ void __launch_bounds__(64)
-k_walk4_snapshot(const Walk4Entry* prog, unsigned kibPerBuffer, const float* matrices, float* snap, int K)
+k_walk4_snapshot(const Walk4Entry* prog, unsigned nprog, const Walk4Entry* side, unsigned kibPerBuffer, const float* matrices, float* snap, int K)
 {
+    const unsigned n = (unsigned) K * 16u;
+    if (blockIdx.x >= nprog) {
+        const Walk4Entry* const r = side + (blockIdx.x - nprog);
+        float* const dst = snap + ((size_t) (prog[r->ctl].dst / kibPerBuffer) * MBAMD_W4_SNAP + 2u) * n;
+        for (unsigned i = threadIdx.x; i < 2u * r->dst * n; i += 64u) {
+            const unsigned c = i / n, j = i - c * n;
+            const Walk4Entry* const e = prog + (c < 2u ? r->c1 : r->c2);
+            dst[i] = matrices[(size_t) (((c & 1u) ? e->m2 : e->m1) >> 2) + j];
+        }
+        return;
+    }
     const Walk4Entry* const e = prog + blockIdx.x;
     if (!(e->ctl & MBAMD_W4_NOSTORE)) return;
-    const unsigned n = (unsigned) K * 16u;
-    float* const dst = snap + (size_t) (e->dst / kibPerBuffer) * 2u * n;
+    float* const dst = snap + (size_t) (e->dst / kibPerBuffer) * MBAMD_W4_SNAP * n;
     for (unsigned i = threadIdx.x; i < 2u * n; i += 64u) {
         const unsigned c = i / n, j = i - c * n;
         dst[i] = matrices[(size_t) ((c ? e->m2 : e->m1) >> 2) + j];
