@@ -200,7 +200,22 @@ BEAGLE_DLLEXPORT int beagleSetTipPartials(int instance, int tipIndex, const doub
 BEAGLE_DLLEXPORT int beagleSetPartials(int instance, int bufferIndex, const double* inPartials);
 /* read a partials buffer back, [category][pattern][state]; scaleIndex must be BEAGLE_OP_NONE */
 BEAGLE_DLLEXPORT int beagleGetPartials(int instance, int bufferIndex, int scaleIndex, double* outPartials);
-/* reference src/likelihood.c:10652,10752: row-major U, U^-1 (S x S) and S real eigenvalues */
+/* reference src/likelihood.c:10652,10752: row-major U, U^-1 (S x S) and S real eigenvalues.
+ *
+ * COMPLEX INSTANCES (the rate matrices of non-reversible models; not used by MrBayes, which rejects complex eigenvalues).  An
+ * instance is complex when BEAGLE_FLAG_EIGEN_COMPLEX is in the requirement flags of beagleCreateInstance, or in the preference
+ * flags while BEAGLE_FLAG_EIGEN_REAL is not required; requiring both flags is BEAGLE_ERROR_NO_IMPLEMENTATION.  Its details.flags
+ * carry EIGEN_COMPLEX instead of EIGEN_REAL; every other instance is what it always was.  On a complex instance inEigenValues
+ * holds 2 * stateCount values: the real parts a_s, then the imaginary parts b_s.  b_s == 0 is a real eigenvalue; b_p != 0 must be
+ * the first of an adjacent pair (p, p+1) with a_(p+1) == a_p and b_(p+1) == -b_p; an unpaired or non-finite value is
+ * BEAGLE_ERROR_OUT_OF_RANGE.  inEigenVectors = V and inInverseEigenVectors = V^-1 stay real S x S: the real block form of the
+ * decomposition (upstream's EigenDecompositionSquare convention), defined by
+ *     Q = V D V^-1,   D block-diagonal:  [a_s] for a real s,   [[a_p, b_p], [-b_p, a_p]] for a pair (p, p+1)
+ * -- for an eigenvector v of a_p + i b_p, columns p and p+1 of V are Re v and Im v.  beagleUpdateTransitionMatrices[WithMultiple-
+ * Models] then gives, with r_k the category rate, mu = r_k (a_p + i b_p), o the derivative order and z = mu^o exp(mu t),
+ *     d^o P_k / dt^o = V B V^-1,   B = [Re z] for a real s,   [[Re z, Im z], [-Im z, Re z]] for a pair
+ * order 0 clamped at zero, orders 1 and 2 not, a rate of exactly 0.0 giving P' = P'' = 0 exactly; everything else about those
+ * calls is unchanged.  mbamdSetRateMatrices[From] stays the reversible solver and leaves zero imaginary parts. */
 BEAGLE_DLLEXPORT int beagleSetEigenDecomposition(int instance, int eigenIndex, const double* inEigenVectors,
                                                  const double* inInverseEigenVectors, const double* inEigenValues);
 /* reference src/mbbeagle.c:1179 */

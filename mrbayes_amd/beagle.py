@@ -27,6 +27,8 @@ BEAGLE_OP_NONE = -1
 
 BEAGLE_FLAG_PRECISION_SINGLE = 1 << 0
 BEAGLE_FLAG_PRECISION_DOUBLE = 1 << 1
+BEAGLE_FLAG_EIGEN_REAL = 1 << 4
+BEAGLE_FLAG_EIGEN_COMPLEX = 1 << 5
 BEAGLE_FLAG_SCALING_ALWAYS = 1 << 8
 BEAGLE_FLAG_SCALERS_LOG = 1 << 10
 BEAGLE_FLAG_PROCESSOR_GPU = 1 << 16
@@ -251,7 +253,11 @@ class BeagleInstance:
         return out
 
     def set_eigen_decomposition(self, idx, evec, ivec, evals):
+        """evals: S values; on a complex instance (BEAGLE_FLAG_EIGEN_COMPLEX) 2 S, the real parts then the imaginary parts."""
         a, b, c = _d(evec), _d(ivec), _d(evals)
+        want = self.state_count * (2 if self.details.flags & BEAGLE_FLAG_EIGEN_COMPLEX else 1)
+        if c.size != want:
+            raise ValueError("set_eigen_decomposition: %d eigenvalues for an instance that reads %d" % (c.size, want))
         self._chk(self.lib.beagleSetEigenDecomposition(self.id, idx, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                                        c.ctypes.data_as(_dp)), "beagleSetEigenDecomposition")
 

@@ -49,7 +49,7 @@ static void buildResources()
         g_resourceDescs[i] = buf;
         g_resourceVec[i].name = const_cast<char*>(g_resourceNames[i].c_str());
         g_resourceVec[i].description = const_cast<char*>(g_resourceDescs[i].c_str());
-        g_resourceVec[i].supportFlags = kSupport | BEAGLE_FLAG_PRECISION_DOUBLE;
+        g_resourceVec[i].supportFlags = kSupport | BEAGLE_FLAG_PRECISION_DOUBLE | BEAGLE_FLAG_EIGEN_COMPLEX;
         g_resourceVec[i].requiredFlags = 0;
     }
     g_resources.list = g_resourceVec.data();
@@ -369,9 +369,14 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCreateInstance: bad dimensions");
     if (stateCount > 64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCreateInstance: more than 64 states");
     if (categoryCount > MBAMD_MAX_RATES) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCreateInstance: more than 16 rate categories");
-    if (requirementFlags & (BEAGLE_FLAG_EIGEN_COMPLEX | BEAGLE_FLAG_PROCESSOR_CPU |
-                            BEAGLE_FLAG_FRAMEWORK_CUDA | BEAGLE_FLAG_FRAMEWORK_OPENCL | BEAGLE_FLAG_SCALERS_RAW))
+    if (requirementFlags & (BEAGLE_FLAG_PROCESSOR_CPU | BEAGLE_FLAG_FRAMEWORK_CUDA | BEAGLE_FLAG_FRAMEWORK_OPENCL | BEAGLE_FLAG_SCALERS_RAW))
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCreateInstance: unsupported requirement flags");
+    if ((requirementFlags & BEAGLE_FLAG_EIGEN_COMPLEX) && (requirementFlags & BEAGLE_FLAG_EIGEN_REAL))
+        return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCreateInstance: both eigen flags required");
+    // complex eigen-systems (the rate matrices of non-reversible models, beagle.h) when the flag is required, or preferred and
+    // real ones are not required: eigenvalues then come as 2 S doubles and the matrix kernels run their complex form
+    const bool wantComplex = (requirementFlags & BEAGLE_FLAG_EIGEN_COMPLEX) ||
+                             ((preferenceFlags & BEAGLE_FLAG_EIGEN_COMPLEX) && !(requirementFlags & BEAGLE_FLAG_EIGEN_REAL));
     if ((requirementFlags & BEAGLE_FLAG_PRECISION_DOUBLE) && (requirementFlags & BEAGLE_FLAG_PRECISION_SINGLE))
         return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleCreateInstance: both precisions required");
     // double precision when it is required, or preferred and single is neither required nor preferred as well (MrBayes puts
@@ -401,7 +406,9 @@ int beagleCreateInstance(int tipCount, int partialsBufferCount, int compactBuffe
     std::unique_ptr<Handle> h(new Handle());       // (a create that fails below takes whatever was made with it)
     h->dim = Dims{tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount,
                   categoryCount, scaleBufferCount};
+    h->dim.complexEigen = wantComplex;             // (with the dimensions: pattern shards and partition children are made from them)
     h->flags = kSupport | (requirementFlags & (BEAGLE_FLAG_SCALING_ALWAYS | BEAGLE_FLAG_SCALING_DYNAMIC));
+    if (wantComplex) h->flags = (h->flags & ~BEAGLE_FLAG_EIGEN_REAL) | BEAGLE_FLAG_EIGEN_COMPLEX;
     h->sw = sw;
     h->device = dev;
     h->shardDevices = devices;

@@ -202,8 +202,9 @@ private:
     friend int new_engine(std::unique_ptr<Instance>&, const Dims&, int, int, const Switches&);
     hipStream_t stream{};
     int tipCount = 0, nBuffers = 0, S = 0, SP = 0, P = 0, Ppad = 0, nEigen = 0, nMatrices = 0, K = 0, nScale = 0;
+    bool complexEigen = false;       // BEAGLE_FLAG_EIGEN_COMPLEX: launchMatrices takes the CX form of the matrix kernels
     bool s4 = false;                 // 4-state float4 layout + tree-walk kernel
-    bool wg = false;                 // 20/61-state tree-walk kernel on the matrix cores (mbamd_walkg.h) + its arenas
+    bool wg = false;                // 20/61-state tree-walk kernel on the matrix cores (mbamd_walkg.h) + its arenas
     bool noWalkG = false;            // the arenas of that path did not fit: level kernels with buffers allocated on first use
     bool arena() const { return s4 || wg; }   // buffers are slices of arenas, exponents are per (pattern, category)
     bool mfma = false;               // general-state path on the matrix cores (mbamd_kernels_mfma.h)
@@ -533,7 +534,7 @@ private:
     int planTable(Plan& plan, const void* table, size_t bytes);
     int timedRun(const Plan& plan, int32_t* cum);
     int flushMatrices();
-    template <int ORDER> int launchMatrices(const MatrixJob* jobs, int count);
+    template <int ORDER, bool CX = false> int launchMatrices(const MatrixJob* jobs, int count);
     std::vector<MatrixJob> pendingJobs;          // queued beagleUpdateTransitionMatrices work
     std::vector<char> pendingMatrixOut;          // matrix buffers the queued jobs write
     int submit(Plan* plan, int cumIdx, int32_t* cumPtr);
@@ -591,6 +592,7 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
     nEigen = dim.eigenBufferCount;
     nMatrices = dim.matrixBufferCount;
     nScale = dim.scaleBufferCount;
+    complexEigen = dim.complexEigen;
     // the 4-state tree walk addresses buffers with 32-bit byte offsets inside a (block, category) column set (Walk4Entry)
     s4 = (S == 4 && !sw.forceGeneric && (size_t) nBuffers * K * 1024 < ((size_t) 1 << 32) && (size_t) nMatrices * K * 64 < ((size_t) 1 << 32) &&
           (size_t) (nScale + MBAMD_W4_SCRATCH_ROWS) * K * 64 < ((size_t) 1 << 32));
@@ -630,7 +632,9 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
         int rc = configureWalk();
         if (rc) return rc;
     }
-    eigenDoubles = (size_t) 3 * S * S + S;       // [U | U^-1 | lambda | V]: V = orthonormal eigenvectors kept for warm starts (k_eigen_reversible)
+    // [U | U^-1 | lambda | V | b | side]: V = orthonormal eigenvectors kept for warm starts (k_eigen_reversible); b | side = the
+    // imaginary parts and where each index's partner lies (complex_factor, mbamd_kernels.h: read on a complex instance only)
+    eigenDoubles = eigen_imag_offset(S) + (size_t) 2 * S;
     partials.assign(nBuffers, nullptr);
     tipStates.assign(nBuffers, nullptr);
     scale.assign(std::max(nScale, 1), nullptr);
@@ -696,6 +700,8 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMalloc(&d_eigen, std::max<size_t>(1, (size_t) nEigen * eigenDoubles) * sizeof(double)));
+    // (a complex instance's kernels index U with `side`: an eigen buffer never set must not send them out of the buffer)
+    if (complexEigen) HIP_TRY(hipMemsetAsync(d_eigen, 0, std::max<size_t>(1, (size_t) nEigen * eigenDoubles) * sizeof(double), stream));
     HIP_TRY(hipMalloc(&d_freqs, std::max<size_t>(1, (size_t) nEigen * S) * sizeof(double)));
     HIP_TRY(hipMalloc(&d_weights, std::max<size_t>(1, (size_t) nEigen * K) * sizeof(double)));
     HIP_TRY(hipMalloc(&d_rates, (size_t) K * sizeof(double)));
@@ -1003,6 +1009,9 @@ inline int Instance::setRateMatrices(int first, int count, const double* q, cons
     else
         MBAMD_LAUNCH_BARRIER(k_eigen_reversible<8>, (unsigned) count, 256, eigen_lds_doubles(S) * sizeof(double), stream, djobs, S, 30);
     HIP_TRY(hipGetLastError());
+    if (complexEigen)                                               // the systems of a reversible matrix are real: b = 0, side = 0
+        for (int i = 0; i < count; ++i)
+            HIP_TRY(hipMemsetAsync(d_eigen + (size_t) (first + i) * eigenDoubles + eigen_imag_offset(S), 0, (size_t) 2 * S * sizeof(double), stream));
     // bookkeeping only once the launch is in the stream: a failure above leaves the buffers "cold" and unshielded
     for (int i = 0; i < count; ++i) {
         eigenWarm[first + i] = warmAfter[i];
@@ -1019,10 +1028,17 @@ inline int Instance::setEigen(int idx, const double* U, const double* Ui, const 
         return BEAGLE_SUCCESS;
     }
     if (eigenWarm.size() == (size_t) nEigen) eigenWarm[idx] = -1;
-    std::vector<double> h((size_t) 2 * S * S + S);
+    // (a complex instance: `lam` holds 2 S values, the whole buffer travels -- V, which no longer belongs to it, as zeros)
+    std::vector<double> h(complexEigen ? eigenDoubles : (size_t) 2 * S * S + S, 0.0);
     std::memcpy(h.data(), U, sizeof(double) * S * S);
     std::memcpy(h.data() + (size_t) S * S, Ui, sizeof(double) * S * S);
     std::memcpy(h.data() + (size_t) 2 * S * S, lam, sizeof(double) * S);
+    if (complexEigen) {
+        double* im = h.data() + eigen_imag_offset(S);
+        std::memcpy(im, lam + S, sizeof(double) * S);
+        if (!eigen_pairs(lam, im, S, im + S))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetEigenDecomposition: an imaginary part without its adjacent conjugate, or a non-finite eigenvalue");
+    }
     return upload(d_eigen + (size_t) idx * eigenDoubles, h.data(), h.size() * sizeof(double));
 }
 
@@ -1111,17 +1127,21 @@ inline int Instance::flushMatrices()
     return rc;
 }
 
-// the transition-matrix launch of `count` jobs of one derivative ORDER (0: the probabilities), whichever kernel the layout takes
-template <int ORDER>
+// the transition-matrix launch of `count` jobs of one derivative ORDER (0: the probabilities), whichever kernel the layout takes;
+// CX: the kernels' form for complex eigen-systems (mbamd_kernels.h), which a complex instance takes -- chosen here, on the host
+template <int ORDER, bool CX>
 inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
 {
+    if constexpr (!CX) {
+        if (complexEigen) return launchMatrices<ORDER, true>(jobs, count);
+    }
     const RatesArg rates = rateSets[pendingRateSet];
     if (s4 && count <= MBAMD_S4_INLINE_JOBS && count * K <= 64) {
         // a branch move's one or two matrices: the jobs in the kernel arguments (mbamd_kernels.h)
         MatrixJobs4 ja;
         std::memset(&ja, 0, sizeof ja);
         std::memcpy(ja.j, jobs, sizeof(MatrixJob) * count);
-        MBAMD_LAUNCH(k_transition_matrices_s4_inline<ORDER>, 1u, 64, 0, stream, ja, rates, K, count * K);
+        MBAMD_LAUNCH((k_transition_matrices_s4_inline<ORDER, CX>), 1u, 64, 0, stream, ja, rates, K, count * K);
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
     }
@@ -1130,7 +1150,7 @@ inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
     if (rc) return rc;
     if (s4) {
         const int total = count * K;
-        MBAMD_LAUNCH(k_transition_matrices_s4<ORDER>, (unsigned) ((total + 255) / 256), 256, 0, stream, djobs, rates, K, total);
+        MBAMD_LAUNCH((k_transition_matrices_s4<ORDER, CX>), (unsigned) ((total + 255) / 256), 256, 0, stream, djobs, rates, K, total);
         HIP_TRY(hipGetLastError());
         return BEAGLE_SUCCESS;
     }
@@ -1138,10 +1158,10 @@ inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
         const unsigned grid = (unsigned) (count * K);
         const int packedT = mfma ? T : 0;
         const size_t wgTab = wg ? wgTabFloats : 0;
-        auto k1 = k_transition_matrices_mfma<1, ORDER>;
-        auto k2 = k_transition_matrices_mfma<2, ORDER>;
-        auto k3 = k_transition_matrices_mfma<3, ORDER>;
-        auto k4 = k_transition_matrices_mfma<4, ORDER>;
+        auto k1 = k_transition_matrices_mfma<1, ORDER, CX>;
+        auto k2 = k_transition_matrices_mfma<2, ORDER, CX>;
+        auto k3 = k_transition_matrices_mfma<3, ORDER, CX>;
+        auto k4 = k_transition_matrices_mfma<4, ORDER, CX>;
         switch ((S + 15) / 16) {
             case 1: MBAMD_LAUNCH_BARRIER(k1, grid, 64, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
             case 2: MBAMD_LAUNCH_BARRIER(k2, grid, 128, 0, stream, djobs, rates, S, SP, K, packedT, wgTab); break;
@@ -1155,12 +1175,12 @@ inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
     const double* evs = nullptr;                 // up to 64 states the matrix kernel forms the exponentials itself
     if (S > 64) {
         const size_t nev = (size_t) count * K * S;
-        rc = grow((void**) &d_ev, &evCap, nev * sizeof(double));
+        rc = grow((void**) &d_ev, &evCap, (CX ? 2 : 1) * nev * sizeof(double));
         if (rc) return rc;
-        MBAMD_LAUNCH(k_eigen_exponentials<ORDER>, (unsigned) ((nev + 255) / 256), 256, 0, stream, djobs, rates, S, K, (int) nev, d_ev);
+        MBAMD_LAUNCH((k_eigen_exponentials<ORDER, CX>), (unsigned) ((nev + 255) / 256), 256, 0, stream, djobs, rates, S, K, (int) nev, d_ev);
         evs = d_ev;
     }
-    MBAMD_LAUNCH_BARRIER(k_transition_matrices_ev<ORDER>, (unsigned) (count * K), threads, 0, stream, djobs, evs, rates, S, SP, K, 1,
+    MBAMD_LAUNCH_BARRIER((k_transition_matrices_ev<ORDER, CX>), (unsigned) (count * K), threads, 0, stream, djobs, evs, rates, S, SP, K, 1,
                          mfma ? T : 0, wg ? wgTabFloats : (size_t) 0);
     HIP_TRY(hipGetLastError());
     return BEAGLE_SUCCESS;

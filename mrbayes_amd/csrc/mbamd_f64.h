@@ -92,6 +92,7 @@ public:
 private:
     int device = 0, tipCount = 0, nBuffers = 0, S = 0, SPAD = 0, IB = 4, P = 0, Ppad = 0, K = 1, nEigen = 0, nMatrices = 0, nScale = 0;
     size_t bufDoubles = 0, matDoubles = 0, eigDoubles = 0;
+    bool complexEigen = false;             // BEAGLE_FLAG_EIGEN_COMPLEX: runMatrices takes the CX form of the matrix kernels
     hipStream_t stream{};
     bool live = false;
     Switches sw;                           // the environment switches, read when the instance was created (mbamd_switches.h)
@@ -166,8 +167,8 @@ private:
     int upload(void* dst, const void* src, size_t bytes);
     int partitionRange(int partition, int* first, int* last, const char* what) const;
     int downloadScale(int idx, const char* what, std::vector<int32_t>& h);
-    template <int ORDER> void launchMatrices(const MatrixJob64* dj, int count);
-    template <int ORDER> int runMatrices(const std::vector<MatrixJob64>& jobs);
+    template <int ORDER, bool CX> void launchMatrices(const MatrixJob64* dj, int count);
+    template <int ORDER, bool CX = false> int runMatrices(const std::vector<MatrixJob64>& jobs);
     int flushMatrices();
     int flushQueue();
     int runPartials(const QueuedOp* qd, int n);
@@ -200,7 +201,8 @@ inline int Engine64::create(const Dims& dim, int patterns, int dev, const Switch
     SPAD = (S + IB - 1) / IB * IB;
     bufDoubles = (size_t) K * S * Ppad;
     matDoubles = (size_t) K * S * S + (size_t) K * S * SPAD;
-    eigDoubles = (size_t) 2 * S * S + S;
+    complexEigen = dim.complexEigen;
+    eigDoubles = eigen_imag_offset64(S) + (size_t) 2 * S;      // [U | U^-1 | lambda | b | side]: the last two are a complex instance's (k64_exponentials)
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     live = true;
@@ -209,6 +211,8 @@ inline int Engine64::create(const Dims& dim, int patterns, int dev, const Switch
     HIP_TRY(hipMalloc(&d_matrices, std::max<size_t>(1, (size_t) nMatrices * matDoubles) * sizeof(double)));
     HIP_TRY(hipMemsetAsync(d_matrices, 0, std::max<size_t>(1, (size_t) nMatrices * matDoubles) * sizeof(double), stream));
     HIP_TRY(hipMalloc(&d_eigen, std::max<size_t>(1, (size_t) nEigen * eigDoubles) * sizeof(double)));
+    // (a complex instance's kernels index U with `side`: an eigen buffer never set must not send them out of the buffer)
+    if (complexEigen) HIP_TRY(hipMemsetAsync(d_eigen, 0, std::max<size_t>(1, (size_t) nEigen * eigDoubles) * sizeof(double), stream));
     HIP_TRY(hipMalloc(&d_freqs, std::max<size_t>(1, (size_t) nEigen * S) * sizeof(double)));
     HIP_TRY(hipMalloc(&d_weights, std::max<size_t>(1, (size_t) nEigen * K) * sizeof(double)));
     HIP_TRY(hipMalloc(&d_pweights, (size_t) Ppad * sizeof(double)));
@@ -357,10 +361,16 @@ inline int Engine64::setEigen(int idx, const double* U, const double* Ui, const 
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
     if (idx < 0 || idx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetEigenDecomposition: eigen index");
-    std::vector<double> h(eigDoubles);
+    std::vector<double> h(eigDoubles, 0.0);
     std::memcpy(h.data(), U, sizeof(double) * S * S);
     std::memcpy(h.data() + (size_t) S * S, Ui, sizeof(double) * S * S);
     std::memcpy(h.data() + (size_t) 2 * S * S, lam, sizeof(double) * S);
+    if (complexEigen) {                    // `lam` holds 2 S values: the real parts, then the imaginary parts
+        double* im = h.data() + eigen_imag_offset64(S);
+        std::memcpy(im, lam + S, sizeof(double) * S);
+        if (!eigen_pairs(lam, im, S, im + S))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetEigenDecomposition: an imaginary part without its adjacent conjugate, or a non-finite eigenvalue");
+    }
     return upload(d_eigen + (size_t) idx * eigDoubles, h.data(), eigDoubles * sizeof(double));
 }
 inline int Engine64::setFreqs(int idx, const double* f)
@@ -390,34 +400,38 @@ inline int Engine64::setPatternWeights(const double* w)
 }
 
 // ---- beagleUpdateTransitionMatrices, beagleSet / GetTransitionMatrix ----
-template <int ORDER> inline void Engine64::launchMatrices(const MatrixJob64* dj, int count)
+template <int ORDER, bool CX> inline void Engine64::launchMatrices(const MatrixJob64* dj, int count)
 {
     if (S >= 16 && S <= 64) {
         const unsigned grid = (unsigned) (count * K);
         switch ((S + 15) / 16) {
-            case 1: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<1, ORDER>), grid, 64, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-            case 2: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<2, ORDER>), grid, 128, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-            case 3: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<3, ORDER>), grid, 192, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
-            default: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<4, ORDER>), grid, 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+            case 1: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<1, ORDER, CX>), grid, 64, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+            case 2: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<2, ORDER, CX>), grid, 128, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+            case 3: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<3, ORDER, CX>), grid, 192, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
+            default: MBAMD_LAUNCH_BARRIER((k64_matrices_mfma<4, ORDER, CX>), grid, 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K); break;
         }
         return;
     }
-    MBAMD_LAUNCH(k64_matrices<ORDER>, (unsigned) (count * K), 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K);
+    MBAMD_LAUNCH((k64_matrices<ORDER, CX>), (unsigned) (count * K), 256, 0, stream, dj, (const double*) d_ev, S, SPAD, K);
 }
-// the exponentials and the matrices of `jobs`, all of one derivative ORDER (the launches share d_ev: stream order keeps them apart)
-template <int ORDER> inline int Engine64::runMatrices(const std::vector<MatrixJob64>& jobs)
+// the exponentials and the matrices of `jobs`, all of one derivative ORDER (the launches share d_ev: stream order keeps them apart);
+// CX: the kernels' form for complex eigen-systems, which a complex instance takes (d_ev then holds the factor pair: twice the doubles)
+template <int ORDER, bool CX> inline int Engine64::runMatrices(const std::vector<MatrixJob64>& jobs)
 {
     if (jobs.empty()) return BEAGLE_SUCCESS;
+    if constexpr (!CX) {
+        if (complexEigen) return runMatrices<ORDER, true>(jobs);
+    }
     const int count = (int) jobs.size();
     void* dj = nullptr;
     int rc = stage(jobs.data(), jobs.size() * sizeof(MatrixJob64), &dj);
     if (rc) return rc;
-    const size_t need = (size_t) count * K * S * sizeof(double);
+    const size_t need = (size_t) (CX ? 2 : 1) * count * K * S * sizeof(double);
     rc = grow_device(stream, (void**) &d_ev, &evCap, need, need * 2);
     if (rc) return rc;
     const int total = count * K * S;
-    MBAMD_LAUNCH(k64_exponentials<ORDER>, (unsigned) ((total + 255) / 256), 256, 0, stream, (const MatrixJob64*) dj, rateSets[matQueueRate], S, K, total, d_ev);
-    launchMatrices<ORDER>((const MatrixJob64*) dj, count);
+    MBAMD_LAUNCH((k64_exponentials<ORDER, CX>), (unsigned) ((total + 255) / 256), 256, 0, stream, (const MatrixJob64*) dj, rateSets[matQueueRate], S, K, total, d_ev);
+    launchMatrices<ORDER, CX>((const MatrixJob64*) dj, count);
     HIP_TRY(hipGetLastError());
     return BEAGLE_SUCCESS;
 }

@@ -1012,7 +1012,10 @@ struct MatrixJob64 {
     double pad_;                 // host side: the derivative order of the job (0, 1, 2), one launch per order
 };
 // (ORDER: 0 = the probabilities, 1 / 2 = their first / second derivative in the branch length -- deriv_exponential, mbamd_kernels.h)
-template <int ORDER>
+// CX: a complex eigen-system (complex_factor, mbamd_kernels.h), [U | U^-1 | lambda | b | side] in this engine.  The factor pair goes
+// to ev[g] (C) and ev[total + g] (G); the matrix kernels' left operand is U[i,s] C[s] + U[i,partner[s]] G[s], partner[s] = s + side[s].
+__host__ __device__ inline size_t eigen_imag_offset64(int S) { return (size_t) 2 * S * S + S; }
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(256)
 k64_exponentials(const MatrixJob64* __restrict__ jobs, RatesArg rates, int S, int K, int total, double* __restrict__ ev)
 {
@@ -1020,7 +1023,13 @@ k64_exponentials(const MatrixJob64* __restrict__ jobs, RatesArg rates, int S, in
     if (g >= total) return;
     const int s = g % S, bk = g / S;
     const int b = bk / K, k = bk % K;
-    ev[g] = deriv_exponential<ORDER>(exp(jobs[b].eig[(size_t) 2 * S * S + s] * jobs[b].length * rates.r[k]), jobs[b].eig[(size_t) 2 * S * S + s], rates.r[k]);
+    if constexpr (CX) {
+        const EigenFactor f = complex_factor<ORDER>(jobs[b].eig + eigen_imag_offset64(S), S, s, jobs[b].eig[(size_t) 2 * S * S + s], jobs[b].length, rates.r[k]);
+        ev[g] = f.c;
+        ev[(size_t) total + g] = f.g;
+    } else {
+        ev[g] = deriv_exponential<ORDER>(exp(jobs[b].eig[(size_t) 2 * S * S + s] * jobs[b].length * rates.r[k]), jobs[b].eig[(size_t) 2 * S * S + s], rates.r[k]);
+    }
 }
 // TiProbs_Gen (reference src/likelihood.c:9498-9545): P_k = U diag(exp(lambda t r_k)) U^-1, negatives clamped to zero
 template <int ORDER> __device__ __forceinline__ double matrix_entry64(double sum)
@@ -1028,7 +1037,7 @@ template <int ORDER> __device__ __forceinline__ double matrix_entry64(double sum
     if constexpr (ORDER == 0) return sum < 0.0 ? 0.0 : sum;
     return sum;
 }
-template <int ORDER>
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(256)
 k64_matrices(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev, int S, int SPAD, int K)
 {
@@ -1041,7 +1050,13 @@ k64_matrices(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev
     for (int idx = threadIdx.x; idx < S * S; idx += blockDim.x) {
         const int i = idx / S, j = idx % S;
         double sum = 0.0;
-        for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
+        if constexpr (CX) {
+            const double* __restrict__ g = e + (size_t) gridDim.x * S;
+            const double* __restrict__ side = jobs[b].eig + eigen_imag_offset64(S) + S;
+            for (int s = 0; s < S; ++s) sum += (U[i * S + s] * e[s] + U[i * S + s + (int) side[s]] * g[s]) * Ui[s * S + j];
+        } else {
+            for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
+        }
         const double v = matrix_entry64<ORDER>(sum);
         M[(size_t) i * S + j] = v;
         MT[(size_t) j * SPAD + i] = v;
@@ -1049,7 +1064,7 @@ k64_matrices(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev
 }
 
 // the same product on the fp64 matrix cores for 16 <= S <= 64 (one wave per 16 rows, as k_transition_matrices_mfma of the fp32 engine)
-template <int NJ, int ORDER>
+template <int NJ, int ORDER, bool CX = false>
 __global__ void __launch_bounds__(64 * NJ)
 k64_matrices_mfma(const MatrixJob64* __restrict__ jobs, const double* __restrict__ ev, int S, int SPAD, int K)
 {
@@ -1057,8 +1072,7 @@ k64_matrices_mfma(const MatrixJob64* __restrict__ jobs, const double* __restrict
     const int b = blockIdx.x / K, k = blockIdx.x % K;
     const MBAMD_AS_GLOBAL double* __restrict__ U = as_global(jobs[b].eig);
     const MBAMD_AS_GLOBAL double* __restrict__ Ui = U + (size_t) S * S;
-    const MBAMD_AS_GLOBAL double* __restrict__ e = as_global(ev) + (size_t) blockIdx.x * S;
-    const int wave = (int) threadIdx.x >> 6, lane = (int) threadIdx.x & 63, li = lane & 15, ls = lane >> 4;
+    const MBAMD_AS_GLOBAL double* __restrict__ e = as_global(ev) + (size_t) blockIdx.x * S;    const int wave = (int) threadIdx.x >> 6, lane = (int) threadIdx.x & 63, li = lane & 15, ls = lane >> 4;
     const int i = 16 * wave + li, ic = i < S ? i : S - 1;
     d4 acc[NJ];
 #pragma unroll
@@ -1072,7 +1086,13 @@ k64_matrices_mfma(const MatrixJob64* __restrict__ jobs, const double* __restrict
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int s = 4 * (st0 + u) + ls, sc = s < S ? s : S - 1;
-            a[u] = (s < S && i < S) ? U[(size_t) ic * S + sc] * e[sc] : 0.0;
+            if constexpr (CX) {         // G lies behind the C of every block; the partner column is a second load of U
+                const MBAMD_AS_GLOBAL double* __restrict__ eg = e + (size_t) gridDim.x * S;
+                const int sp = sc + (int) U[eigen_imag_offset64(S) + S + sc];
+                a[u] = (s < S && i < S) ? U[(size_t) ic * S + sc] * e[sc] + U[(size_t) ic * S + sp] * eg[sc] : 0.0;
+            } else {
+                a[u] = (s < S && i < S) ? U[(size_t) ic * S + sc] * e[sc] : 0.0;
+            }
 #pragma unroll
             for (int jt = 0; jt < NJ; ++jt) bb[u][jt] = Ui[(size_t) sc * S + jc[jt]];
         }

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -104,7 +105,26 @@ inline uint64_t fnv1a(const int* v, size_t n, uint64_t h = 1469598103934665603ul
 struct Dims {
     int tipCount, partialsBufferCount, compactBufferCount, stateCount, patternCount, eigenBufferCount, matrixBufferCount, categoryCount,
         scaleBufferCount;
+    bool complexEigen = false;       // BEAGLE_FLAG_EIGEN_COMPLEX: eigenvalues come as 2 S doubles, the matrix kernels run their CX form
 };
+
+// The imaginary parts of a complex instance's eigenvalues (beagle.h): b[s] == 0 is a real eigenvalue; b[p] != 0 opens the adjacent pair
+// (p, p + 1) with a[p+1] == a[p] and b[p+1] == -b[p].  -> side[s] = +1 / -1 / 0: where the partner of index s lies (complex_factor,
+// mbamd_kernels.h).  false: an unpaired or non-finite value.
+inline bool eigen_pairs(const double* a, const double* b, int S, double* side)
+{
+    for (int s = 0; s < S; ++s)
+        if (!std::isfinite(a[s]) || !std::isfinite(b[s])) return false;
+    for (int s = 0; s < S; ++s) {
+        side[s] = 0.0;
+        if (b[s] == 0.0) continue;
+        if (s + 1 >= S || a[s + 1] != a[s] || b[s + 1] != -b[s]) return false;
+        side[s] = 1.0;
+        side[s + 1] = -1.0;
+        ++s;
+    }
+    return true;
+}
 
 // v3 pattern partitions (beagleSetPatternPartitions): ids[c] = partition of pattern c.  Partitions must be contiguous, increasing
 // pattern ranges (MrBayes lists its divisions one after the other): -> (first pattern, pattern count) of each of the `count` partitions.

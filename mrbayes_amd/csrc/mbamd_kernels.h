@@ -299,10 +299,56 @@ template <int ORDER> __device__ __forceinline__ float matrix_entry(double sum)
     return (float) sum;
 }
 
+// Complex eigen-systems (BEAGLE_FLAG_EIGEN_COMPLEX, beagle.h: the rate matrices of non-reversible models).  U and U^-1 stay real:
+// they are the real block form, Q = U D U^-1 with D = [a_s] at a real eigenvalue and [[a_p, b_p], [-b_p, a_p]] at a conjugate
+// pair (p, p + 1).  With mu = r_k (a_s + i b_s) and z = mu^ORDER exp(mu t), the derivative of order ORDER of P_k is U B U^-1 with
+// B = [Re z] and [[Re z, Im z], [-Im z, Re z]] in the same places.  The kernels keep their contraction over ONE eigen index: where
+// the real form has one factor e[s] per index, the complex form (template parameter CX, chosen by the host from the instance's flag;
+// the real instantiations are the code they were) has the pair
+//     C[s] = Re z_s,   G[s] = -Im z_s     (z_(p+1) is the conjugate of z_p: G is -Im z at p, +Im z at p + 1, and 0 at a real index)
+// and the index partner[s] = p + 1, p, or s itself; the left operand U[i,s] e[s] becomes U[i,s] C[s] + U[i,partner[s]] G[s].
+// The imaginary parts live behind the eigen-system as [b (S) | side (S)], side[s] = +1.0, -1.0 or 0.0: partner[s] = s + side[s]
+// (the host has checked the pairs, Instance::setEigen / Engine64::setEigen).  A real index takes deriv_exponential, as ever.
+// The trigonometry happens here, once per (job, category, eigen index), where the exponentials are formed -- never in a contraction.
+struct EigenFactor { double c, g; int partner; };
+// `im`: the [b | side] block of the eigen-system; a = lambda_s (the real part), t the branch length, r the category rate
+template <int ORDER> __device__ __forceinline__ EigenFactor complex_factor(const double* __restrict__ im, int S, int s, double a, double t, double r)
+{
+    EigenFactor f;
+    const double b = im[s];
+    f.partner = s + (int) im[S + s];
+    const double e = exp(a * t * r);
+    if (b == 0.0) {
+        f.c = deriv_exponential<ORDER>(e, a, r);
+        f.g = 0.0;
+        return f;
+    }
+    double sn, cs;
+    sincos(b * t * r, &sn, &cs);
+    double re = e * cs, img = e * sn;                        // exp(mu t)
+    if constexpr (ORDER > 0) {                               // times mu^ORDER (a rate of 0.0: mu = 0, the product an exact zero)
+        double mr = a * r, mi = b * r;
+        if constexpr (ORDER == 2) {
+            const double qr = mr * mr - mi * mi, qi = 2.0 * (mr * mi);
+            mr = qr;
+            mi = qi;
+        }
+        const double zr = mr * re - mi * img, zi = mr * img + mi * re;
+        re = zr;
+        img = zi;
+    }
+    f.c = re;
+    f.g = -img;
+    return f;
+}
+// where the [b | side] block lies in the single-precision engine's eigen buffer [U | U^-1 | lambda | V | b | side]
+__host__ __device__ inline size_t eigen_imag_offset(int S) { return (size_t) 3 * S * S + S; }
+
 // exp(lambda*t) hoisted: one thread per (job, k, s) fills ev[(job*K+k)*S + s]; the matrix kernel
 // below then reads it (second launch on the same stream, so no barrier is needed).
 // `jobs` may live in pinned host memory (read once, directly over the host link).
-template <int ORDER>
+// (CX: C in ev[g], G in ev[total + g])
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(256)
 k_eigen_exponentials(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, int K, int total, double* __restrict__ ev)
 {
@@ -311,12 +357,38 @@ k_eigen_exponentials(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, 
     const int s = g % S, bk = g / S;
     const int b = bk / K, k = bk % K;
     const double* __restrict__ lam = jobs[b].eig + (size_t) 2 * S * S;
-    ev[g] = deriv_exponential<ORDER>(exp(lam[s] * jobs[b].length * rates.r[k]), lam[s], rates.r[k]);
+    if constexpr (CX) {
+        const EigenFactor f = complex_factor<ORDER>(jobs[b].eig + eigen_imag_offset(S), S, s, lam[s], jobs[b].length, rates.r[k]);
+        ev[g] = f.c;
+        ev[(size_t) total + g] = f.g;
+    } else {
+        ev[g] = deriv_exponential<ORDER>(exp(lam[s] * jobs[b].length * rates.r[k]), lam[s], rates.r[k]);
+    }
+}
+
+// the four-state matrix of one (job, category) from a complex eigen-system: the body of both four-state kernels' CX form
+template <int ORDER> __device__ __forceinline__ void s4_matrix_complex(const MatrixJob& job, double r, int k)
+{
+    const double* __restrict__ U = job.eig;
+    const double* __restrict__ Ui = job.eig + 16;
+    const double* __restrict__ lam = job.eig + 32;
+    EigenFactor f[4];
+    for (int s = 0; s < 4; ++s) f[s] = complex_factor<ORDER>(job.eig + eigen_imag_offset(4), 4, s, lam[s], job.length, r);
+    float* __restrict__ out = job.out + (size_t) k * 16;
+    for (int i = 0; i < 4; ++i) {
+        double a[4];
+        for (int s = 0; s < 4; ++s) a[s] = U[i * 4 + s] * f[s].c + U[i * 4 + f[s].partner] * f[s].g;
+        for (int j = 0; j < 4; ++j) {
+            double sum = 0.0;
+            for (int s = 0; s < 4; ++s) sum += a[s] * Ui[s * 4 + j];
+            out[j * 4 + i] = matrix_entry<ORDER>(sum);
+        }
+    }
 }
 
 // 4-state path: one thread per (branch, category) does the whole 4x4 matrix, exps included
 // (TiProbs_Gen for S = 4, src/likelihood.c:9498-9545); output transposed mT[j][i] = P(i->j).
-template <int ORDER>
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(256)
 k_transition_matrices_s4(const MatrixJob* __restrict__ jobs, RatesArg rates, int K, int total)
 {
@@ -324,6 +396,7 @@ k_transition_matrices_s4(const MatrixJob* __restrict__ jobs, RatesArg rates, int
     if (g >= total) return;
     const int b = g / K, k = g % K;
     const MatrixJob job = jobs[b];
+    if constexpr (CX) { s4_matrix_complex<ORDER>(job, rates.r[k], k); return; }
     const double* __restrict__ U = job.eig;
     const double* __restrict__ Ui = job.eig + 16;
     const double* __restrict__ lam = job.eig + 32;
@@ -360,7 +433,7 @@ k_copy_from_ring4(const unsigned* __restrict__ src, unsigned* __restrict__ dst, 
 // path kernel waits behind it in 86 % of a chain's generations).
 #define MBAMD_S4_INLINE_JOBS 8
 struct MatrixJobs4 { MatrixJob j[MBAMD_S4_INLINE_JOBS]; };
-template <int ORDER>
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(64)
 k_transition_matrices_s4_inline(MatrixJobs4 jobs, RatesArg rates, int K, int total)
 {
@@ -368,6 +441,7 @@ k_transition_matrices_s4_inline(MatrixJobs4 jobs, RatesArg rates, int K, int tot
     if (g >= total) return;
     const int b = g / K, k = g % K;
     const MatrixJob job = jobs.j[b];
+    if constexpr (CX) { s4_matrix_complex<ORDER>(job, rates.r[k], k); return; }
     const double* __restrict__ U = job.eig;
     const double* __restrict__ Ui = job.eig + 16;
     const double* __restrict__ lam = job.eig + 32;
@@ -385,20 +459,30 @@ k_transition_matrices_s4_inline(MatrixJobs4 jobs, RatesArg rates, int K, int tot
 // packedT > 0: additionally write the MFMA A-operand copy behind the K transposed matrices:
 //   packed[((k*NT + i/32)*T + j/2)*64 + (i%32) + 32*(j%2)] = P_k(i->j),  NT = ceil(S/32), T = packedT = ceil(S/2)
 // wgTab > 0: additionally scatter into the tree-walk tables of category k, wgTab floats into the buffer (mbamd_walkg.h)
-template <int ORDER>
+// CX (complex eigen-systems, complex_factor above): the factor pair C | G in own[0..63 | 64..127], or in ev[..] | ev[gridDim.x S + ..]
+// as k_eigen_exponentials<ORDER, true> left it
+template <int ORDER, bool CX = false>
 __global__ void __launch_bounds__(256)
 k_transition_matrices_ev(const MatrixJob* __restrict__ jobs, const double* __restrict__ ev, RatesArg rates, int S, int SP, int K,
                          int transposed, int packedT, size_t wgTab)
 {
     // ev == nullptr (up to 64 states): the block forms its own S exponentials -- the expression of k_eigen_exponentials, one launch
     // less in front of every small-state evaluation (round 5: a standard-data class is a few hundred patterns, all launch latency)
-    __shared__ double own[64];
+    __shared__ double own[CX ? 128 : 64];
     const int b = blockIdx.x / K, k = blockIdx.x % K;
     const double* __restrict__ U = jobs[b].eig;
     const double* __restrict__ Ui = jobs[b].eig + (size_t) S * S;
     if (ev == nullptr) {
         const double* __restrict__ lam = jobs[b].eig + (size_t) 2 * S * S;
-        if ((int) threadIdx.x < S) own[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * jobs[b].length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
+        if constexpr (CX) {
+            if ((int) threadIdx.x < S) {
+                const EigenFactor f = complex_factor<ORDER>(jobs[b].eig + eigen_imag_offset(S), S, threadIdx.x, lam[threadIdx.x], jobs[b].length, rates.r[k]);
+                own[threadIdx.x] = f.c;
+                own[64 + threadIdx.x] = f.g;
+            }
+        } else {
+            if ((int) threadIdx.x < S) own[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * jobs[b].length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
+        }
         MBAMD_SYNC();
     }
     const double* __restrict__ e = ev ? ev + (size_t) blockIdx.x * S : own;
@@ -407,7 +491,13 @@ k_transition_matrices_ev(const MatrixJob* __restrict__ jobs, const double* __res
         // consecutive threads take consecutive j so that U^-1 reads are coalesced
         const int i = idx / S, j = idx % S;
         double sum = 0.0;
-        for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
+        if constexpr (CX) {
+            const double* __restrict__ g = ev ? e + (size_t) gridDim.x * S : own + 64;
+            const double* __restrict__ side = jobs[b].eig + eigen_imag_offset(S) + S;
+            for (int s = 0; s < S; ++s) sum += (U[i * S + s] * e[s] + U[i * S + s + (int) side[s]] * g[s]) * Ui[s * S + j];
+        } else {
+            for (int s = 0; s < S; ++s) sum += U[i * S + s] * e[s] * Ui[s * S + j];
+        }
         const float v = matrix_entry<ORDER>(sum);
         if (transposed) out[(size_t) j * SP + i] = v;
         else            out[(size_t) i * SP + j] = v;

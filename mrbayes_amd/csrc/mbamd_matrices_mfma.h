@@ -20,17 +20,31 @@ namespace mbamd {
 // doubles, <= 64 KiB) is L2 resident.  grid = count * K workgroups of ceil(S/16) waves; NJ = ceil(S/16).
 // ---------------------------------------------------------------------------------------------
 
-template <int NJ, int ORDER>
+// CX: a complex eigen-system (complex_factor, mbamd_kernels.h).  The prologue leaves the factor pair C | G in ev[0..63 | 64..127] and
+// the partner indices in LDS; the A operand is U[i,s] C[s] + U[i,partner[s]] G[s].  The partner column belongs to another lane group
+// (s = 4 st + (lane>>4)), so it is a second load from the L2-resident eigen-system, issued with the chunk's other operand loads; the
+// MFMA chain is the real form's.
+template <int NJ, int ORDER, bool CX = false>
 __global__ void __launch_bounds__(64 * NJ, 3)     // (three workgroups per CU: at 61 states 141 + 32 registers allowed two, and the 594 workgroups of codon 100 x 5 000 ran in two rounds)
 k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, int S, int SP, int K, int packedT, size_t wgTab)
 {
-    __shared__ double ev[64];
+    __shared__ double ev[CX ? 192 : 64];          // (CX: C | G | the partner indices, as int, in the last third)
     const int b = blockIdx.x / K, k = blockIdx.x % K;
     const MatrixJob job = jobs[b];
     const MBAMD_AS_GLOBAL double* __restrict__ U = as_global(job.eig);
     const MBAMD_AS_GLOBAL double* __restrict__ Ui = U + (size_t) S * S;
     const MBAMD_AS_GLOBAL double* __restrict__ lam = U + (size_t) 2 * S * S;
-    if ((int) threadIdx.x < S) ev[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * job.length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
+    if constexpr (CX) {
+        int* const partner = reinterpret_cast<int*>(ev + 128);
+        if ((int) threadIdx.x < S) {
+            const EigenFactor f = complex_factor<ORDER>(job.eig + eigen_imag_offset(S), S, threadIdx.x, lam[threadIdx.x], job.length, rates.r[k]);
+            ev[threadIdx.x] = f.c;
+            ev[64 + threadIdx.x] = f.g;
+            partner[threadIdx.x] = f.partner;
+        }
+    } else {
+        if ((int) threadIdx.x < S) ev[threadIdx.x] = deriv_exponential<ORDER>(exp(lam[threadIdx.x] * job.length * rates.r[k]), lam[threadIdx.x], rates.r[k]);
+    }
     MBAMD_SYNC();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int li = lane & 15, ls = lane >> 4;
@@ -42,12 +56,13 @@ k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, i
     constexpr int CH = 8;
     const int steps = (S + 3) / 4;
     for (int st0 = 0; st0 < steps; st0 += CH) {
-        double a[CH], bb[NJ][CH];
+        double a[CH], a2[CX ? CH : 1], bb[NJ][CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             const int s = 4 * (st0 + u) + ls;
             const int sc = min(s, S - 1);
             a[u] = U[(size_t) ic * S + sc];
+            if constexpr (CX) a2[u] = U[(size_t) ic * S + reinterpret_cast<const int*>(ev + 128)[sc]];
 #pragma unroll
             for (int jt = 0; jt < NJ; ++jt) bb[jt][u] = Ui[(size_t) sc * S + min(16 * jt + li, S - 1)];
         }
@@ -55,7 +70,9 @@ k_transition_matrices_mfma(const MatrixJob* __restrict__ jobs, RatesArg rates, i
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             const int s = 4 * (st0 + u) + ls;
-            const double av = (s < S && i < S) ? a[u] * ev[min(s, S - 1)] : 0.0;      // zero A kills the padded terms
+            double av;
+            if constexpr (CX) av = (s < S && i < S) ? a[u] * ev[min(s, S - 1)] + a2[u] * ev[64 + min(s, S - 1)] : 0.0;
+            else av = (s < S && i < S) ? a[u] * ev[min(s, S - 1)] : 0.0;      // zero A kills the padded terms
 #pragma unroll
             for (int jt = 0; jt < NJ; ++jt) acc[jt] = mbd_mfma_f64_16x16x4(av, bb[jt][u], acc[jt]);
         }

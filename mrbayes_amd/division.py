@@ -37,6 +37,11 @@ class Division:
     rate_matrices: Optional[List[np.ndarray]] = None   # the Q behind each eigen part (device-side eigen: mbamdSetRateMatrices)
 
     @property
+    def complex_eigen(self) -> bool:
+        """an eigen part with imaginary parts: the instance is created with BEAGLE_FLAG_EIGEN_COMPLEX"""
+        return any(e.imag is not None for e in self.eigen)
+
+    @property
     def npatterns(self) -> int:
         return int(self.weights.shape[0])
 
@@ -129,6 +134,13 @@ def build_division(kind: str, tree, weights, tip_states, tip_partials, *, revmat
         eig = [mbmodel.eigen_reversible(qmats[0], pi)]
         corr = 1.0
         part_w = np.ones(1)
+    elif kind.startswith("nrev"):                    # a non-reversible model of int(kind[4:]) states: complex eigen-systems
+        s = int(kind[4:])                            # (an instance created with BEAGLE_FLAG_EIGEN_COMPLEX, likelihood.py)
+        q, pi = mbmodel.nonreversible_q(s)
+        qmats = [q]
+        eig = [mbmodel.eigen_general(q)]
+        corr = 1.0
+        part_w = np.ones(1)
     else:
         raise ValueError(kind)
     rates = mbmodel.discrete_gamma(alpha, ncat) if (alpha is not None and ncat > 1) else np.ones(ncat)
@@ -174,7 +186,7 @@ def synthetic_division(kind: str, ntaxa: int, npatterns: int, seed: int = 7, tre
                        brlen: Optional[float] = 0.05) -> Division:
     """Synthetic inputs of the BASELINE shapes: every column is kept as its own pattern
     (weight 1) so P is exactly `npatterns`."""
-    nstates = int(kind[3:]) if kind.startswith("gen") else {"gtr": 4, "wag": 20, "m3": 61}[kind]
+    nstates = int(kind[3:]) if kind.startswith("gen") else int(kind[4:]) if kind.startswith("nrev") else {"gtr": 4, "wag": 20, "m3": 61}[kind]
     st = mbdata.synthetic_states(ntaxa, npatterns, nstates, seed, 0.15, p_gap)
     tr = mbtree.random_tree(ntaxa, tree_seed, brlen=brlen)
     tip_states, tip_partials = _tips_from_states(st)
@@ -191,7 +203,7 @@ def synthetic_division(kind: str, ntaxa: int, npatterns: int, seed: int = 7, tre
             p = rng.dirichlet(np.full(20, 5.0))
             wag = (ex, p)
         return build_division("wag", tr, w, tip_states, tip_partials, alpha=alpha, ncat=ncat, wag=wag)
-    if kind.startswith("gen"):
+    if kind.startswith("gen") or kind.startswith("nrev"):
         return build_division(kind, tr, w, tip_states, tip_partials, alpha=alpha, ncat=ncat)
     return build_division("m3", tr, w, tip_states, tip_partials, omegas=[0.1, 1.0, 3.0],
                           omega_freqs=[0.5, 0.3, 0.2], ncat=1)

@@ -26,6 +26,7 @@ import numpy as np
 
 from . import beagle as bg
 from .division import Division
+from .model import eigen_blocks
 
 MB_BEAGLE_SCALE_ALWAYS = 0
 MB_BEAGLE_SCALE_DYNAMIC = 1
@@ -87,6 +88,13 @@ class BeagleDivision:
             self.numPreOrder = nNodes + 1
             self.diffMatrixIndex = self.numTiProbs * step
             self.numDiffMatrices = 1
+            if div.complex_eigen:
+                # a non-reversible model cannot turn the root branch round: the process starts at the top interior node, and the
+                # root tip is its third child -- one more pre-order buffer (the root tip's) and an identity matrix (PreOrderOperations)
+                self.preOrderRootIndex = (self.numCondLikes + nNodes + 1) * step
+                self.numPreOrder = nNodes + 2
+                self.identityMatrixIndex = (self.numTiProbs + 1) * step
+                self.numDiffMatrices = 2
         # --- dirty flags ("touch" state), per chain ----------------------------------------------
         self.upDateCl = [[True] * nNodes for _ in range(nchains)]
         self.upDateTi = [[True] * nNodes for _ in range(nchains)]
@@ -106,6 +114,8 @@ class BeagleDivision:
         part_ambig = [d.tip_states[i] is None for i in range(self.N)]
         num_part_ambig = sum(part_ambig)
         req = bg.BEAGLE_FLAG_SCALERS_LOG if self.scaling == MB_BEAGLE_SCALE_ALWAYS else 0   # src/mbbeagle.c:191-194
+        if d.complex_eigen:                                               # a non-reversible model: eigenvalues in conjugate pairs
+            req |= bg.BEAGLE_FLAG_EIGEN_COMPLEX
         self.inst = bg.BeagleInstance(
             self.lib, self.N, (self.numCondLikes + self.numPreOrder) * self.step, self.N - num_part_ambig, d.nstates, d.npatterns,
             (self.nchains + 1) * self.step, (self.numTiProbs + self.numDiffMatrices) * self.step, d.ncat, self.numScalers * self.step,
@@ -195,8 +205,9 @@ class BeagleDivision:
             # unmodified MrBayes has no call for this, it sends finished eigen-systems like the branch below
             self.inst.set_rate_matrices(self.cijkIndex[chain], np.stack(self.div.rate_matrices), self.div.pi)
         else:
+            d_complex = self.div.complex_eigen          # (a complex instance reads 2 S eigenvalues: zero imaginary parts for a real part)
             for i, es in enumerate(self.div.eigen):
-                self.inst.set_eigen_decomposition(self.cijkIndex[chain] + i, es.evec, es.ivec, es.eval)
+                self.inst.set_eigen_decomposition(self.cijkIndex[chain] + i, es.evec, es.ivec, es.values if d_complex else es.eval)
         self.upDateAll[chain] = True
 
     # ---- TreeTiProbs_Beagle ------------------------------------------------------------------------
@@ -391,11 +402,20 @@ class BeagleDivision:
     def PreOrderOperations(self, chain):
         """The pre-order list of the whole tree, top-down and level by level (the engine runs operations that do not depend on one
         another in one launch, and cuts the list where they do): the top interior node hangs from the start vector without a
-        sibling factor, every other node from its parent's pre-order buffer with its sibling's post-order buffer."""
+        sibling factor, every other node from its parent's pre-order buffer with its sibling's post-order buffer.  (A division with
+        complex eigen-systems: the root tip is the top node's third child, see below.)"""
         t = self.div.tree
         top = t.root_left
-        ops = [[self.preOrderIndex[top], bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderStartIndex, self.tiProbsIndex[chain][top],
-                bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE]]
+        if self.div.complex_eigen:
+            # the start vector is pi at the top node; its buffer gets pi_i (P_top tip_root)[i] (the root tip as a sibling, through the
+            # identity), the root tip's own buffer sum_i P_top[i,j] pi_i post_top[i]: the pair BranchGradient reads for the root branch
+            ops = [[self.preOrderIndex[top], bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderStartIndex, self.identityMatrixIndex,
+                    self.condLikeIndex[chain][t.root], self.tiProbsIndex[chain][top]],
+                   [self.preOrderRootIndex, bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderStartIndex, self.tiProbsIndex[chain][top],
+                    self.condLikeIndex[chain][top], self.identityMatrixIndex]]
+        else:
+            ops = [[self.preOrderIndex[top], bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, self.preOrderStartIndex, self.tiProbsIndex[chain][top],
+                    bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE]]
         level = [top]
         while level:
             below = []
@@ -425,8 +445,21 @@ class BeagleDivision:
         else:
             tip = np.asarray(d.tip_partials[t.root], dtype=np.float64).reshape(P, S)
         start = tip * np.asarray(d.pi, dtype=np.float64)[None, :]
+        if d.complex_eigen:                  # (the root tip enters through the operations: PreOrderOperations)
+            start = np.broadcast_to(np.asarray(d.pi, dtype=np.float64)[None, :], (P, S))
+            self.inst.set_transition_matrix(self.identityMatrixIndex, np.broadcast_to(np.eye(S), (K, S, S)))
         self.inst.set_partials(self.preOrderStartIndex, np.broadcast_to(start, (K, P, S)))
         self.inst.update_pre_partials(self.PreOrderOperations(chain))
+
+    # the (post-order, pre-order) buffer pair at the lower end of every branch; a non-reversible model reads the root branch at
+    # the root tip (PreOrderOperations)
+    def _EdgePosts(self, chain, nodes):
+        t = self.div.tree
+        return [self.condLikeIndex[chain][t.root if self.div.complex_eigen and n == t.root_left else n] for n in nodes]
+
+    def _EdgePres(self, nodes):
+        t = self.div.tree
+        return [self.preOrderRootIndex if self.div.complex_eigen and n == t.root_left else self.preOrderIndex[n] for n in nodes]
 
     def BranchGradient(self, chain=0, sites=False):
         """{node: d lnL / d t_node} for all 2N-3 branches of the chain's current tree, after LogLike: the start vector
@@ -435,10 +468,13 @@ class BeagleDivision:
         self._PreOrderPass(chain, "BranchGradient")
         d, t = self.div, self.div.tree
         es = d.eigen[0]
-        q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
+        if es.imag is None:
+            q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
+        else:                                # Q = U D U^-1 with D in block form
+            q = np.asarray(es.evec, dtype=np.float64) @ eigen_blocks(es, es.eval + 1j * es.imag) @ np.asarray(es.ivec, dtype=np.float64)
         self.inst.set_differential_matrix(self.diffMatrixIndex, np.asarray(d.cat_rates, dtype=np.float64)[:, None, None] * q[None, :, :])
         nodes = list(t.all_down_pass)
-        rc, per, sums, _ = self.inst.calculate_edge_gradient([self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes],
+        rc, per, sums, _ = self.inst.calculate_edge_gradient(self._EdgePosts(chain, nodes), self._EdgePres(nodes),
                                                              [self.diffMatrixIndex] * len(nodes), [self.cijkIndex[chain]] * len(nodes), sites=sites)
         grad = {n: float(sums[i]) for i, n in enumerate(nodes)}
         return (grad, {n: per[i] for i, n in enumerate(nodes)}) if sites else grad
@@ -451,7 +487,7 @@ class BeagleDivision:
         self._PreOrderPass(chain, "RateMatrixCrossProducts")
         nodes = list(t.all_down_pass)
         lengths = [min(max(t.length[n], BRLENS_MIN), BRLENS_MAX) for n in nodes]
-        _, x = self.inst.calculate_cross_products([self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes],
+        _, x = self.inst.calculate_cross_products(self._EdgePosts(chain, nodes), self._EdgePres(nodes),
                                                   [0] * len(nodes), [self.cijkIndex[chain]] * len(nodes), lengths)
         return x
 

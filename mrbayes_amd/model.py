@@ -14,6 +14,9 @@ decompose it, and hand (U, U^-1, lambda) to the engine through `beagleSetEigenDe
 Eigen-decomposition: the reference uses a general real Hessenberg-QR (GetEigens, src/utils.c:11201);
 every model on the BEAGLE path is time-reversible, so we use the symmetric similarity transform
 B = D^1/2 Q D^-1/2 and a symmetric eigen-solver, which is real by construction.
+
+A general (non-reversible) rate matrix has complex-conjugate pairs of eigenvalues: `eigen_general` gives its real block
+form for an instance created with BEAGLE_FLAG_EIGEN_COMPLEX (include/libhmsbeagle/beagle.h).
 """
 from __future__ import annotations
 
@@ -46,10 +49,16 @@ def sense_codons(code: str = _UNIVERSAL) -> Tuple[List[Tuple[int, int, int]], Li
 
 @dataclass
 class EigenSystem:
-    """What beagleSetEigenDecomposition receives: row-major U, U^-1, real eigenvalues."""
+    """What beagleSetEigenDecomposition receives: row-major U, U^-1, real eigenvalues -- or, with `imag`, the real block form
+    of a complex eigen-system (a complex instance: `values` is then what the call takes, real parts then imaginary parts)."""
     evec: np.ndarray      # [S,S]
     ivec: np.ndarray      # [S,S]
     eval: np.ndarray      # [S]
+    imag: Optional[np.ndarray] = None      # [S] imaginary parts: b[p] != 0 opens the adjacent pair (p, p + 1), b[p+1] = -b[p]
+
+    @property
+    def values(self) -> np.ndarray:
+        return self.eval if self.imag is None else np.concatenate([self.eval, self.imag])
 
 
 def eigen_reversible(q: np.ndarray, pi: np.ndarray) -> EigenSystem:
@@ -68,6 +77,30 @@ def eigen_reversible(q: np.ndarray, pi: np.ndarray) -> EigenSystem:
     evec = v / d[:, None]
     ivec = v.T * d[None, :]
     return EigenSystem(np.ascontiguousarray(evec), np.ascontiguousarray(ivec), w)
+
+
+def eigen_general(q: np.ndarray) -> EigenSystem:
+    """The real block form of the eigen-decomposition of any diagonalisable rate matrix (upstream's EigenDecompositionSquare
+    convention): Q = V D V^-1 with D = [a_s] at a real eigenvalue and [[a_p, b_p], [-b_p, a_p]] at a conjugate pair (p, p + 1),
+    whose columns p and p + 1 of V are the real and the imaginary part of the eigenvector of a_p + i b_p."""
+    q = np.asarray(q, dtype=np.float64)
+    n = q.shape[0]
+    w, v = np.linalg.eig(q)
+    tol = 1e-12 * max(1.0, float(np.max(np.abs(w))))
+    is_real = np.abs(w.imag) <= tol
+    vecs, a, b = [], [], []
+    for s in np.flatnonzero(is_real):                # the real eigenvalues first ...
+        x = v[:, s]
+        x = (x * np.exp(-1j * np.angle(x[np.argmax(np.abs(x))]))).real      # (eig may hand a real vector a complex phase)
+        vecs.append(x); a.append(w[s].real); b.append(0.0)
+    for s in np.flatnonzero(~is_real & (w.imag > 0)):                       # ... then each pair once, its members adjacent
+        vecs += [v[:, s].real, v[:, s].imag]
+        a += [w[s].real, w[s].real]
+        b += [w[s].imag, -w[s].imag]
+    if len(a) != n:
+        raise ValueError("eigen_general: the complex eigenvalues do not come in conjugate pairs")
+    evec = np.ascontiguousarray(np.array(vecs).T)
+    return EigenSystem(evec, np.ascontiguousarray(np.linalg.inv(evec)), np.array(a), np.array(b))
 
 
 def gtr_q(rates: Sequence[float], pi: Sequence[float]) -> np.ndarray:
@@ -161,8 +194,44 @@ def discrete_gamma(alpha: float, k: int, median: bool = False) -> np.ndarray:
 
 
 def transition_matrices(es: EigenSystem, t: float, cat_rates: Sequence[float]) -> np.ndarray:
-    """fp64 P_k(t) = U diag(exp(lambda t r_k)) U^-1 -- test helper, not on the product path."""
-    out = np.empty((len(cat_rates), es.eval.size, es.eval.size))
+    """fp64 P_k(t) = U diag(exp(lambda t r_k)) U^-1 -- test helper, not on the product path.  With imaginary parts the
+    diagonal becomes the block form: [[Re z, Im z], [-Im z, Re z]] at a pair, z = exp((a + i b) t r_k)."""
+    n = es.eval.size
+    out = np.empty((len(cat_rates), n, n))
     for k, r in enumerate(cat_rates):
-        out[k] = (es.evec * np.exp(es.eval * t * r)[None, :]) @ es.ivec
+        if es.imag is None:
+            out[k] = (es.evec * np.exp(es.eval * t * r)[None, :]) @ es.ivec
+            continue
+        out[k] = es.evec @ eigen_blocks(es, np.exp((es.eval + 1j * es.imag) * t * r)) @ es.ivec
     return out
+
+
+def eigen_blocks(es: EigenSystem, z: np.ndarray) -> np.ndarray:
+    """The block-diagonal matrix of the values z_s on the eigen-system's indices: [Re z_s] at a real index,
+    [[Re z_p, Im z_p], [-Im z_p, Re z_p]] at a pair (p, p + 1).  z = the eigenvalues themselves: D of Q = U D U^-1."""
+    z = np.asarray(z, dtype=np.complex128)
+    blocks = np.diag(z.real)
+    p = 0
+    while es.imag is not None and p < z.size:
+        if es.imag[p] != 0.0:
+            blocks[p, p + 1], blocks[p + 1, p] = z[p].imag, -z[p].imag
+            p += 1
+        p += 1
+    return blocks
+
+
+def nonreversible_q(nstates: int, seed: int = 97):
+    """(Q, pi): a seeded random NON-reversible rate matrix with a cyclic bias -- the flow i -> i + 1 is favoured over its way
+    back, so that complex-conjugate pairs of eigenvalues occur -- scaled to one expected substitution per unit time at its
+    stationary distribution pi (the left null vector of Q)."""
+    rng = np.random.default_rng(seed + nstates)
+    q = rng.random((nstates, nstates)) * 0.5 + 0.05
+    for i in range(nstates):
+        q[i, (i + 1) % nstates] += 2.0
+    np.fill_diagonal(q, 0.0)
+    np.fill_diagonal(q, -q.sum(axis=1))
+    w, v = np.linalg.eig(q.T)
+    pi = v[:, np.argmin(np.abs(w))].real
+    pi = pi / pi.sum()
+    q = q / -(pi * np.diag(q)).sum()
+    return q, pi
