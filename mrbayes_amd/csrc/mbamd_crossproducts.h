@@ -263,7 +263,7 @@ k_cross_product_sums(const double* __restrict__ partial, int n, int SS, double* 
 
 // ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
 
-// the argument checks the two engines share (the rest, on buffers and indices, is each engine's own: as in its edgeGradient)
+// the check of the edge lengths (those on buffers and indices: edge_check, as in edge_gradient)
 inline int cross_check_lengths(const char* who, const double* t, int count)
 {
     for (int e = 0; e < count; ++e)
@@ -298,6 +298,59 @@ inline int launch_cross_products(hipStream_t stream, CrossArgs a, int chunks, bo
         for (a.slab = 0; a.slab < slabs; ++a.slab) MBAMD_LAUNCH_BARRIER(kernel, grid, 64, lds, stream, a);
         return slabs;
     }
+}
+
+// beagleCalculateCrossProductDerivative on the engine's patterns: the edge table -- GradEdge and, behind the edges, t_e r_k as
+// doubles -- is staged; the edges are cut into chunks (cross_chunks), one launch (the plain kernel beyond 256 entries: one per 256)
+// leaves a matrix per (block, chunk) in the result scratch, k_cross_product_sums adds them and S * S doubles come back: out[S * S] is
+// overwritten.  Synchronous.  The matrix-core kernel serves 16 .. 64 states in single precision (MBAMD_XPROD_GENERIC: the plain one).
+template <class Engine>
+inline int cross_products(Engine& e, const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
+{
+    const char* const who = "beagleCalculateCrossProductDerivative";
+    { const int rc = edge_list_begin(e, who); if (rc) return rc; }
+    for (int i = 0; i < count; ++i) {
+        const int rc = edge_check(e, who, post[i], pre[i], wIdx[i]);
+        if (rc) return rc;
+        if (!e.rateSets.has(rateIdx[i])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category rates index");
+    }
+    { const int rc = cross_check_lengths(who, lengths, count); if (rc) return rc; }
+    const int S = e.S, K = e.K;
+    const size_t SS = (size_t) S * S;
+    std::fill_n(out, SS, 0.0);
+    if (count <= 0) return BEAGLE_SUCCESS;
+    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
+    std::vector<unsigned char> table(edgeBytes + (size_t) count * K * sizeof(double), 0);
+    { const int rc = edge_list_fill(e, post, pre, count, reinterpret_cast<GradEdge*>(table.data())); if (rc) return rc; }
+    double* const tr = reinterpret_cast<double*>(table.data() + edgeBytes);
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < K; ++k) tr[(size_t) i * K + k] = lengths[i] * e.rateSets[rateIdx[i]].r[k];
+    void* d_table = nullptr;
+    { const int rc = e.stageTable(table.data(), table.size(), &d_table); if (rc) return rc; }
+    const int nb = e.Ppad / 64;
+    const int chunks = cross_chunks(count, nb, S);
+    CrossArgs a;
+    std::memset(&a, 0, sizeof a);
+    { const int rc = e.resultScratch(((size_t) chunks * nb + 1) * SS * sizeof(double), &a.partial); if (rc) return rc; }
+    a.g = e.layoutArgs();
+    a.edges = static_cast<const GradEdge*>(d_table);
+    a.tr = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_table) + edgeBytes);
+    a.q = K > 1 ? e.d_q : nullptr;
+    a.pattern_weights = e.d_pweights;
+    a.nb = nb;
+    a.edgeCount = count;
+    a.perChunk = (count + chunks - 1) / chunks;
+    const int used = (count + a.perChunk - 1) / a.perChunk;          // (the last chunks may be empty: not launched)
+    double* const d_out = a.partial + (size_t) used * nb * SS;
+    const bool mfma = S >= 16 && S <= 64 && !e.sw.xprodGeneric;
+    const int launches = e.withLayout([&](auto L) { return launch_cross_products<L(), deriv_real<L()>>(e.stream, a, used, mfma); });
+    MBAMD_LAUNCH(k_cross_product_sums, (unsigned) SS, 64, 0, e.stream, (const double*) a.partial, used * nb, (int) SS, d_out);
+    HIP_TRY(hipGetLastError());
+    e.countLaunches(launches + 1);
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    e.afterSync();
+    HIP_TRY(hipMemcpy(out, d_out, SS * sizeof(double), hipMemcpyDeviceToHost));
+    return BEAGLE_SUCCESS;
 }
 
 }  // namespace mbamd

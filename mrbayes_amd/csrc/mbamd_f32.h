@@ -334,7 +334,57 @@ private:
     void* d_preTable = nullptr;       size_t preTableCap = 0;      // the PreOp / GradEdge table of the call being served
     int lnlOperands(DerivArgs& a, int parent, int child, int prob, int wIdx, int fIdx, int cumIdx);
     DerivArgs layoutArgs() const;
-    int ensurePosteriors();
+    // f(this engine's layout as a compile-time constant): the one place that chooses among the kernels' instantiations
+    template <class F> auto withLayout(F&& f) const
+    {
+        if (s4) return f(std::integral_constant<int, DERIV_S4>());
+        if (wg) return f(std::integral_constant<int, DERIV_WG>());
+        return f(std::integral_constant<int, DERIV_LEVELS>());
+    }
+    // ---- what the shared bodies of the pre-order, gradient and cross-product calls ask of this engine (mbamd_preorder.h) ----
+    template <class E> friend int update_pre_partials(E&, const BeagleOperation*, int, int);
+    template <class E> friend int ensure_posteriors(E&);
+    template <class E> friend int edge_list_begin(E&, const char*);
+    template <class E> friend int edge_check(const E&, const char*, int, int, int);
+    template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
+    template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
+    template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    // everything queued or held runs first
+    int runQueued() { return hasWork() ? flushPending() : BEAGLE_SUCCESS; }
+    // (nothing to refuse: an engine of this kind holds one partition, and the C ABI turns a partitioned instance away itself)
+    int refuses(const char*) const { return BEAGLE_SUCCESS; }
+    // the buffer holds compact tip states / something a kernel can read (an unstored buffer is `valid`: beforeRead)
+    bool holdsTip(int b) const { return tipStates[b] != nullptr; }
+    bool readable(int b) const { return tipStates[b] || valid[b]; }
+    // the buffer as an operand: its tip states or its partials
+    const void* operandPtr(int b) const { return tipStates[b] ? (const void*) tipStates[b] : (const void*) partials[b]; }
+    float* partialsPtr(int b) const { return partials[b]; }
+    // the buffers buf(0 .. n) that a call reads are in memory (those below zero: none)
+    template <class F> int beforeRead(int n, F buf)
+    {
+        if (!nUnstored) return BEAGLE_SUCCESS;
+        std::vector<int> reads((size_t) n);
+        for (int i = 0; i < n; ++i) reads[(size_t) i] = buf(i);
+        return ensureStored(reads.data(), n);
+    }
+    // a destination holds no recipe any more and has memory (buffers of the level kernels are allocated on first use) ...
+    int beforeWrite(int d) { dropRecipe(d); return ensurePartials(d); }
+    // ... nor the exponents of a final pass
+    void afterWrite(int d) { if (d < (int) finalExpOf.size()) finalExpOf[d] = nullptr; }
+    // the PreOp / GradEdge table of a call, on the device
+    int stageTable(const void* src, size_t bytes, void** out)
+    {
+        const int rc = grow(&d_preTable, &preTableCap, bytes);
+        *out = d_preTable;
+        return rc ? rc : upload(d_preTable, src, bytes);
+    }
+    // device memory for a call's results
+    int resultScratch(size_t bytes, double** out) { const int rc = grow(&d_tmp, &tmpCap, bytes); *out = static_cast<double*>(d_tmp); return rc; }
+    // the stream was synchronised: every launch so far is complete
+    void afterSync() { syncedClock = launchClock; }
+    // launches for kernelTiming to report
+    void countLaunches(int n) { pendingLaunches += n; }
+    int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
     bool haveSite = false;
@@ -3357,253 +3407,30 @@ inline int Instance::lnlOperands(DerivArgs& a, int parent, int child, int prob, 
     return BEAGLE_SUCCESS;
 }
 
-// beagleUpdatePrePartials: the list is checked as a whole, cut into launches (pre_order_groups) and run, one launch per group.
-inline int Instance::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx)
-{
-    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
-    if (n <= 0) return BEAGLE_SUCCESS;
-    if (cumIdx != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (cumulativeScaleIndex must be BEAGLE_OP_NONE)");
-    std::vector<char> written((size_t) nBuffers, 0);
-    for (int o = 0; o < n; ++o) {
-        const BeagleOperation& b = ops[o];
-        if (b.destinationScaleWrite != BEAGLE_OP_NONE || b.destinationScaleRead != BEAGLE_OP_NONE)
-            return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (scale indices must be BEAGLE_OP_NONE)");
-        const int d = b.destinationPartials, p = b.child1Partials, sib = b.child2Partials;
-        if (d < 0 || d >= nBuffers || p < 0 || p >= nBuffers || (sib != BEAGLE_OP_NONE && (sib < 0 || sib >= nBuffers)))
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: partials index");
-        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
-            (sib != BEAGLE_OP_NONE && (b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices)))
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: matrix index");
-        if (tipStates[d]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination holds compact tip states");
-        if (tipStates[p] || (!valid[p] && !written[p])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the parent's pre-order buffer holds no partials");
-        if (sib != BEAGLE_OP_NONE && !tipStates[sib] && !valid[sib] && !written[sib])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the sibling's buffer was never written");
-        if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
-        written[d] = 1;
-    }
-    if (nUnstored) {                             // the post-order buffers the pass reads; what it writes holds no recipe afterwards
-        std::vector<int> reads;
-        for (int o = 0; o < n; ++o) { reads.push_back(ops[o].child1Partials); reads.push_back(ops[o].child2Partials); }
-        const int src = ensureStored(reads.data(), (int) reads.size());
-        if (src) return src;
-        for (int o = 0; o < n; ++o) dropRecipe(ops[o].destinationPartials);
-    }
-    std::vector<PreOp> table((size_t) n);
-    for (int o = 0; o < n; ++o) {
-        const BeagleOperation& b = ops[o];
-        const int rc = ensurePartials(b.destinationPartials);
-        if (rc) return rc;
-        PreOp& t = table[(size_t) o];
-        std::memset(&t, 0, sizeof t);
-        t.dst = partials[b.destinationPartials];
-        t.parent = partials[b.child1Partials];
-        t.mOwn = matrixPtr(b.child1TransitionMatrix);
-        t.sibKind = -1;
-        if (b.child2Partials != BEAGLE_OP_NONE) {
-            const int sib = b.child2Partials;
-            t.sibKind = tipStates[sib] ? 1 : 0;
-            t.sib = tipStates[sib] ? (const void*) tipStates[sib] : (const void*) partials[sib];
-            t.mSib = matrixPtr(b.child2TransitionMatrix);
-        }
-    }
-    int rc = grow(&d_preTable, &preTableCap, table.size() * sizeof(PreOp));
-    if (rc) return rc;
-    rc = upload(d_preTable, table.data(), table.size() * sizeof(PreOp));
-    if (rc) return rc;
-    if (preOrder.size() != (size_t) nBuffers) preOrder.assign((size_t) nBuffers, 0);
-    std::vector<int> start;
-    pre_order_groups(ops, n, nBuffers, start);
-    PreArgs a;
-    a.g = layoutArgs();
-    for (size_t gI = 0; gI + 1 < start.size(); ++gI) {
-        a.ops = static_cast<const PreOp*>(d_preTable) + start[gI];
-        const int count = start[gI + 1] - start[gI];
-        if (s4) launch_pre_partials<DERIV_S4, float>(stream, a, count);
-        else if (wg) launch_pre_partials<DERIV_WG, float>(stream, a, count);
-        else launch_pre_partials<DERIV_LEVELS, float>(stream, a, count);
-        HIP_TRY(hipGetLastError());
-        pendingLaunches += 1;
-    }
-    for (int o = 0; o < n; ++o) {
-        const int d = ops[o].destinationPartials;
-        valid[d] = 1;
-        preOrder[d] = 1;
-        if (d < (int) finalExpOf.size()) finalExpOf[d] = nullptr;
-    }
-    return BEAGLE_SUCCESS;
-}
-
-// q [K][Ppad] of the latest log-likelihood call's operands as they are now, unless d_q holds it already
-inline int Instance::ensurePosteriors()
-{
-    if (qStamp == lastLnl.stamp && d_q) return BEAGLE_SUCCESS;
-    int cum = lastLnl.cum;
-    int rc = checkIntegrate(&lastLnl.parent, lastLnl.child >= 0 ? &lastLnl.child : nullptr, &lastLnl.prob, &lastLnl.weights, &lastLnl.freqs, &cum, 1);
-    if (rc) return rc;
-    rc = grow((void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double));
-    if (rc) return rc;
-    rc = ensureStored(lastLnl.parent, lastLnl.child);
-    if (rc) return rc;
-    DerivArgs a;
-    rc = lnlOperands(a, lastLnl.parent, lastLnl.child, lastLnl.prob, lastLnl.weights, lastLnl.freqs, lastLnl.cum);
-    if (rc) return rc;
-    a.site = d_q;
-    auto kernel = s4 ? k_category_posteriors<DERIV_S4, float> : wg ? k_category_posteriors<DERIV_WG, float> : k_category_posteriors<DERIV_LEVELS, float>;
-    MBAMD_LAUNCH(kernel, (unsigned) (Ppad / 64), 64, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    qStamp = lastLnl.stamp;
-    return BEAGLE_SUCCESS;
-}
-
-// beagleCalculateEdgeDerivatives on this engine's patterns: the edges in chunks (gradient_chunk), per chunk one launch of
-// k_edge_gradient and one of k_gradient_sums, then the chunk's results come back through d_tmp.
+// The pre-order pass, the gradient in all branch lengths and the cross products: the bodies are shared with the double-precision
+// engine (mbamd_preorder.h, mbamd_crossproducts.h).
+inline int Instance::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx) { return update_pre_partials(*this, ops, n, cumIdx); }
 inline int Instance::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
                                   double* sums, double* sumsSq)
 {
-    const char* const who = "beagleCalculateEdgeDerivatives";
-    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
-    if (K > 1) {
-        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
-        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
-    }
-    for (int e = 0; e < count; ++e) {
-        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
-        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
-        if (post[e] < 0 || post[e] >= nBuffers || (!tipStates[post[e]] && !valid[post[e]])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
-        if (dmat[e] < 0 || dmat[e] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
-    }
-    if (count <= 0) return BEAGLE_SUCCESS;
-    if (nUnstored) {
-        std::vector<int> reads(post, post + count);
-        reads.insert(reads.end(), pre, pre + count);
-        const int src = ensureStored(reads.data(), (int) reads.size());
-        if (src) return src;
-    }
-    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
-    std::vector<GradEdge> table((size_t) count);
-    for (int e = 0; e < count; ++e) {
-        GradEdge& t = table[(size_t) e];
-        std::memset(&t, 0, sizeof t);
-        t.pre = partials[pre[e]];
-        t.postTip = tipStates[post[e]] ? 1 : 0;
-        t.post = tipStates[post[e]] ? (const void*) tipStates[post[e]] : (const void*) partials[post[e]];
-        t.D = matrixPtr(dmat[e]);
-    }
-    int rc = grow(&d_preTable, &preTableCap, table.size() * sizeof(GradEdge));
-    if (rc) return rc;
-    rc = upload(d_preTable, table.data(), table.size() * sizeof(GradEdge));
-    if (rc) return rc;
-    const int nb = Ppad / 64;
-    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
-    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
-    rc = grow(&d_tmp, &tmpCap, (nSite + nBlock + nOut) * sizeof(double));
-    if (rc) return rc;
-    double* const d_site_ = static_cast<double*>(d_tmp);
-    double* const d_block = d_site_ + nSite;
-    double* const d_out = d_block + nBlock;
-    std::vector<double> h(nSite + nOut);
-    GradArgs a;
-    a.g = layoutArgs();
-    a.q = K > 1 ? d_q : nullptr;
-    a.pattern_weights = d_pweights;
-    a.site = sites ? d_site_ : nullptr;
-    a.sums = d_block;
-    a.nb = nb;
-    auto kernel = s4 ? k_edge_gradient<DERIV_S4, float> : wg ? k_edge_gradient<DERIV_WG, float> : k_edge_gradient<DERIV_LEVELS, float>;
-    for (int e0 = 0; e0 < count; e0 += chunk) {
-        const int ne = std::min(chunk, count - e0);
-        a.edges = static_cast<const GradEdge*>(d_preTable) + e0;
-        a.edgeCount = ne;
-        MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, stream, a);
-        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, stream, (const double*) d_block, nb, ne, d_out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(stream));
-        syncedClock = launchClock;
-        if (sites) HIP_TRY(hipMemcpy(h.data(), d_site_, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
-        for (int e = 0; e < ne; ++e) {
-            if (sites) std::memcpy(sites + (size_t) (e0 + e) * siteStride, h.data() + (size_t) e * Ppad, (size_t) P * sizeof(double));
-            if (sums) sums[e0 + e] = h[nSite + (size_t) e];
-            if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
-        }
-    }
-    return BEAGLE_SUCCESS;
+    return edge_gradient(*this, post, pre, dmat, wIdx, count, sites, siteStride, sums, sumsSq);
 }
-
-// beagleCalculateCrossProductDerivative on this engine's patterns (mbamd_crossproducts.h): the edge table -- GradEdge and, behind
-// the edges, t_e r_k as doubles -- goes to d_preTable; the edges are cut into chunks (cross_chunks), one launch (the plain kernel
-// beyond 256 entries: one per 256) leaves a matrix per (block, chunk) in d_tmp, k_cross_product_sums adds them and S * S doubles
-// come back.
 inline int Instance::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
-    const char* const who = "beagleCalculateCrossProductDerivative";
-    if (hasWork()) { int frc = flushPending(); if (frc) return frc; }
-    if (K > 1) {
-        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
-        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
-    }
-    for (int e = 0; e < count; ++e) {
-        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
-        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
-        if (post[e] < 0 || post[e] >= nBuffers || (!tipStates[post[e]] && !valid[post[e]])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
-        if (!rateSets.has(rateIdx[e])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category rates index");
-    }
-    { const int lrc = cross_check_lengths(who, lengths, count); if (lrc) return lrc; }
-    const size_t SS = (size_t) S * S;
-    std::fill_n(out, SS, 0.0);
-    if (count <= 0) return BEAGLE_SUCCESS;
-    if (nUnstored) {
-        std::vector<int> reads(post, post + count);
-        reads.insert(reads.end(), pre, pre + count);
-        const int src = ensureStored(reads.data(), (int) reads.size());
-        if (src) return src;
-    }
-    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
-    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
-    std::vector<unsigned char> table(edgeBytes + (size_t) count * K * sizeof(double), 0);
-    GradEdge* const te = reinterpret_cast<GradEdge*>(table.data());
-    double* const tr = reinterpret_cast<double*>(table.data() + edgeBytes);
-    for (int e = 0; e < count; ++e) {
-        te[e].pre = partials[pre[e]];
-        te[e].postTip = tipStates[post[e]] ? 1 : 0;
-        te[e].post = tipStates[post[e]] ? (const void*) tipStates[post[e]] : (const void*) partials[post[e]];
-        for (int k = 0; k < K; ++k) tr[(size_t) e * K + k] = lengths[e] * rateSets[rateIdx[e]].r[k];
-    }
-    int rc = grow(&d_preTable, &preTableCap, table.size());
+    return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
+}
+// what ensure_posteriors asks for: the latest log-likelihood call's operands, checked and in memory, and room for q
+inline int Instance::posteriorOperands(DerivArgs& a)
+{
+    const LnlOperands& l = lastLnl;
+    int cum = l.cum;
+    int rc = checkIntegrate(&l.parent, l.child >= 0 ? &l.child : nullptr, &l.prob, &l.weights, &l.freqs, &cum, 1);
     if (rc) return rc;
-    rc = upload(d_preTable, table.data(), table.size());
+    rc = grow((void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double));
     if (rc) return rc;
-    const int nb = Ppad / 64;
-    const int chunks = cross_chunks(count, nb, S);
-    rc = grow(&d_tmp, &tmpCap, ((size_t) chunks * nb + 1) * SS * sizeof(double));
+    rc = ensureStored(l.parent, l.child);
     if (rc) return rc;
-    CrossArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.g = layoutArgs();
-    a.edges = static_cast<const GradEdge*>(d_preTable);
-    a.tr = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_preTable) + edgeBytes);
-    a.q = K > 1 ? d_q : nullptr;
-    a.pattern_weights = d_pweights;
-    a.partial = static_cast<double*>(d_tmp);
-    a.nb = nb;
-    a.edgeCount = count;
-    a.perChunk = (count + chunks - 1) / chunks;
-    const int used = (count + a.perChunk - 1) / a.perChunk;          // (the last chunks may be empty: not launched)
-    double* const d_out = a.partial + (size_t) used * nb * SS;
-    const bool mfma = S >= 16 && S <= 64 && !sw.xprodGeneric;
-    int launches;
-    if (s4) launches = launch_cross_products<DERIV_S4, float>(stream, a, used, false);
-    else if (wg) launches = launch_cross_products<DERIV_WG, float>(stream, a, used, mfma);
-    else launches = launch_cross_products<DERIV_LEVELS, float>(stream, a, used, mfma);
-    MBAMD_LAUNCH(k_cross_product_sums, (unsigned) SS, 64, 0, stream, (const double*) a.partial, used * nb, (int) SS, d_out);
-    HIP_TRY(hipGetLastError());
-    pendingLaunches += launches + 1;
-    HIP_TRY(hipStreamSynchronize(stream));
-    syncedClock = launchClock;
-    HIP_TRY(hipMemcpy(out, d_out, SS * sizeof(double), hipMemcpyDeviceToHost));
-    return BEAGLE_SUCCESS;
+    return lnlOperands(a, l.parent, l.child, l.prob, l.weights, l.freqs, l.cum);
 }
 
 // Branch-length derivatives over one edge: one launch of k_edge_derivatives on this engine's partials layout, then a wait.  Never the
@@ -3632,8 +3459,10 @@ inline int Instance::edgeDerivatives(int parent, int child, int prob, int d1, in
     a.sums = h_deriv_dev + (size_t) 3 * Ppad;
     a.first = 0; a.last = P;
     a.sumStride = nb;
-    auto kernel = s4 ? k_edge_derivatives<DERIV_S4, float> : wg ? k_edge_derivatives<DERIV_WG, float> : k_edge_derivatives<DERIV_LEVELS, float>;
-    MBAMD_LAUNCH(kernel, (unsigned) nb, 64, 0, stream, a);
+    withLayout([&](auto L) {
+        auto kernel = k_edge_derivatives<L(), float>;
+        MBAMD_LAUNCH(kernel, (unsigned) nb, 64, 0, stream, a);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     syncedClock = launchClock;

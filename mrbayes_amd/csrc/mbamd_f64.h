@@ -148,7 +148,39 @@ private:
     double* d_grad = nullptr;              // a gradient chunk's per-site values, block sums and sums
     size_t qCap = 0, gradCap = 0;
     DerivArgs layoutArgs() const;
-    int ensurePosteriors();
+    // ---- what the shared bodies of the pre-order, gradient and cross-product calls ask of this engine (mbamd_preorder.h); they also
+    // use partialsPtr() and matrixPtr() below ----
+    template <class E> friend int update_pre_partials(E&, const BeagleOperation*, int, int);
+    template <class E> friend int ensure_posteriors(E&);
+    template <class E> friend int edge_list_begin(E&, const char*);
+    template <class E> friend int edge_check(const E&, const char*, int, int, int);
+    template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
+    template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
+    template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    // everything queued runs first
+    int runQueued() { return flushQueue(); }
+    // pattern partitions are not served
+    int refuses(const char* who) const { return parts.size() > 1 ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance") : BEAGLE_SUCCESS; }
+    // the buffer holds compact tip states / something a kernel can read (`valid` covers tips here)
+    bool holdsTip(int b) const { return isTip[b] != 0; }
+    bool readable(int b) const { return valid[b] != 0; }
+    // the buffer as an operand: its tip states or its partials
+    const void* operandPtr(int b) const { return isTip[b] ? (const void*) statesPtr(b) : (const void*) partialsPtr(b); }
+    // (every buffer is in memory, allocated, and carries nothing a write would have to clear: a tip destination is refused)
+    template <class F> int beforeRead(int, F) { return BEAGLE_SUCCESS; }
+    int beforeWrite(int) { return BEAGLE_SUCCESS; }
+    void afterWrite(int) {}
+    // the PreOp / GradEdge table of a call, on the device
+    int stageTable(const void* src, size_t bytes, void** out) { return stage(src, bytes, out); }
+    // device memory for a call's results
+    int resultScratch(size_t bytes, double** out) { const int rc = grow_device(stream, (void**) &d_grad, &gradCap, bytes, bytes); *out = d_grad; return rc; }
+    // (nothing is kept of a synchronisation)
+    void afterSync() {}
+    // launches for kernelTiming to report
+    void countLaunches(int n) { preLaunches += (uint64_t) n; }
+    // f(this engine's layout as a compile-time constant)
+    template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }
+    int posteriorOperands(DerivArgs& a);
     // ---- matrix updates waiting to run ----
     // Matrix updates are queued like operation lists: MrBayes updates a codon model's eigen parts one call each (src/mbbeagle.c:1475-1486),
     // and three launches of 200 matrices fill the chip worse than one of 600.  Every other entry point flushes (flushQueue); a second
@@ -1216,7 +1248,8 @@ inline int Engine64::edgeDerivatives(const int* parent, const int* child, const 
     derivValid = true;
     return finite ? BEAGLE_SUCCESS : BEAGLE_ERROR_FLOATING_POINT;
 }
-// ---- the pre-order pass and the gradient in all branch lengths (mbamd_preorder.h), as Instance's ----
+// ---- the pre-order pass, the gradient in all branch lengths and the cross products: the bodies are shared with the single-precision
+// engine (mbamd_preorder.h, mbamd_crossproducts.h); here the plain kernels run in double precision ----
 inline DerivArgs Engine64::layoutArgs() const
 {
     DerivArgs a;
@@ -1225,210 +1258,33 @@ inline DerivArgs Engine64::layoutArgs() const
     a.first = 0; a.last = P;
     return a;
 }
-inline int Engine64::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx)
+inline int Engine64::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx) { return update_pre_partials(*this, ops, n, cumIdx); }
+inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq)
 {
-    { const int rcq = flushQueue(); if (rcq) return rcq; }
-    if (n <= 0) return BEAGLE_SUCCESS;
-    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: not on a multi-partition instance");
-    if (cumIdx != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (cumulativeScaleIndex must be BEAGLE_OP_NONE)");
-    std::vector<char> written((size_t) nBuffers, 0);
-    for (int o = 0; o < n; ++o) {
-        const BeagleOperation& b = ops[o];
-        if (b.destinationScaleWrite != BEAGLE_OP_NONE || b.destinationScaleRead != BEAGLE_OP_NONE)
-            return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (scale indices must be BEAGLE_OP_NONE)");
-        const int d = b.destinationPartials, p = b.child1Partials, sib = b.child2Partials;
-        if (d < 0 || d >= nBuffers || p < 0 || p >= nBuffers || (sib != BEAGLE_OP_NONE && (sib < 0 || sib >= nBuffers)))
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: partials index");
-        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
-            (sib != BEAGLE_OP_NONE && (b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices)))
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: matrix index");
-        if (isTip[d]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination holds compact tip states");
-        if (written[p] ? false : (isTip[p] || !valid[p])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the parent's pre-order buffer holds no partials");
-        if (sib != BEAGLE_OP_NONE && !valid[sib] && !written[sib]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the sibling's buffer was never written");
-        if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
-        written[d] = 1;
-    }
-    std::vector<PreOp> table((size_t) n);
-    for (int o = 0; o < n; ++o) {
-        const BeagleOperation& b = ops[o];
-        PreOp& t = table[(size_t) o];
-        std::memset(&t, 0, sizeof t);
-        t.dst = partialsPtr(b.destinationPartials);
-        t.parent = partialsPtr(b.child1Partials);
-        t.mOwn = matrixPtr(b.child1TransitionMatrix);
-        t.sibKind = -1;
-        if (b.child2Partials != BEAGLE_OP_NONE) {
-            const int sib = b.child2Partials;
-            const bool tip = isTip[sib] && !written[sib];
-            t.sibKind = tip ? 1 : 0;
-            t.sib = tip ? (const void*) statesPtr(sib) : (const void*) partialsPtr(sib);
-            t.mSib = matrixPtr(b.child2TransitionMatrix);
-        }
-    }
-    void* d_table = nullptr;
-    { const int rc = stage(table.data(), table.size() * sizeof(PreOp), &d_table); if (rc) return rc; }
-    if (preOrder.size() != (size_t) nBuffers) preOrder.assign((size_t) nBuffers, 0);
-    std::vector<int> start;
-    pre_order_groups(ops, n, nBuffers, start);
-    PreArgs a;
-    a.g = layoutArgs();
-    for (size_t gI = 0; gI + 1 < start.size(); ++gI) {
-        a.ops = static_cast<const PreOp*>(d_table) + start[gI];
-        launch_pre_partials<DERIV_F64, double>(stream, a, start[gI + 1] - start[gI]);
-        HIP_TRY(hipGetLastError());
-        preLaunches++;
-    }
-    for (int o = 0; o < n; ++o) {
-        const int d = ops[o].destinationPartials;
-        valid[d] = 1;
-        isTip[d] = 0;
-        preOrder[d] = 1;
-    }
-    return BEAGLE_SUCCESS;
+    return edge_gradient(*this, post, pre, dmat, wIdx, count, sites, (size_t) P, sums, sumsSq);
 }
-inline int Engine64::ensurePosteriors()
+inline int Engine64::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
-    if (qStamp == lastLnl.stamp && d_q) return BEAGLE_SUCCESS;
+    return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
+}
+// what ensure_posteriors asks for: the latest log-likelihood call's operands, checked, and room for q
+inline int Engine64::posteriorOperands(DerivArgs& a)
+{
     const LnlOperands& l = lastLnl;
     if (l.parent < 0 || l.parent >= nBuffers || !valid[l.parent] || isTip[l.parent] || l.weights < 0 || l.weights >= nEigen || l.freqs < 0 || l.freqs >= nEigen ||
         (l.child >= 0 && (l.child >= nBuffers || !valid[l.child] || l.prob < 0 || l.prob >= nMatrices)) || (l.cum != BEAGLE_OP_NONE && (l.cum < 0 || l.cum >= nScale)))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeDerivatives: the operands of the latest log-likelihood call");
     { const int rc = grow_device(stream, (void**) &d_q, &qCap, (size_t) K * Ppad * sizeof(double), (size_t) K * Ppad * sizeof(double)); if (rc) return rc; }
-    DerivArgs a = layoutArgs();
+    a = layoutArgs();
     a.parent = partialsPtr(l.parent);
     if (l.child >= 0) {
         a.child_tip = isTip[l.child] ? 1 : 0;
-        a.child = isTip[l.child] ? (const void*) statesPtr(l.child) : (const void*) partialsPtr(l.child);
+        a.child = operandPtr(l.child);
         a.matrix[0] = matrixPtr(l.prob);
     }
     a.weights = d_weights + (size_t) l.weights * K;
     a.freqs = d_freqs + (size_t) l.freqs * S;
     if (l.cum != BEAGLE_OP_NONE) a.cum = d_scale + (size_t) l.cum * Ppad;
-    a.site = d_q;
-    auto kernel = k_category_posteriors<DERIV_F64, double>;
-    MBAMD_LAUNCH(kernel, (unsigned) (Ppad / 64), 64, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    qStamp = lastLnl.stamp;
-    return BEAGLE_SUCCESS;
-}
-inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq)
-{
-    const char* const who = "beagleCalculateEdgeDerivatives";
-    { const int rcq = flushQueue(); if (rcq) return rcq; }
-    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
-    if (K > 1) {
-        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
-        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
-    }
-    for (int e = 0; e < count; ++e) {
-        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
-        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
-        if (post[e] < 0 || post[e] >= nBuffers || !valid[post[e]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
-        if (dmat[e] < 0 || dmat[e] >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
-    }
-    if (count <= 0) return BEAGLE_SUCCESS;
-    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
-    std::vector<GradEdge> table((size_t) count);
-    for (int e = 0; e < count; ++e) {
-        GradEdge& t = table[(size_t) e];
-        std::memset(&t, 0, sizeof t);
-        t.pre = partialsPtr(pre[e]);
-        t.postTip = isTip[post[e]] ? 1 : 0;
-        t.post = isTip[post[e]] ? (const void*) statesPtr(post[e]) : (const void*) partialsPtr(post[e]);
-        t.D = matrixPtr(dmat[e]);
-    }
-    void* d_table = nullptr;
-    { const int rc = stage(table.data(), table.size() * sizeof(GradEdge), &d_table); if (rc) return rc; }
-    const int nb = Ppad / 64;
-    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
-    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
-    { const size_t bytes = (nSite + nBlock + nOut) * sizeof(double); const int rc = grow_device(stream, (void**) &d_grad, &gradCap, bytes, bytes); if (rc) return rc; }
-    double* const d_block = d_grad + nSite;
-    double* const d_out = d_block + nBlock;
-    std::vector<double> h(nSite + nOut);
-    GradArgs a;
-    a.g = layoutArgs();
-    a.q = K > 1 ? d_q : nullptr;
-    a.pattern_weights = d_pweights;
-    a.site = sites ? d_grad : nullptr;
-    a.sums = d_block;
-    a.nb = nb;
-    auto kernel = k_edge_gradient<DERIV_F64, double>;
-    for (int e0 = 0; e0 < count; e0 += chunk) {
-        const int ne = std::min(chunk, count - e0);
-        a.edges = static_cast<const GradEdge*>(d_table) + e0;
-        a.edgeCount = ne;
-        MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, stream, a);
-        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, stream, (const double*) d_block, nb, ne, d_out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (sites) HIP_TRY(hipMemcpy(h.data(), d_grad, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
-        for (int e = 0; e < ne; ++e) {
-            if (sites) std::memcpy(sites + (size_t) (e0 + e) * P, h.data() + (size_t) e * Ppad, (size_t) P * sizeof(double));
-            if (sums) sums[e0 + e] = h[nSite + (size_t) e];
-            if (sumsSq) sumsSq[e0 + e] = h[nSite + (size_t) ne + e];
-        }
-    }
-    return BEAGLE_SUCCESS;
-}
-// beagleCalculateCrossProductDerivative (mbamd_crossproducts.h), as Instance's: the plain kernel in double precision
-inline int Engine64::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
-{
-    const char* const who = "beagleCalculateCrossProductDerivative";
-    { const int rcq = flushQueue(); if (rcq) return rcq; }
-    if (parts.size() > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
-    if (K > 1) {
-        if (lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
-        if (lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
-    }
-    for (int e = 0; e < count; ++e) {
-        if (K > 1 && wIdx[e] != lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
-        if (pre[e] < 0 || pre[e] >= nBuffers || (size_t) pre[e] >= preOrder.size() || !preOrder[pre[e]])
-            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
-        if (post[e] < 0 || post[e] >= nBuffers || !valid[post[e]]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
-        if (!rateSets.has(rateIdx[e])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category rates index");
-    }
-    { const int lrc = cross_check_lengths(who, lengths, count); if (lrc) return lrc; }
-    const size_t SS = (size_t) S * S;
-    std::fill_n(out, SS, 0.0);
-    if (count <= 0) return BEAGLE_SUCCESS;
-    if (K > 1) { const int rc = ensurePosteriors(); if (rc) return rc; }
-    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
-    std::vector<unsigned char> table(edgeBytes + (size_t) count * K * sizeof(double), 0);
-    GradEdge* const te = reinterpret_cast<GradEdge*>(table.data());
-    double* const tr = reinterpret_cast<double*>(table.data() + edgeBytes);
-    for (int e = 0; e < count; ++e) {
-        te[e].pre = partialsPtr(pre[e]);
-        te[e].postTip = isTip[post[e]] ? 1 : 0;
-        te[e].post = isTip[post[e]] ? (const void*) statesPtr(post[e]) : (const void*) partialsPtr(post[e]);
-        for (int k = 0; k < K; ++k) tr[(size_t) e * K + k] = lengths[e] * rateSets[rateIdx[e]].r[k];
-    }
-    void* d_table = nullptr;
-    { const int rc = stage(table.data(), table.size(), &d_table); if (rc) return rc; }
-    const int nb = Ppad / 64;
-    const int chunks = cross_chunks(count, nb, S);
-    { const size_t bytes = ((size_t) chunks * nb + 1) * SS * sizeof(double); const int rc = grow_device(stream, (void**) &d_grad, &gradCap, bytes, bytes); if (rc) return rc; }
-    CrossArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.g = layoutArgs();
-    a.edges = static_cast<const GradEdge*>(d_table);
-    a.tr = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_table) + edgeBytes);
-    a.q = K > 1 ? d_q : nullptr;
-    a.pattern_weights = d_pweights;
-    a.partial = d_grad;
-    a.nb = nb;
-    a.edgeCount = count;
-    a.perChunk = (count + chunks - 1) / chunks;
-    const int used = (count + a.perChunk - 1) / a.perChunk;          // (the last chunks may be empty: not launched)
-    double* const d_out = d_grad + (size_t) used * nb * SS;
-    const int launches = launch_cross_products<DERIV_F64, double>(stream, a, used, false);
-    MBAMD_LAUNCH(k_cross_product_sums, (unsigned) SS, 64, 0, stream, (const double*) d_grad, used * nb, (int) SS, d_out);
-    HIP_TRY(hipGetLastError());
-    preLaunches += (uint64_t) launches + 1;
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(out, d_out, SS * sizeof(double), hipMemcpyDeviceToHost));
     return BEAGLE_SUCCESS;
 }
 inline int Engine64::getSites(double* out)

@@ -21,7 +21,9 @@
 
 #include <math.h>
 
-#include "mbamd_host.h"          // beagle.h, <algorithm>, <vector>
+#include <type_traits>
+
+#include "mbamd_host.h"          // beagle.h, fail / HIP_TRY, <algorithm>, <cstring>, <vector>
 #include "mbamd_derivatives.h"
 
 namespace mbamd {
@@ -270,6 +272,19 @@ k_gradient_sums(const double* __restrict__ sums, int nb, int edges, double* __re
 }
 
 // ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
+// The calls are written once, as templates on the engine (Instance, Engine64).  They read its members of the same name -- the sizes
+// S, K, P, Ppad, nBuffers, nMatrices, stream, valid, preOrder, lastLnl, qStamp, d_q, d_pweights, rateSets, sw, layoutArgs(),
+// partialsPtr(), matrixPtr() -- and ask it for the rest through a few small hooks, which each engine keeps in one block:
+//     runQueued, refuses                  before anything else: what is queued or held runs; an instance the calls do not serve
+//     holdsTip, readable, operandPtr      a buffer holds compact tip states / something to read; where that is
+//     beforeRead, beforeWrite, afterWrite around the partials buffers of a call
+//     stageTable, resultScratch           device memory for the call's table and for its results
+//     afterSync, countLaunches            bookkeeping
+//     withLayout                          f(layout as a compile-time constant)
+//     posteriorOperands                   the checked operands of the latest log-likelihood call
+
+// the arithmetic type of a layout
+template <int LAYOUT> using deriv_real = std::conditional_t<LAYOUT == DERIV_F64, double, float>;
 
 // What an engine remembers of its latest beagleCalculate{Root,Edge}LogLikelihoods call (integers only): the operands q is made of.
 struct LnlOperands {
@@ -328,6 +343,188 @@ inline int gradient_chunk(int count, int Ppad, bool sites)
 {
     const size_t per = (size_t) 2 * (Ppad / 64) + 2 + (sites ? (size_t) Ppad : 0);
     return (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
+}
+
+// beagleUpdatePrePartials: the list is checked as a whole, cut into launches (pre_order_groups) and run, one launch per group.
+template <class Engine>
+inline int update_pre_partials(Engine& e, const BeagleOperation* ops, int n, int cumIdx)
+{
+    { const int rc = e.runQueued(); if (rc) return rc; }
+    if (n <= 0) return BEAGLE_SUCCESS;
+    { const int rc = e.refuses("beagleUpdatePrePartials"); if (rc) return rc; }
+    if (cumIdx != BEAGLE_OP_NONE) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (cumulativeScaleIndex must be BEAGLE_OP_NONE)");
+    const int nBuffers = e.nBuffers, nMatrices = e.nMatrices;
+    std::vector<char> written((size_t) nBuffers, 0);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        if (b.destinationScaleWrite != BEAGLE_OP_NONE || b.destinationScaleRead != BEAGLE_OP_NONE)
+            return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePrePartials: pre-order buffers are always self-normalised (scale indices must be BEAGLE_OP_NONE)");
+        const int d = b.destinationPartials, p = b.child1Partials, sib = b.child2Partials;
+        if (d < 0 || d >= nBuffers || p < 0 || p >= nBuffers || (sib != BEAGLE_OP_NONE && (sib < 0 || sib >= nBuffers)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: partials index");
+        if (b.child1TransitionMatrix < 0 || b.child1TransitionMatrix >= nMatrices ||
+            (sib != BEAGLE_OP_NONE && (b.child2TransitionMatrix < 0 || b.child2TransitionMatrix >= nMatrices)))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: matrix index");
+        // (a destination never holds tip states, so neither does a buffer this list has written)
+        if (e.holdsTip(d)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination holds compact tip states");
+        if (e.holdsTip(p) || (!e.valid[p] && !written[p])) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the parent's pre-order buffer holds no partials");
+        if (sib != BEAGLE_OP_NONE && !e.readable(sib) && !written[sib])
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the sibling's buffer was never written");
+        if (d == p || d == sib) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleUpdatePrePartials: the destination is an operand");
+        written[d] = 1;
+    }
+    { const int rc = e.beforeRead(2 * n, [&](int i) { return i & 1 ? ops[i / 2].child2Partials : ops[i / 2].child1Partials; }); if (rc) return rc; }
+    std::vector<PreOp> table((size_t) n);
+    for (int o = 0; o < n; ++o) {
+        const BeagleOperation& b = ops[o];
+        const int rc = e.beforeWrite(b.destinationPartials);
+        if (rc) return rc;
+        PreOp& t = table[(size_t) o];
+        std::memset(&t, 0, sizeof t);
+        t.dst = e.partialsPtr(b.destinationPartials);
+        t.parent = e.partialsPtr(b.child1Partials);
+        t.mOwn = e.matrixPtr(b.child1TransitionMatrix);
+        t.sibKind = -1;
+        if (b.child2Partials != BEAGLE_OP_NONE) {
+            t.sibKind = e.holdsTip(b.child2Partials) ? 1 : 0;
+            t.sib = e.operandPtr(b.child2Partials);
+            t.mSib = e.matrixPtr(b.child2TransitionMatrix);
+        }
+    }
+    void* d_table = nullptr;
+    { const int rc = e.stageTable(table.data(), table.size() * sizeof(PreOp), &d_table); if (rc) return rc; }
+    if (e.preOrder.size() != (size_t) nBuffers) e.preOrder.assign((size_t) nBuffers, 0);
+    std::vector<int> start;
+    pre_order_groups(ops, n, nBuffers, start);
+    PreArgs a;
+    a.g = e.layoutArgs();
+    for (size_t gI = 0; gI + 1 < start.size(); ++gI) {
+        a.ops = static_cast<const PreOp*>(d_table) + start[gI];
+        const int count = start[gI + 1] - start[gI];
+        e.withLayout([&](auto L) { launch_pre_partials<L(), deriv_real<L()>>(e.stream, a, count); });
+        HIP_TRY(hipGetLastError());
+        e.countLaunches(1);
+    }
+    for (int o = 0; o < n; ++o) {
+        const int d = ops[o].destinationPartials;
+        e.valid[d] = 1;
+        e.preOrder[d] = 1;
+        e.afterWrite(d);
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// q [K][Ppad] of the latest log-likelihood call's operands as they are now, unless d_q holds it already
+template <class Engine>
+inline int ensure_posteriors(Engine& e)
+{
+    if (e.qStamp == e.lastLnl.stamp && e.d_q) return BEAGLE_SUCCESS;
+    DerivArgs a;
+    { const int rc = e.posteriorOperands(a); if (rc) return rc; }
+    a.site = e.d_q;
+    e.withLayout([&](auto L) {
+        auto kernel = k_category_posteriors<L(), deriv_real<L()>>;
+        MBAMD_LAUNCH(kernel, (unsigned) (e.Ppad / 64), 64, 0, e.stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    e.qStamp = e.lastLnl.stamp;
+    return BEAGLE_SUCCESS;
+}
+
+// What the calls over a list of (post, pre) edges share -- the gradient below, the cross products of mbamd_crossproducts.h.
+// Before the list is looked at:
+template <class Engine>
+inline int edge_list_begin(Engine& e, const char* who)
+{
+    { const int rc = e.runQueued(); if (rc) return rc; }
+    { const int rc = e.refuses(who); if (rc) return rc; }
+    if (e.K > 1) {
+        if (e.lastLnl.count == 0) return fail(BEAGLE_ERROR_GENERAL, who, "no log-likelihood was calculated yet: the category posteriors come from its operands");
+        if (e.lastLnl.count > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "the latest log-likelihood call had more than one subset");
+    }
+    return BEAGLE_SUCCESS;
+}
+// ... the checks of one edge, in front of the call's own:
+template <class Engine>
+inline int edge_check(const Engine& e, const char* who, int post, int pre, int wIdx)
+{
+    if (e.K > 1 && wIdx != e.lastLnl.weights) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "category weights index differs from the latest log-likelihood call's");
+    if (pre < 0 || pre >= e.nBuffers || (size_t) pre >= e.preOrder.size() || !e.preOrder[pre])
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pre-order index names a buffer that no pre-order operation wrote (or that was overwritten since)");
+    if (post < 0 || post >= e.nBuffers || !e.readable(post)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "post-order buffer");
+    return BEAGLE_SUCCESS;
+}
+// ... and once the list is good: its buffers are in memory, q is that of the latest log-likelihood call, the edges are in `table`
+template <class Engine>
+inline int edge_list_fill(Engine& e, const int* post, const int* pre, int count, GradEdge* table)
+{
+    { const int rc = e.beforeRead(2 * count, [&](int i) { return i < count ? post[i] : pre[i - count]; }); if (rc) return rc; }
+    if (e.K > 1) { const int rc = ensure_posteriors(e); if (rc) return rc; }
+    for (int i = 0; i < count; ++i) {
+        std::memset(&table[i], 0, sizeof table[i]);
+        table[i].pre = e.partialsPtr(pre[i]);
+        table[i].postTip = e.holdsTip(post[i]) ? 1 : 0;
+        table[i].post = e.operandPtr(post[i]);
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// beagleCalculateEdgeDerivatives on the engine's patterns: the edges in chunks (gradient_chunk), per chunk one launch of k_edge_gradient
+// and one of k_gradient_sums, then the chunk's results come back.  Synchronous; sums[i] and sumsSq[i] are the weighted sums of edge i,
+// sites (or null) takes d_c of edge i at sites[i * siteStride + c].
+template <class Engine>
+inline int edge_gradient(Engine& e, const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
+                         double* sums, double* sumsSq)
+{
+    const char* const who = "beagleCalculateEdgeDerivatives";
+    { const int rc = edge_list_begin(e, who); if (rc) return rc; }
+    for (int i = 0; i < count; ++i) {
+        const int rc = edge_check(e, who, post[i], pre[i], wIdx[i]);
+        if (rc) return rc;
+        if (dmat[i] < 0 || dmat[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
+    }
+    if (count <= 0) return BEAGLE_SUCCESS;
+    std::vector<GradEdge> table((size_t) count);
+    { const int rc = edge_list_fill(e, post, pre, count, table.data()); if (rc) return rc; }
+    for (int i = 0; i < count; ++i) table[(size_t) i].D = e.matrixPtr(dmat[i]);
+    void* d_table = nullptr;
+    { const int rc = e.stageTable(table.data(), table.size() * sizeof(GradEdge), &d_table); if (rc) return rc; }
+    const int P = e.P, Ppad = e.Ppad, nb = Ppad / 64;
+    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
+    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
+    double* d_site = nullptr;
+    { const int rc = e.resultScratch((nSite + nBlock + nOut) * sizeof(double), &d_site); if (rc) return rc; }
+    double* const d_block = d_site + nSite;
+    double* const d_out = d_block + nBlock;
+    std::vector<double> h(nSite + nOut);
+    GradArgs a;
+    a.g = e.layoutArgs();
+    a.q = e.K > 1 ? e.d_q : nullptr;
+    a.pattern_weights = e.d_pweights;
+    a.site = sites ? d_site : nullptr;
+    a.sums = d_block;
+    a.nb = nb;
+    for (int e0 = 0; e0 < count; e0 += chunk) {
+        const int ne = std::min(chunk, count - e0);
+        a.edges = static_cast<const GradEdge*>(d_table) + e0;
+        a.edgeCount = ne;
+        e.withLayout([&](auto L) {
+            auto kernel = k_edge_gradient<L(), deriv_real<L()>>;
+            MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, e.stream, a);
+        });
+        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, e.stream, (const double*) d_block, nb, ne, d_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(e.stream));
+        e.afterSync();
+        if (sites) HIP_TRY(hipMemcpy(h.data(), d_site, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < ne; ++i) {
+            if (sites) std::memcpy(sites + (size_t) (e0 + i) * siteStride, h.data() + (size_t) i * Ppad, (size_t) P * sizeof(double));
+            if (sums) sums[e0 + i] = h[nSite + (size_t) i];
+            if (sumsSq) sumsSq[e0 + i] = h[nSite + (size_t) ne + i];
+        }
+    }
+    return BEAGLE_SUCCESS;
 }
 
 }  // namespace mbamd

@@ -326,9 +326,17 @@ def _raises(lib, code, call, *args, **kwargs):
         call(*args, **kwargs)
     assert err.value.code == code, (err.value.code, code)
     assert lib.last_error()
+    return err.value.code, lib.last_error()
 
 
 def check_argument_errors(lib, double_precision=False):
+    """Every bad call is refused with the expected status; returns (status, message) of each, in order: the two engines run one
+    body per call (mbamd_preorder.h, mbamd_crossproducts.h), so they answer alike -- check_engines_agree."""
+    seen = []
+
+    def raises(code, call, *args, **kwargs):
+        seen.append(_raises(lib, code, call, *args, **kwargs))
+
     div = division(4, 2, 130)
     t = div.tree
     nodes = list(t.all_down_pass)
@@ -338,7 +346,7 @@ def check_argument_errors(lib, double_precision=False):
         inst = bd.inst
         cross = inst.calculate_cross_products
         # more than one category and no log-likelihood call yet
-        _raises(lib, bg.BEAGLE_ERROR_GENERAL, cross, edge_lengths=lengths, **cross_indices(bd, nodes))
+        raises(bg.BEAGLE_ERROR_GENERAL, cross, edge_lengths=lengths, **cross_indices(bd, nodes))
         bd.LogLike(0)
         bd.AcceptMove(0)
         bd.RateMatrixCrossProducts(0)
@@ -346,26 +354,26 @@ def check_argument_errors(lib, double_precision=False):
         n = len(nodes)
         assert cross(edge_lengths=lengths, **ix)[0] == 0
         # a buffer for the sums of squares
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, cross, edge_lengths=lengths, squared=True, **ix)
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, cross, edge_lengths=lengths, squared=True, **ix)
         # a weights index different from the remembered one
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, weights=[bd.cijkScratchIndex] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, weights=[bd.cijkScratchIndex] * n))
         # a pre index that no pre-order operation wrote; one that beagleUpdatePartials has overwritten since
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, pres=[bd.preOrderStartIndex] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, pres=[bd.preOrderStartIndex] * n))
         ops = bd.PreOrderOperations(0)
         victim = bd.preOrderIndex[t.root_left]
         inst.update_partials(np.array([[victim, bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, bd.condLikeIndex[0][0], bd.tiProbsIndex[0][0],
                                         bd.condLikeIndex[0][1], bd.tiProbsIndex[0][1]]], dtype=np.int32), bg.BEAGLE_OP_NONE)
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **ix)
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **ix)
         inst.update_pre_partials(ops)                                                   # (all of them pre-order buffers again)
         assert cross(edge_lengths=lengths, **ix)[0] == 0
         # an invalid post buffer, an unknown rates index
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, posts=[10 ** 6] * n))
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, posts=[-1] * n))
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, rates=[7] * n))
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, rates=[-1] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, posts=[10 ** 6] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, posts=[-1] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, rates=[7] * n))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths, **dict(ix, rates=[-1] * n))
         # an edge length that is negative or not finite
         for bad in (-1e-3, float("nan"), float("inf")):
-            _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths[:-1] + [bad], **ix)
+            raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, cross, edge_lengths=lengths[:-1] + [bad], **ix)
         # null arrays
         arrays = [np.asarray(ix[key], dtype=np.int32) for key in ("posts", "pres", "rates", "weights")] + [np.asarray(lengths, dtype=np.float64)]
         out = np.empty((4, 4))
@@ -374,12 +382,13 @@ def check_argument_errors(lib, double_precision=False):
             ptrs[missing] = None
             rc = inst.lib.beagleCalculateCrossProductDerivative(inst.id, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], n, ptrs[5], None)
             assert rc == bg.BEAGLE_ERROR_OUT_OF_RANGE and lib.last_error(), (missing, rc)
+            seen.append((rc, lib.last_error()))
         # the latest log-likelihood call had two subsets
         top = t.root_left
         one = dict(parents=[bd.condLikeIndex[0][top]], children=[bd.condLikeIndex[0][t.root]], probs=[bd.tiProbsIndex[0][top]],
                    weights=[bd.cijkIndex[0]], freqs=[bd.cijkIndex[0]], cums=[bd.siteScalerIndex[0]])
         inst.calculate_edge_log_likelihoods(**{key: value * 2 for key, value in one.items()})
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, cross, edge_lengths=lengths, **ix)
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, cross, edge_lengths=lengths, **ix)
         inst.calculate_edge_log_likelihoods(**one)
         assert cross(edge_lengths=lengths, **ix)[0] == 0
     finally:
@@ -394,17 +403,23 @@ def check_argument_errors(lib, double_precision=False):
         inst.set_pattern_weights(div.weights)
         inst.set_pattern_partitions(2, np.concatenate([np.zeros(70, dtype=np.int32), np.ones(60, dtype=np.int32)]))
         assert inst.child_count() == 2
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.calculate_cross_products, [0], [N + 1], [0], [0], [0.1])
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.calculate_cross_products, [0], [N + 1], [0], [0], [0.1])
     finally:
         inst.finalize()
+    return seen
+
+
+def check_engines_agree(lib):
+    single, double = check_argument_errors(lib), check_argument_errors(lib, double_precision=True)
+    assert len(single) == len(double)
+    for i, (s, d) in enumerate(zip(single, double)):
+        assert s == d, (i, s, d)
 
 
 def test_argument_errors_on_emulation(emu):
-    check_argument_errors(emu)
-    check_argument_errors(emu, double_precision=True)
+    check_engines_agree(emu)
 
 
 @pytest.mark.gpu
 def test_argument_errors(gpu):
-    check_argument_errors(gpu)
-    check_argument_errors(gpu, double_precision=True)
+    check_engines_agree(gpu)

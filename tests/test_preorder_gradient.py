@@ -280,16 +280,24 @@ def _raises(lib, code, call, *args, **kwargs):
         call(*args, **kwargs)
     assert err.value.code == code, (err.value.code, code)
     assert lib.last_error()
+    return err.value.code, lib.last_error()
 
 
 def check_argument_errors(lib, double_precision=False):
+    """Every bad call is refused with the expected status; returns (status, message) of each, in order: the two engines run one
+    body per call (mbamd_preorder.h, mbamd_crossproducts.h), so they answer alike -- check_engines_agree."""
+    seen = []
+
+    def raises(code, call, *args, **kwargs):
+        seen.append(_raises(lib, code, call, *args, **kwargs))
+
     div = division(4, 2, 130)
     t = div.tree
     bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, pre_order=True)
     try:
         inst = bd.inst
         # more than one category and no log-likelihood call yet
-        _raises(lib, bg.BEAGLE_ERROR_GENERAL, inst.calculate_edge_gradient, **gradient_indices(bd))
+        raises(bg.BEAGLE_ERROR_GENERAL, inst.calculate_edge_gradient, **gradient_indices(bd))
         bd.LogLike(0)
         bd.AcceptMove(0)
         bd.BranchGradient(0)
@@ -299,27 +307,27 @@ def check_argument_errors(lib, double_precision=False):
         for field in (1, 2):
             bad = ops.copy()
             bad[3, field] = bd.nodeScalerIndex[0][t.root_left]
-            _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, bad)
+            raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, bad)
             assert "self-normalised" in lib.last_error()
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, ops, bd.siteScalerIndex[0])
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, ops, bd.siteScalerIndex[0])
         # a weights index different from the remembered one
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, weights=[bd.cijkScratchIndex] * len(ix["posts"])))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, weights=[bd.cijkScratchIndex] * len(ix["posts"])))
         # a pre index that no pre-order operation wrote; one that beagleUpdatePartials has overwritten since
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, pres=[bd.preOrderStartIndex] * len(ix["posts"])))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, pres=[bd.preOrderStartIndex] * len(ix["posts"])))
         victim = bd.preOrderIndex[t.root_left]
         inst.update_partials(np.array([[victim, bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, bd.condLikeIndex[0][0], bd.tiProbsIndex[0][0],
                                         bd.condLikeIndex[0][1], bd.tiProbsIndex[0][1]]], dtype=np.int32), bg.BEAGLE_OP_NONE)
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **ix)
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **ix)
         inst.update_pre_partials(ops)                                                   # (all of them pre-order buffers again)
         assert inst.calculate_edge_gradient(sites=False, **ix)[0] == 0
         # a destination holding compact tip states; out-of-range buffer and matrix indices
         for row, field, value in ((1, 0, bd.condLikeIndex[0][0]), (1, 0, 10 ** 6), (1, 3, -2), (1, 5, 10 ** 6), (1, 4, 10 ** 6), (1, 6, -3)):
             bad = ops.copy()
             bad[row, field] = value
-            _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.update_pre_partials, bad)
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, dmats=[10 ** 6] * len(ix["posts"])))
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, posts=[10 ** 6] * len(ix["posts"])))
-        _raises(lib, bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.set_differential_matrix, 10 ** 6, np.zeros((div.ncat, 4, 4)))
+            raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.update_pre_partials, bad)
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, dmats=[10 ** 6] * len(ix["posts"])))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.calculate_edge_gradient, **dict(ix, posts=[10 ** 6] * len(ix["posts"])))
+        raises(bg.BEAGLE_ERROR_OUT_OF_RANGE, inst.set_differential_matrix, 10 ** 6, np.zeros((div.ncat, 4, 4)))
     finally:
         bd.finalize()
     # a multi-partition instance serves none of the three
@@ -333,22 +341,28 @@ def check_argument_errors(lib, double_precision=False):
         inst.set_pattern_partitions(2, np.concatenate([np.zeros(70, dtype=np.int32), np.ones(60, dtype=np.int32)]))
         assert inst.child_count() == 2
         one = np.array([[N + 1, bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE, N, 0, bg.BEAGLE_OP_NONE, bg.BEAGLE_OP_NONE]], dtype=np.int32)
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, one)
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.set_differential_matrix, 0, np.zeros((K, S, S)))
-        _raises(lib, bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.calculate_edge_gradient, [0], [N + 1], [0], [0])
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.update_pre_partials, one)
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.set_differential_matrix, 0, np.zeros((K, S, S)))
+        raises(bg.BEAGLE_ERROR_NO_IMPLEMENTATION, inst.calculate_edge_gradient, [0], [N + 1], [0], [0])
     finally:
         inst.finalize()
+    return seen
+
+
+def check_engines_agree(lib):
+    single, double = check_argument_errors(lib), check_argument_errors(lib, double_precision=True)
+    assert len(single) == len(double)
+    for i, (s, d) in enumerate(zip(single, double)):
+        assert s == d, (i, s, d)
 
 
 def test_argument_errors_on_emulation(emu):
-    check_argument_errors(emu)
-    check_argument_errors(emu, double_precision=True)
+    check_engines_agree(emu)
 
 
 @pytest.mark.gpu
 def test_argument_errors(gpu):
-    check_argument_errors(gpu)
-    check_argument_errors(gpu, double_precision=True)
+    check_engines_agree(gpu)
 
 
 # ---- pattern shards -----------------------------------------------------------------------------------------------------------
