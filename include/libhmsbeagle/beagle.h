@@ -246,6 +246,34 @@ BEAGLE_DLLEXPORT int beagleUpdateTransitionMatrices(int instance, int eigenIndex
 BEAGLE_DLLEXPORT int beagleSetTransitionMatrix(int instance, int matrixIndex, const double* inMatrix, double paddedValue);
 BEAGLE_DLLEXPORT int beagleGetTransitionMatrix(int instance, int matrixIndex, double* outMatrix);
 
+/* Transition matrices made out of transition matrices, on the device (upstream BEAGLE's names and argument order; MrBayes calls
+ * none of them).  Common to the three calls: they are asynchronous on the instance's stream, like beagleUpdateTransitionMatrices;
+ * count == 0 is a successful no-op; a NULL array, a negative count or an index outside [0, matrixBufferCount) is
+ * BEAGLE_ERROR_OUT_OF_RANGE; EVERY entry is checked before any matrix is written, so a refused call leaves all matrices as they
+ * were.  A result is an ordinary matrix buffer: every copy the engine keeps of it is written, and nothing tells it from the same
+ * values given to beagleSetTransitionMatrix.  On a sharded or multi-partition instance every child engine does the same.
+ *
+ * beagleConvolveTransitionMatrices: for entry u and every category k
+ *     R_k[i,j] = sum_l A_k[i,l] B_k[l,j]     A = firstIndices[u] (the segment on the from-state / parent side), B = secondIndices[u],
+ *                                            R = resultIndices[u]; [category][from][to] as beagleGetTransitionMatrix returns them
+ * -- the matrix P(t1; Q1) P(t2; Q2) of a branch that crosses a change of rate matrix.  Nothing is clamped: the buffers may hold P'
+ * or P''.  The operands are read as stored (fp32 on the single-precision engine, fp64 on the double-precision one), products and
+ * sums are formed in double, and ONE rounding goes to the stored type.  Entries take effect in list order: a result may be an
+ * operand of a later entry (P1 P2 -> tmp, tmp P3 -> out), and of two entries that write one result the later wins; entries that
+ * do not depend on one another run in one launch.  resultIndices[u] equal to firstIndices[u] or secondIndices[u] is
+ * BEAGLE_ERROR_OUT_OF_RANGE (no convolution in place, as upstream). */
+BEAGLE_DLLEXPORT int beagleConvolveTransitionMatrices(int instance, const int* firstIndices, const int* secondIndices,
+                                                      const int* resultIndices, int matrixCount);
+/* R_k = A_k^T for every category, exact; A = inputIndices[u], R = resultIndices[u], which may be the same buffer.  List order and
+ * launches as for beagleConvolveTransitionMatrices. */
+BEAGLE_DLLEXPORT int beagleTransposeTransitionMatrices(int instance, const int* inputIndices, const int* resultIndices, int matrixCount);
+/* The batch form of beagleSetTransitionMatrix: inMatrices holds `count` matrices of categoryCount * stateCount * stateCount
+ * doubles, matrix u for buffer matrixIndices[u]; paddedValues is ignored, as paddedValue is there (it may be NULL).  The stored
+ * values, every copy, are bit-identical to `count` single calls in list order (of an index named twice the later matrix stays);
+ * the call makes one host-to-device transfer. */
+BEAGLE_DLLEXPORT int beagleSetTransitionMatrices(int instance, const int* matrixIndices, const double* inMatrices,
+                                                 const double* paddedValues, int count);
+
 /* ---------------------------------------------------------------------------------------------
  * partial likelihoods and scale factors
  * ------------------------------------------------------------------------------------------- */

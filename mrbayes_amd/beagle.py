@@ -61,7 +61,8 @@ EXPORTS = [
     "beagleFinalizeInstance", "beagleFinalize", "beagleSetTipStates", "beagleSetTipPartials", "beagleSetPartials",
     "beagleGetPartials", "beagleSetEigenDecomposition", "beagleSetStateFrequencies", "beagleSetCategoryWeights",
     "beagleSetCategoryRates", "beagleSetPatternWeights", "beagleUpdateTransitionMatrices",
-    "beagleSetTransitionMatrix", "beagleGetTransitionMatrix", "beagleUpdatePartials", "beagleWaitForPartials",
+    "beagleSetTransitionMatrix", "beagleGetTransitionMatrix", "beagleConvolveTransitionMatrices", "beagleTransposeTransitionMatrices",
+    "beagleSetTransitionMatrices", "beagleUpdatePartials", "beagleWaitForPartials",
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
@@ -135,6 +136,9 @@ class BeagleLibrary:
         L.beagleUpdateTransitionMatrices.argtypes = [C.c_int, C.c_int, _ip, _ip, _ip, _dp, C.c_int]
         L.beagleSetTransitionMatrix.argtypes = [C.c_int, C.c_int, _dp, C.c_double]
         L.beagleGetTransitionMatrix.argtypes = [C.c_int, C.c_int, _dp]
+        L.beagleConvolveTransitionMatrices.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int]
+        L.beagleTransposeTransitionMatrices.argtypes = [C.c_int, _ip, _ip, C.c_int]
+        L.beagleSetTransitionMatrices.argtypes = [C.c_int, _ip, _dp, _dp, C.c_int]
         L.beagleUpdatePartials.argtypes = [C.c_int, C.POINTER(BeagleOperation), C.c_int, C.c_int]
         L.beagleWaitForPartials.argtypes = [C.c_int, _ip, C.c_int]
         L.beagleAccumulateScaleFactors.argtypes = [C.c_int, _ip, C.c_int, C.c_int]
@@ -310,6 +314,30 @@ class BeagleInstance:
         out = np.empty((self.category_count, self.state_count, self.state_count))
         self._chk(self.lib.beagleGetTransitionMatrix(self.id, idx, out.ctypes.data_as(_dp)), "beagleGetTransitionMatrix")
         return out
+
+    def convolve_transition_matrices(self, first_indices, second_indices, result_indices):
+        """result[u] = first[u] x second[u] per category, on the device, in list order (a result may be an operand of a later
+        entry; never of its own).  Asynchronous."""
+        a, b, r = _i(first_indices), _i(second_indices), _i(result_indices)
+        if not len(a) == len(b) == len(r):
+            raise ValueError("convolve_transition_matrices: the three index lists differ in length")
+        self._chk(self.lib.beagleConvolveTransitionMatrices(self.id, a.ctypes.data_as(_ip), b.ctypes.data_as(_ip), r.ctypes.data_as(_ip), len(r)),
+                  "beagleConvolveTransitionMatrices")
+
+    def transpose_transition_matrices(self, input_indices, result_indices):
+        """result[u] = the transpose of input[u] per category, on the device (result[u] == input[u] is allowed).  Asynchronous."""
+        a, r = _i(input_indices), _i(result_indices)
+        if len(a) != len(r):
+            raise ValueError("transpose_transition_matrices: the two index lists differ in length")
+        self._chk(self.lib.beagleTransposeTransitionMatrices(self.id, a.ctypes.data_as(_ip), r.ctypes.data_as(_ip), len(r)),
+                  "beagleTransposeTransitionMatrices")
+
+    def set_transition_matrices(self, indices, matrices):
+        """The batch form of set_transition_matrix: matrices [count][categories][states][states], one transfer."""
+        idx = _i(indices)
+        a = _d(matrices).reshape(len(idx), self.category_count, self.state_count, self.state_count)
+        self._chk(self.lib.beagleSetTransitionMatrices(self.id, idx.ctypes.data_as(_ip), a.ctypes.data_as(_dp), None, len(idx)),
+                  "beagleSetTransitionMatrices")
 
     # ---- partials / scaling -----------------------------------------------------------------------
     def update_partials(self, operations, cumulative_scale_index=BEAGLE_OP_NONE):

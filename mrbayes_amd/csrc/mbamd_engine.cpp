@@ -684,6 +684,31 @@ int beagleGetTransitionMatrix(int instance, int matrixIndex, double* outMatrix)
     if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
     return c->getMatrix(matrixIndex, outMatrix);
 }
+// ---- matrices made out of matrices (mbamd_matrix_products.h; semantics: beagle.h).  Pattern shards and v3 partition children each
+// hold their own matrices: every child does the same, as for beagleSetTransitionMatrix.  The list is checked by the engine, the same
+// body on both (matrix_list_check): a child never writes before the whole list passed, and all children hold the same buffers.
+int beagleConvolveTransitionMatrices(int instance, const int* firstIndices, const int* secondIndices, const int* resultIndices, int matrixCount)
+{
+    GET_INSTANCE(instance);
+    API_TRACE("beagleConvolveTransitionMatrices(count=%d)", matrixCount);
+    if (h->f64) return h->f64->convolveMatrices(firstIndices, secondIndices, resultIndices, matrixCount);
+    EACH_ENGINE(true, c->convolveMatrices(firstIndices, secondIndices, resultIndices, matrixCount));
+}
+int beagleTransposeTransitionMatrices(int instance, const int* inputIndices, const int* resultIndices, int matrixCount)
+{
+    GET_INSTANCE(instance);
+    API_TRACE("beagleTransposeTransitionMatrices(count=%d)", matrixCount);
+    if (h->f64) return h->f64->transposeMatrices(inputIndices, resultIndices, matrixCount);
+    EACH_ENGINE(true, c->transposeMatrices(inputIndices, resultIndices, matrixCount));
+}
+int beagleSetTransitionMatrices(int instance, const int* matrixIndices, const double* inMatrices, const double* paddedValues, int count)
+{
+    (void) paddedValues;
+    GET_INSTANCE(instance);
+    API_TRACE("beagleSetTransitionMatrices(count=%d)", count);
+    if (h->f64) return h->f64->setMatrices(matrixIndices, inMatrices, count);
+    EACH_ENGINE(true, c->setMatrices(matrixIndices, inMatrices, count));
+}
 int beagleUpdatePartials(int instance, const BeagleOperation* operations, int operationCount, int cumulativeScaleIndex)
 {
     StatTimer st_(ST_PARTIALS);

@@ -18,6 +18,7 @@
 #include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
+#include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
 
 namespace mbamd {
 
@@ -154,6 +155,10 @@ struct Instance {
                        const int* d1Idx = nullptr, const int* d2Idx = nullptr);
     int setMatrix(int idx, const double* in);
     int getMatrix(int idx, double* out);
+    // matrices made out of matrices (mbamd_matrix_products.h; semantics: beagle.h): asynchronous, every stored copy of a result written
+    int convolveMatrices(const int* first, const int* second, const int* result, int count);
+    int transposeMatrices(const int* input, const int* result, int count);
+    int setMatrices(const int* idx, const double* in, int count);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
     int flushPending(bool keepPath = false);
     // scale buffers, whichever of their forms holds them (scaleState 0 / 1 / 2 in the arenas, an int32 buffer on the level kernels)
@@ -349,8 +354,28 @@ private:
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
+    template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued or held runs first
     int runQueued() { return hasWork() ? flushPending() : BEAGLE_SUCCESS; }
+    // ---- ... and the bodies of the matrix-product calls (mbamd_matrix_products.h) ----
+    // where the copies of a matrix buffer lie: the device form of setMatrix / getMatrix
+    MatrixLayoutF32 matrixLayout() const { return MatrixLayoutF32{S, SP, K, mfma ? T : 0, wg ? wgTabFloats : (size_t) 0}; }
+    // what setMatrix does before a matrix changes: the matrices an unstored-subtree recipe needs are copied first
+    int beforeMatrixWrite() { return snapPlan ? flushSnapshot() : BEAGLE_SUCCESS; }
+    // the entry table of a list, staged as launchMatrices stages its jobs: in the pinned ring, which the kernel reads over the host link
+    // (no copy launch in front of the kernel); a table too large for a quarter of the ring goes through device memory like a PreOp table
+    int stageMatrixTable(const void* src, size_t bytes, const void** out)
+    {
+        if (((bytes + 63) & ~(size_t) 63) <= stage.capacity() / 4) return stageDirect(src, bytes, out);
+        void* d = nullptr;
+        const int rc = stageTable(src, bytes, &d);
+        *out = d;
+        return rc;
+    }
+    // the host image of a matrix buffer, every copy, from [K][S][S] doubles: what setMatrix uploads (h: matrixValues() floats)
+    size_t matrixValues() const { return matrixFloats; }
+    void matrixImage(const double* in, float* h) const;
     // (nothing to refuse: an engine of this kind holds one partition, and the C ABI turns a partitioned instance away itself)
     int refuses(const char*) const { return BEAGLE_SUCCESS; }
     // the buffer holds compact tip states / something a kernel can read (an unstored buffer is `valid`: beforeRead)
@@ -1236,11 +1261,9 @@ inline int Instance::launchMatrices(const MatrixJob* jobs, int count)
     return BEAGLE_SUCCESS;
 }
 
-inline int Instance::setMatrix(int idx, const double* in)
+inline void Instance::matrixImage(const double* in, float* h) const
 {
-    if (idx < 0 || idx >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTransitionMatrix: matrix index");
-    if (snapPlan) { int src = flushSnapshot(); if (src) return src; }
-    std::vector<float> h(matrixFloats, 0.0f);
+    std::fill(h, h + matrixFloats, 0.0f);
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < S; ++i)
             for (int j = 0; j < S; ++j) {
@@ -1248,13 +1271,29 @@ inline int Instance::setMatrix(int idx, const double* in)
                 h[(size_t) k * SP * SP + (size_t) j * SP + i] = v;
                 if (mfma)
                     h[(size_t) K * SP * SP + ((size_t) (k * NT + i / 32) * T + j / 2) * 64 + (i % 32) + 32 * (j % 2)] = v;
-                if (wg) wg_table_put(h.data() + wgTabFloats + (size_t) k * wg_table_floats(S), S, i, j, v);
+                if (wg) wg_table_put(h + wgTabFloats + (size_t) k * wg_table_floats(S), S, i, j, v);
             }
     if (wg)
         for (int k = 0; k < K; ++k)
-            for (int i = 0; i < S; ++i) wg_table_put_missing(h.data() + wgTabFloats + (size_t) k * wg_table_floats(S), S, i);
+            for (int i = 0; i < S; ++i) wg_table_put_missing(h + wgTabFloats + (size_t) k * wg_table_floats(S), S, i);
+}
+inline int Instance::setMatrix(int idx, const double* in)
+{
+    if (idx < 0 || idx >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTransitionMatrix: matrix index");
+    if (snapPlan) { int src = flushSnapshot(); if (src) return src; }
+    std::vector<float> h(matrixFloats);
+    matrixImage(in, h.data());
     return upload(matrixPtr(idx), h.data(), matrixFloats * sizeof(float));
 }
+inline int Instance::convolveMatrices(const int* first, const int* second, const int* result, int count)
+{
+    return matrix_list_run(*this, "beagleConvolveTransitionMatrices", true, first, second, result, count);
+}
+inline int Instance::transposeMatrices(const int* input, const int* result, int count)
+{
+    return matrix_list_run(*this, "beagleTransposeTransitionMatrices", false, input, (const int*) nullptr, result, count);
+}
+inline int Instance::setMatrices(const int* idx, const double* in, int count) { return matrix_list_set(*this, "beagleSetTransitionMatrices", idx, in, count); }
 
 inline int Instance::getMatrix(int idx, double* out)
 {

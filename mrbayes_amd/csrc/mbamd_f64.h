@@ -30,6 +30,7 @@
 #include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient <DERIV_F64, double>: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
+#include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
 
 namespace mbamd {
 
@@ -61,6 +62,10 @@ public:
     // in: [K][S][S] row = from-state (BEAGLE's order)
     int setMatrix(int idx, const double* m);
     int getMatrix(int idx, double* out);
+    // matrices made out of matrices (mbamd_matrix_products.h; semantics: beagle.h): asynchronous, both stored copies of a result written
+    int convolveMatrices(const int* first, const int* second, const int* result, int count);
+    int transposeMatrices(const int* input, const int* result, int count);
+    int setMatrices(const int* idx, const double* in, int count);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
     // (operations `stride` bytes apart, queued: see the definition)
     int updatePartialsEx(const void* opsRaw, size_t stride, int n, const int* partition, const int* cumOf);
@@ -157,8 +162,20 @@ private:
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
+    template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued runs first
     int runQueued() { return flushQueue(); }
+    // ---- ... and the bodies of the matrix-product calls (mbamd_matrix_products.h) ----
+    // where the two copies of a matrix buffer lie: the device form of setMatrix / getMatrix
+    MatrixLayoutF64 matrixLayout() const { return MatrixLayoutF64{S, SPAD, K}; }
+    // (setMatrix runs the queues before a matrix changes: runQueued has)
+    int beforeMatrixWrite() { return BEAGLE_SUCCESS; }
+    // the entry table of a list, staged as runMatrices stages its jobs
+    int stageMatrixTable(const void* src, size_t bytes, const void** out) { void* d = nullptr; const int rc = stage(src, bytes, &d); *out = d; return rc; }
+    // the host image of a matrix buffer, both copies, from [K][S][S] doubles: what setMatrix uploads (h: matrixValues() doubles)
+    size_t matrixValues() const { return matDoubles; }
+    void matrixImage(const double* m, double* h) const;
     // pattern partitions are not served
     int refuses(const char* who) const { return parts.size() > 1 ? fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance") : BEAGLE_SUCCESS; }
     // the buffer holds compact tip states / something a kernel can read (`valid` covers tips here)
@@ -533,11 +550,9 @@ inline int Engine64::updateMatricesMulti(const int* eigenIdx, const int* rateIdx
     }
     return BEAGLE_SUCCESS;
 }
-inline int Engine64::setMatrix(int idx, const double* m)
+inline void Engine64::matrixImage(const double* m, double* h) const
 {
-    { const int rcq = flushQueue(); if (rcq) return rcq; }
-    if (idx < 0 || idx >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTransitionMatrix: matrix index");
-    std::vector<double> h(matDoubles, 0.0);
+    std::fill(h, h + matDoubles, 0.0);
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < S; ++i)
             for (int j = 0; j < S; ++j) {
@@ -545,8 +560,24 @@ inline int Engine64::setMatrix(int idx, const double* m)
                 h[((size_t) k * S + i) * S + j] = v;
                 h[(size_t) K * S * S + ((size_t) k * S + j) * SPAD + i] = v;
             }
+}
+inline int Engine64::setMatrix(int idx, const double* m)
+{
+    { const int rcq = flushQueue(); if (rcq) return rcq; }
+    if (idx < 0 || idx >= nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetTransitionMatrix: matrix index");
+    std::vector<double> h(matDoubles);
+    matrixImage(m, h.data());
     return upload(matrixPtr(idx), h.data(), matDoubles * sizeof(double));
 }
+inline int Engine64::convolveMatrices(const int* first, const int* second, const int* result, int count)
+{
+    return matrix_list_run(*this, "beagleConvolveTransitionMatrices", true, first, second, result, count);
+}
+inline int Engine64::transposeMatrices(const int* input, const int* result, int count)
+{
+    return matrix_list_run(*this, "beagleTransposeTransitionMatrices", false, input, (const int*) nullptr, result, count);
+}
+inline int Engine64::setMatrices(const int* idx, const double* in, int count) { return matrix_list_set(*this, "beagleSetTransitionMatrices", idx, in, count); }
 inline int Engine64::getMatrix(int idx, double* out)
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
