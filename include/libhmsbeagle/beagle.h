@@ -492,10 +492,16 @@ BEAGLE_DLLEXPORT int mbamdGetKernelTiming(int instance, double* outMilliseconds,
  * log-likelihood behind them as one launch, out[4] lists compiled for the tree-walk kernel, out[5] their operations.  (Counters for
  * tests and MBAMD_STATS; a facade or a double-precision instance reports zeros.) */
 BEAGLE_DLLEXPORT int mbamdGetListCounts(int instance, long* out6);
-/* Launches of the 4-state tree-walk kernel since the instance was made: out[0] on its plain instantiation (whole-tree lists: one
- * wave, every entry an operation, no prefetch, wait, barrier or stored exponent), out[1] on the generic one.  (As above: for tests;
+/* Launches of the 4-state tree-walk kernel since the instance was made: out[0] on its plain instantiations (whole-tree lists:
+ * every entry an operation, no prefetch, wait or stored exponent; one wave or several, mbamdGetPlainWaveCounts), out[1] on the generic one.  (As above: for tests;
  * a facade or a double-precision instance reports zeros; a null pointer is BEAGLE_ERROR_OUT_OF_RANGE.) */
 BEAGLE_DLLEXPORT int mbamdGetWalkCounts(int instance, long* out2);
+/* The launches on the plain instantiations by waves per workgroup: out[W - 1], W = 1 ... 8, launches of plain programs of W waves (a
+ * whole-tree list cut over W > 1 waves runs the plain loop on each, values that cross waves travel through LDS; a list that would need
+ * an eviction, a prefetch or a stored exponent at that geometry runs on the generic instantiation and is counted there).  (For tests:
+ * the sums over the engines behind the instance; a double-precision instance reports zeros; a null pointer is
+ * BEAGLE_ERROR_OUT_OF_RANGE.) */
+BEAGLE_DLLEXPORT int mbamdGetPlainWaveCounts(int instance, long* out8);
 /* Tip pairs (operations on two compact tips) of whole-tree 4-state lists are not stored by the plain tree-walk kernel: the buffer keeps
  * a recipe and is recomputed, bit for bit, before the first call that reads it (MBAMD_STORE_TIP_PAIRS=1 stores everything).  Since the
  * instance was made: out[0] buffers launches left unstored, out[1] buffers materialised since, out[2] launches that materialised them.

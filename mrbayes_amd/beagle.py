@@ -67,7 +67,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
-    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
+    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
@@ -158,6 +158,7 @@ class BeagleLibrary:
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdGetPlainWaveCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetSubtreeRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetStepTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
@@ -562,6 +563,12 @@ class BeagleInstance:
         """(launches of the 4-state walk kernel's plain instantiation, launches of the generic one)"""
         out = (C.c_long * 2)()
         self._chk(self.lib.mbamdGetWalkCounts(self.id, out), "mbamdGetWalkCounts")
+        return tuple(int(v) for v in out)
+
+    def get_plain_wave_counts(self):
+        """launches of the 4-state walk kernel's plain instantiations by waves per workgroup: element W - 1, W = 1 ... 8"""
+        out = (C.c_long * 8)()
+        self._chk(self.lib.mbamdGetPlainWaveCounts(self.id, out), "mbamdGetPlainWaveCounts")
         return tuple(int(v) for v in out)
 
     def get_recompute_counts(self):

@@ -1120,6 +1120,14 @@ int mbamdGetWalkCounts(int instance, long* out2)
     in->walkCounts(out2);
     return BEAGLE_SUCCESS;
 }
+int mbamdGetPlainWaveCounts(int instance, long* out8)
+{
+    GET_INSTANCE_NOFLUSH(instance);
+    if (!out8) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetPlainWaveCounts: null output");
+    for (int w = 0; w < MBAMD_W4_MAXW; ++w) out8[w] = 0;
+    if (h->f64) return BEAGLE_SUCCESS;
+    EACH_ENGINE(false, (c->plainWaveCounts(out8), BEAGLE_SUCCESS));       // (children: the sums over them)
+}
 int mbamdGetRecomputeCounts(int instance, long* out3)
 {
     GET_INSTANCE_NOFLUSH(instance);

@@ -90,6 +90,7 @@ struct Plan {
     struct Segment {                             // tree-walk path: one launch per hazard-free segment
         size_t first; int W, entries, nslots, tail = 2;
         bool plain = false, peel = false;        // 4-state walk: nothing rare in it (Walk4Template::plain / peel) -- k_walk4_t<Walk4Args, true>
+        bool waves = false;                      // ... cut over W > 1 waves (Walk4Template::waves) -- k_walk4_t<Walk4Args, true, true>; nslots: of the workgroup
     };
     std::vector<Segment> segments;               // (Walk4Entry index of its program in d_table, geometry)
     std::vector<Walk4Entry> inlineProg;          // 4-state walk: a short single-segment program travels in the kernel arguments instead
@@ -196,7 +197,8 @@ struct Instance {
     int kernelTiming(double* ms, long* launches, int reset);
     int stepTiming(double* ms, long* steps, int reset);
     void listCounts(long out6[6]) const { const long c[6] = {listsTotal, listsPath, forkedPaths, fusedPaths, listsWalked, opsWalked}; std::copy(c, c + 6, out6); }
-    void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of k_walk4_t<Walk4Args, true> / of the generic instantiations
+    void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of the plain instantiations of k_walk4_t (one wave or several) / of the generic ones
+    void plainWaveCounts(long out[MBAMD_W4_MAXW]) const { for (int w = 0; w < MBAMD_W4_MAXW; ++w) out[w] += walksPlainByW[w]; }   // ... of the plain ones by waves per workgroup (out[W - 1]; added: the sums over engines)
     int walkTrace(long long* out, int maxSteps, int* outSteps, int* outWaves);
     // tip-pair buffers launches left unstored / buffers materialised since / launches that materialised them (mbamdGetRecomputeCounts);
     // the same for the subtrees of three and four tips (mbamdGetSubtreeRecomputeCounts)
@@ -229,7 +231,7 @@ private:
     unsigned estride = 0;            // bytes between blocks
     std::vector<int32_t*> wideScale; // cumulative exponents int32 [K][Ppad], allocated on first use
     std::vector<char> scaleState;    // 0 = never written (zero), 1 = node exponents in the arena, 2 = cumulative (wide)
-    int lastWalkW = 0, lastWalkSlots = 0, lastWalkEntries = 0, lastWalkPhases = 0;
+    int lastWalkW = 0, lastWalkSlots = 0, lastWalkEntries = 0, lastWalkPhases = 0, lastWalkCrossing = 0;
     bool walkCumFresh = false;       // the cumulative buffer of the list being submitted holds nothing yet (store, do not add)
     // ---- small subtrees a whole-tree launch did not store (MBAMD_W4_NOSTORE, mbamd_walk4.h).  Such a buffer stays `valid`: it carries a RECIPE
     // -- its compact tips, its one to three operations with their scale modes (Walk4Recipe: a closure, no inner buffer is named), and its
@@ -517,6 +519,7 @@ private:
     uint64_t planClock = 0;
     int layoutEpoch = 0;             // bumped whenever a buffer changes between compact-tip and partials form
     long planHits = 0, planMisses = 0, fusedPaths = 0, heldPaths = 0, forkedPaths = 0, listsTotal = 0, listsPath = 0, opsWalked = 0, listsWalked = 0;
+    long walksPlainByW[MBAMD_W4_MAXW] = {};      // walksPlain by waves per workgroup (mbamdGetPlainWaveCounts)
     long walksPlain = 0, walksGeneric = 0;       // k_walk4_t launches: the plain instantiation / the generic ones (mbamdGetWalkCounts); materialising launches (ensureStored) are not counted
 
     // ---- helpers ----------------------------------------------------------------------------
@@ -840,6 +843,18 @@ inline Instance::~Instance()
 // Tree-walk geometry.  The grid is (pattern blocks) x (categories) workgroups of W waves; each wave owns `slots` LDS
 // slots of 1 KiB.  W and the slot count are chosen so that the whole grid is resident at once when the chip allows it:
 // few blocks -> more tree parallelism per block, many blocks -> single-wave workgroups with deep slot stacks.
+#define MBAMD_W4_PLAIN_WAVES_PER_CU 32    // eight waves per SIMD: beyond that the grid is not resident
+#define MBAMD_W4_PLAIN_MAXW 4            // (the sweep's largest)
+// microseconds per entry and wave of the plain 4-state loop against the waves resident on a CU: measured on the MI355X at DNA 500 x
+// 20 000 and 1000 x 50 000, W = 1 ... 4 (profiles/walk4_plain_waves.txt section 3), linear between the points and beyond the last
+static inline double walk4_entry_us(double wavesPerCU)
+{
+    static const double x[] = {4.9, 9.8, 12.2, 14.7, 19.6, 24.4}, y[] = {0.354, 0.395, 0.428, 0.485, 0.542, 0.747};
+    if (wavesPerCU <= x[0]) return y[0];
+    int i = 1;
+    while (i < 5 && wavesPerCU > x[i]) ++i;
+    return y[i - 1] + (y[i] - y[i - 1]) * (wavesPerCU - x[i - 1]) / (x[i] - x[i - 1]);
+}
 inline int Instance::configureWalk()
 {
     int numCU = 256;
@@ -848,6 +863,7 @@ inline int Instance::configureWalk()
     const int maxLds = 160 * 1024;
     if (s4 && (hipFuncSetAttribute((const void*) k_walk4_t<Walk4Args>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
                hipFuncSetAttribute((const void*) k_walk4_t<Walk4Args, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
+               hipFuncSetAttribute((const void*) k_walk4_t<Walk4Args, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
                hipFuncSetAttribute((const void*) k_walk4_t<Walk4ArgsInline>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess))
         (void) hipGetLastError();
     if (wg) {
@@ -889,6 +905,31 @@ inline int Instance::configureWalk()
     w4.forward = true;
     w4.safeWaits = sw.walkSafe;
     if (sw.walkSmallPhase) w4.smallPhase = std::max(1, *sw.walkSmallPhase);
+    // Whole-tree lists on the plain loop (Walk4Builder::plainWaves) have a geometry of their own.  Their time is one wave's serial chain
+    // of entries, each with an exposed scalar-load round trip: more waves per workgroup shorten the chain, but every wave more on a CU
+    // makes an entry slower (at 24 waves per CU 1.7 times what it is at 12), and the whole grid must stay resident.  The LDS of a
+    // workgroup's share of the CU is ONE pool of slots, nothing in front of them; a list that does not fit it without an eviction, or
+    // whose cut does not win against one wave, is tried on fewer waves and then gets the geometry above.
+    // How many: the measured time per entry and wave against the waves on a CU (profiles/walk4_plain_waves.txt section 3) says what W
+    // waves of n / W entries would take; the W with the least, and per W the longest wave that still beats one wave by 5 %.
+    {
+        const double wpc = (double) wgs / numCU;
+        double bestTime = walk4_entry_us(wpc);
+        w4.plainWaves = 1;
+        for (int w = 2; w <= MBAMD_W4_PLAIN_MAXW; ++w) {
+            w4.plainShare[w] = (int) (1024.0 * 0.95 * walk4_entry_us(wpc) / walk4_entry_us(wpc * w));
+            if (perCU * w > MBAMD_W4_PLAIN_WAVES_PER_CU) continue;                 // (the whole grid resident)
+            const double tw = walk4_entry_us(wpc * w) / w;
+            if (tw < bestTime) { bestTime = tw; w4.plainWaves = w; }
+        }
+        w4.plainDescend = !sw.walkWaves;
+    }
+    if (sw.walkWaves) w4.plainWaves = W;
+    if (sw.noPlainWalk) w4.plainWaves = 0;
+    // (a sixteenth of the share kept back: 12 slots of the 12.2 KiB that 13 workgroups per CU leave each ran as 12 workgroups per CU and
+    //  a second round, profiles/walk4_plain_waves.txt; forced: the pool is that many)
+    w4.plainSlots = std::min(250, sw.maxLdsSlots ? slots : (ldsPerWG - ldsPerWG / 16) / 1024);
+    if (sw.walkPlainMinOps) w4.plainMinOps = std::max(1, *sw.walkPlainMinOps);
     if (sw.verbose) std::fprintf(stderr, "[mbamd] tree walk: %ld workgroups (%d per CU), up to %d waves x %d slots\n", wgs, perCU, W, slots);
     return BEAGLE_SUCCESS;
 }
@@ -1783,6 +1824,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         key.reserve(seg.size() * 3 + 4);
         key.push_back((int) seg.size()); key.push_back(w4.maxW); key.push_back(w4.maxSlots + 256 * w4.maxSlots1);
         key.push_back(w4.prefetchDistance * 2 + (w4.safeWaits ? 1 : 0));
+        key.push_back(w4.plainWaves + 16 * w4.plainSlots); key.push_back(w4.plainMinOps + 64 * w4.plainShare[std::max(2, std::min(8, w4.plainWaves))] + (w4.plainDescend ? 1 << 20 : 0));
         {
             std::vector<int>& writer = w4writer;          // buffer -> operation of this segment that writes it (-1 outside this block)
             // (4-state walk) per operation: the tips of its subtree if that is compact tips and operations of this segment alone and has at
@@ -1837,7 +1879,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         Plan::Segment sg;
         sg.first = w4table.size();
         sg.W = t.W; sg.entries = t.entries; sg.nslots = t.nslots; sg.tail = t.tail;
-        sg.plain = t.plain && !wg; sg.peel = t.peel;
+        sg.plain = t.plain && !wg; sg.peel = t.peel; sg.waves = sg.plain && t.waves;
         plan.segments.push_back(sg);
         w4table.resize(sg.first + t.prog.size());
         // bytes per buffer inside a block / tile, bytes per LDS slot
@@ -1846,7 +1888,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         const uint32_t pbuf = wg ? (uint32_t) K * slotb : (uint32_t) ((size_t) (Ppad / 64) * K);
         const uint32_t ebuf = (uint32_t) K * 64u, mbuf = wg ? (uint32_t) (matrixFloats * 4) : (uint32_t) K * 64u;
         int prevKept = -1;                           // (20/61-state walk) slot the previous operation of the same program kept its result in
-        w4entryOf.assign(seg.size(), -1);            // (4-state walk) operation -> its entry, for the recipes of a one-wave plain program
+        w4entryOf.assign(seg.size(), -1);            // (4-state walk) operation -> its entry, for the recipes of a plain program (entries are filled wave by wave: a subtree with an inner operation on a LATER wave than its own finds -1 there and is stored, `placed` below)
         for (size_t i = 0; i < t.prog.size(); ++i) {
             const Walk4Template::Entry& te = t.prog[i];
             Walk4Entry& e = w4table[sg.first + i];
@@ -1912,7 +1954,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                 if (op.scaleRead >= 0) e.eread = (uint32_t) op.scaleRead * ebuf;
                 w4entryOf[(size_t) te.op] = (int) (sg.first + i);
                 const int subTips = w4subTips[(size_t) te.op];
-                if (sg.plain && t.W == 1 && subTips >= 2 && subTips <= unstoredTips()) {     // (kept or dropped below)
+                if (sg.plain && subTips >= 2 && subTips <= unstoredTips()) {     // (kept or dropped below)
                     // the recipe: the subtree's operations with their children as tips or as operations of the recipe; every one of them
                     // ran earlier in this program (a child runs before its parent), so its entry is known
                     constexpr int RO = MBAMD_W4_UNSTORED_TIPS_MAX - 1;
@@ -1951,7 +1993,16 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
                 e.eread = (flags & MBAMD_W4_TIP1) ? e.c1 : 0u;
             }
         }
-        lastWalkW = t.W; lastWalkSlots = t.nslots; lastWalkEntries = t.entries; lastWalkPhases = t.phases;
+        if (sg.waves) {
+            // the phase table behind the program (walk4_waves_table_entries)
+            const size_t at = w4table.size();
+            w4table.resize(at + walk4_waves_table_entries(t.W, t.phases));
+            std::memset(&w4table[at], 0, (w4table.size() - at) * sizeof(Walk4Entry));
+            uint32_t* const tab = reinterpret_cast<uint32_t*>(&w4table[at]);
+            tab[0] = (uint32_t) t.phases;
+            for (size_t q = 0; q < t.phaseCount.size(); ++q) tab[1 + q] = (uint32_t) t.phaseCount[q];
+        }
+        lastWalkW = t.W; lastWalkSlots = t.nslots; lastWalkEntries = t.entries; lastWalkPhases = t.phases; lastWalkCrossing = t.crossing;
         seg.clear();
         segList.clear();
         std::fill(segRead.begin(), segRead.end(), 0);
@@ -1999,14 +2050,17 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
     int rc = flushSegment();
     if (rc) return rc;
     if (sw.verbose)
-        std::fprintf(stderr, "[mbamd] walk plan: %d ops, %zu segment(s), W=%d, %d entries/wave, %d slots/wave, %d phases, %d reloads, %d external children\n",
-                     n, plan.segments.size(), lastWalkW, lastWalkEntries, lastWalkSlots, phases, reloads, externals);
+        std::fprintf(stderr, "[mbamd] walk plan: %d ops, %zu segment(s), W=%d, %d entries/wave, %d slots/%s, %d phases, %d reloads, %d external children, %d values cross waves in LDS%s\n",
+                     n, plan.segments.size(), lastWalkW, lastWalkEntries, lastWalkSlots, plan.segments.back().waves ? "workgroup" : "wave", phases, reloads, externals,
+                     lastWalkCrossing, plan.segments.back().plain ? " (plain)" : "");
     // a short program goes out with the launch itself (k_walk4_t<Walk4ArgsInline>, k_walkg<..., WalkGArgsInline>)
     plan.inlineProg.clear();
-    const bool inlineForm = !sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE;
+    // (a plain program of several waves has no generic reading: the slots of its entries are the workgroup's)
+    const bool inlineForm = !sw.noInlinePrograms && plan.segments.size() == 1 && w4table.size() <= (size_t) MBAMD_W4_INLINE && !plan.segments[0].waves;
     // Small subtrees are not stored where nothing can read the HBM copy in the launch that makes them: the list is ONE segment and that
-    // segment runs on the plain kernel (one wave, no prefetch: every child is a tip, a slot or the forwarded result).  Lists cut over
-    // several waves or segments, programs in the kernel arguments and the generic / path kernels store everything.
+    // segment runs on the plain kernel, on one wave or several (no prefetch: every child is a tip, a slot -- also of a value from another
+    // wave -- or the forwarded result).  Lists cut over several segments, programs in the kernel arguments and the generic / path
+    // kernels store everything.
     plan.sideFirst = 0; plan.sideCount = 0;
     if (s4 && !sw.storeTipPairs && !sw.noPlainWalk && !inlineForm && plan.segments.size() == 1 && plan.segments[0].plain) {
         for (const Plan::Unstored& u : plan.unstoredSubtrees) w4table[(size_t) u.entry].ctl |= MBAMD_W4_NOSTORE;
@@ -2255,6 +2309,13 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
         if (!plan.inlineProg.empty()) {
             auto kernel = k_walk4_t<Walk4ArgsInline>;
             MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_lds_bytes(sg.W, sg.nslots), stream, ai);
+        } else if (sg.waves) {
+            // a whole-tree list cut over several waves, each on the plain loop: the program's own layout, no other kernel reads it
+            a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
+            auto kernel = k_walk4_t<Walk4Args, true, true>;
+            MBAMD_LAUNCH_BARRIER(kernel, walk4_grid(Ppad / 64, K), 64 * sg.W, walk4_waves_lds_bytes(sg.W, sg.nslots), stream, a);
+            plainHere = true;
+            if (!plan.unstoredSubtrees.empty()) { const int urc = leaveUnstored(plan); if (urc) return urc; }
         } else if (sg.plain && !sw.noPlainWalk) {
             // nothing rare in the program (a whole-tree list): the instantiation without that code; an odd operation count's padding entry joins the tail
             a.prog = reinterpret_cast<const Walk4Entry*>(plan.d_table) + sg.first;
@@ -2270,6 +2331,7 @@ inline int Instance::runWalk(const Plan& plan, int32_t* cum)
         }
         HIP_TRY(hipGetLastError());
         ++(plainHere ? walksPlain : walksGeneric);
+        if (plainHere) ++walksPlainByW[(sg.waves ? sg.W : 1) - 1];
         pendingLaunches += 1;
     }
     return BEAGLE_SUCCESS;
@@ -2302,7 +2364,7 @@ inline int Instance::flushSnapshot()
     if (!plan || plan->segments.size() != 1 || !plan->d_table) return BEAGLE_SUCCESS;
     const Plan::Segment& sg = plan->segments[0];
     plan->lastLaunch = ++launchClock;            // (the program must stay what it is until this launch has run: planTable)
-    const unsigned nprog = (unsigned) (sg.entries - sg.tail);
+    const unsigned nprog = sg.waves ? (unsigned) (sg.W * sg.entries) : (unsigned) (sg.entries - sg.tail);   // (several waves: [W][entries], the padding carries no flag)
     MBAMD_LAUNCH(k_walk4_snapshot, nprog + (unsigned) plan->sideCount, 64, 0, stream, reinterpret_cast<const Walk4Entry*>(plan->d_table) + sg.first,
                  nprog, reinterpret_cast<const Walk4Entry*>(plan->d_table) + plan->sideFirst, (unsigned) ((size_t) (Ppad / 64) * K), (const float*) matrices, d_snap, K);
     HIP_TRY(hipGetLastError());

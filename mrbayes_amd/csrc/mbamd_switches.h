@@ -38,8 +38,9 @@ struct Switches {
     std::optional<int> spineWidth;         // MBAMD_SPINE_WIDTH=<w>: trailing levels of at most w operations join the serial launch
     bool noPoll = false;                   // MBAMD_NO_POLL: wait for a result with hipStreamSynchronize (the parsimony scorer too)
     std::optional<int> walkWaves;          // MBAMD_WALK_WAVES=<W>: waves per workgroup of the tree walks
-    std::optional<int> maxLdsSlots;        // MBAMD_MAX_LDS_SLOTS=<n>: LDS slots per wave of the tree walks
+    std::optional<int> maxLdsSlots;        // MBAMD_MAX_LDS_SLOTS=<n>: LDS slots per wave of the tree walks (a plain 4-state program of several waves: of its workgroup's one pool)
     std::optional<int> walkSmallPhase;     // MBAMD_WALK_SMALL_PHASE=<n>: tree-walk schedule shape
+    std::optional<int> walkPlainMinOps;    // MBAMD_WALK_PLAIN_MIN_OPS=<n>: operations per wave from which a whole-tree 4-state list runs the plain loop on several waves (32)
     std::optional<int> walkPrefetch;       // MBAMD_WALK_PREFETCH=<distance>: prefetch distance of the 4-state walk
     bool walkSafe = false;                 // MBAMD_WALK_SAFE: every wait of the 4-state walk waits for everything
     bool eigen256 = false;                 // MBAMD_EIGEN_256: the device eigen-solver on 256 threads at every state count
@@ -75,6 +76,7 @@ inline Switches read_switches()
     s.noFusePath = on("MBAMD_NO_FUSE_PATH"); s.noForkPath = on("MBAMD_NO_FORK_PATH"); s.noPathG = on("MBAMD_NO_PATHG");
     s.mfmaSerial = num("MBAMD_MFMA_SERIAL"); s.noSpine = on("MBAMD_NO_SPINE"); s.spineWidth = num("MBAMD_SPINE_WIDTH"); s.noPoll = on("MBAMD_NO_POLL");
     s.walkWaves = num("MBAMD_WALK_WAVES"); s.maxLdsSlots = num("MBAMD_MAX_LDS_SLOTS"); s.walkSmallPhase = num("MBAMD_WALK_SMALL_PHASE");
+    s.walkPlainMinOps = num("MBAMD_WALK_PLAIN_MIN_OPS");
     s.walkPrefetch = num("MBAMD_WALK_PREFETCH"); s.walkSafe = on("MBAMD_WALK_SAFE"); s.eigen256 = on("MBAMD_EIGEN_256");
     s.xprodGeneric = on("MBAMD_XPROD_GENERIC");
     s.parsPhaseLimit = num("MBAMD_PARS_PHASE_LIMIT"); s.parsWaves = num("MBAMD_PARS_WAVES");

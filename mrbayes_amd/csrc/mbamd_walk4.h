@@ -15,7 +15,8 @@
 //             to the wave (1 KiB each), never from HBM; HBM sees one 1 KiB contiguous store per operation
 //     workgroup = W waves (tree parallelism: the host cuts the operation forest into subtrees, packs them into
 //             W bins, and separates the few dependent phases with a workgroup barrier; values crossing waves
-//             travel through HBM/L2 and an LDS-DMA prefetch), grid = (pattern blocks, categories)
+//             travel through HBM/L2 and an LDS-DMA prefetch -- or, in a whole-tree list on the plain loop, through an
+//             LDS slot of the workgroup's one pool: WAVES, below), grid = (pattern blocks, categories)
 //
 // Everything wave-uniform comes through the SCALAR memory path (s_load_* through the scalar cache, counted by
 // lgkmcnt): the program entries, the 4x4 transition matrices -- which then feed v_pk_fma_f32 directly as scalar
@@ -60,7 +61,8 @@ namespace mbamd {
 // A SMALL SUBTREE (compact tips alone below it: a tip pair, or three or four tips, MBAMD_UNSTORED_TIPS) of a whole-tree list on the plain instantiation: the 1 KiB result is NOT stored -- its parent reads
 // the LDS slot or the forwarding registers, and it is a pure function of 64 bytes of tip planes and two matrices: whoever needs it later has
 // it recomputed (the host keeps a recipe and a snapshot of the matrices, Instance::ensureStored).  Exponent byte, slot, cum_e: as ever.
-// Honoured by k_walk4_t<Walk4Args, true> only; the host sets it nowhere else.
+// Honoured by k_walk4_t<Walk4Args, true> (one wave or several: a flagged result whose parent runs on another wave reaches it through its
+// slot like any value that crosses) only; the host sets it nowhere else.
 #define MBAMD_W4_NOSTORE  0x20000000u
 #define MBAMD_W4_NOSTORE_BIT 29
 static_assert(MBAMD_W4_NOSTORE == 1u << MBAMD_W4_NOSTORE_BIT, "the kernel tests the bit by its number");
@@ -130,6 +132,11 @@ struct Walk4Args {
 
 #define MBAMD_W4_STAGE 768       // bytes per wave in front of its slots: two 64-dword landing areas for stored exponents + one nobody reads
 __host__ __device__ inline size_t walk4_lds_bytes(int W, int nslots) { return (size_t) W * (MBAMD_W4_STAGE + (size_t) nslots * 1024); }
+// ... of a plain program of W > 1 waves (k_walk4_t<Walk4Args, true, true>): `nslots` slots for the WORKGROUP and nothing in front of them --
+// such a program reads no stored exponents; the waves' exponent sums meet in the first 256 W bytes of the slots, behind a meeting of their own
+__host__ __device__ inline size_t walk4_waves_lds_bytes(int W, int nslots) { return (size_t) nslots * 1024 > (size_t) W * 256 ? (size_t) nslots * 1024 : (size_t) W * 256; }
+// the phase table behind such a program ([W][entries]): word 0 = phases, word 1 + phase * W + wave = that wave's operations in that phase
+__host__ __device__ inline size_t walk4_waves_table_entries(int W, int phases) { return ((size_t) phases * W + 1 + 7) / 8; }
 // The grid is one-dimensional and XCD-aware: workgroup id -> XCD id % 8 (observed dispatch rule), and the K category
 // workgroups of one pattern block get consecutive positions on ONE XCD, so that the tip bitplanes and the matrix
 // lines they all read are fetched into that XCD's L2 once.
@@ -141,6 +148,7 @@ struct Walk4Planes { uint64_t p[4]; };
 #include <mbamd_dev_walk4.h>     // Walk4Mat, walk4_load_* / walk4_tip_vector / walk4_dma* / walk4_wait_vm / walk4_barrier / walk4_matvec / ... (csrc/device/)
 #include <mbamd_dev_walk4_store.h>   // walk4_store_unless: the plain walk's store pair (csrc/device/)
 #include <mbamd_dev_walk4_kinds.h>   // walk4_product: behind the plain walk's per-kind bodies (csrc/device/)
+#include <mbamd_dev_walk4_waves.h>   // walk4_meet / walk4_load_word: the plain walk of several waves (csrc/device/)
 namespace mbamd {
 
 // the values walk4_wait_vm implements, for the host: the largest supported count <= n
@@ -215,7 +223,16 @@ namespace mbamd {
 // and scalar loads alike, so the generic loop waits for the scalar-load burst it has just issued -- lgkmcnt(0) in front of
 // e = ew | er -- with its two stores not yet issued.  Here nothing between the burst and the stores reads LDS or a loaded scalar.
 // `entries - tail` may be odd (the host counts the padding entry of an odd operation count to the tail): the last entry is peeled.
-template <class ARGS, bool PLAIN = false>
+//
+// WAVES = true (with PLAIN): a whole-tree list cut over W > 1 waves, every wave running the plain loop (Walk4Template::waves,
+// Walk4Builder::placePlainWaves).  A wave's program is a sequence of PHASES, each a straight run of plain operations -- the same loop,
+// the same step: the same bits -- whose lengths stand in a table behind the program (walk4_waves_table_entries).  Between two phases
+// the wave drains its LDS writes and meets the workgroup (walk4_meet: lgkmcnt only, the store stream is nobody's business) and starts
+// the read-ahead anew.  The slots are ONE pool of the workgroup and the entries name them by their place in it: a value that crosses
+// waves is KEEP-written by its producer where its consumer's slot read finds it behind the meeting -- no HBM round trip, no LDS-DMA,
+// no vmcnt wait, no stored-exponent landing areas.  Nothing is forwarded across a meeting (an odd phase's peeled entry leaves its
+// result in the other register set; the host knows).  Every wave takes part in every meeting, with or without operations of its own.
+template <class ARGS, bool PLAIN = false, bool WAVES = false>
 __global__ void __launch_bounds__(64 * MBAMD_W4_MAXW)
 k_walk4_t(ARGS AA)
 {
@@ -228,9 +245,10 @@ k_walk4_t(ARGS AA)
     const unsigned xcd = blockIdx.x & 7u, pos = blockIdx.x >> 3;
     const unsigned blk = (pos / K) * 8u + xcd, k = pos % K;
     if (blk >= (unsigned) A.nblocks) return;
-    char* const mine = lds + (size_t) wave * (MBAMD_W4_STAGE + (size_t) A.nslots * 1024);
-    int* const stage = reinterpret_cast<int*>(mine);                           // [2][64] landing areas of stored exponents
-    char* const slots = mine + MBAMD_W4_STAGE + lane * 16;                     // this wave's private slots, this lane's f4
+    static_assert(!WAVES || PLAIN, "several waves on the plain loop, or the generic kernel");
+    char* const mine = WAVES ? lds : lds + (size_t) wave * (MBAMD_W4_STAGE + (size_t) A.nslots * 1024);
+    int* const stage = reinterpret_cast<int*>(WAVES ? lds + (size_t) wave * 256 : mine);   // [2][64] landing areas of stored exponents (WAVES: where this wave's exponent sums meet the others')
+    char* const slots = mine + (WAVES ? 0 : MBAMD_W4_STAGE) + lane * 16;       // this wave's private slots (WAVES: the workgroup's), this lane's f4
     // this wave's columns: wave-uniform bases, the entries hold byte offsets from them
     f4* const P0 = A.partials + (size_t) blk * A.pstride + (size_t) k * 64;
     const uint64_t* const T0 = A.tips + (size_t) blk * A.tstride;
@@ -368,25 +386,54 @@ k_walk4_t(ARGS AA)
         }
         out = o;
     };
-    for (int j = 0; j + (PLAIN ? 1 : 0) < n; j += 2) {
-        step(DA, DB, pp + 2, 0, RA, RB);
-        step(DB, DA, pp + 3, 1, RB, RA);
-        pp += 2;
+    if constexpr (WAVES) {
+        (void) n;
+        const int W = (int) (blockDim.x >> 6);
+        const uint32_t* const tab = reinterpret_cast<const uint32_t*>(walk4_program(AA) + (size_t) W * A.entries);
+        const int phases = (int) walk4_load_word(tab);
+        const Walk4Entry* base = pp;
+        for (int ph = 0; ph < phases; ++ph) {
+            const int np = (int) walk4_load_word(tab + 1 + ph * W + wave);
+            if (ph > 0) {
+                walk4_meet();
+                // the read-ahead prologue again, at this phase's first entry
+                pp = base;
+                DA = walk4_load_entry(pp); DB = walk4_load_entry(pp + 1);
+                M1 = walk4_load_matrix(walk4_at(M0, DA.m1));
+                M2 = walk4_load_matrix(walk4_at(M0, DA.m2));
+                T1 = walk4_load_planes(walk4_at(T0, DA.eread));
+                T2 = walk4_load_planes(walk4_at(T0, (DA.ctl & MBAMD_W4_TIP2) ? DA.c2 : 0u));
+            }
+            for (int j = 0; j + 1 < np; j += 2) {
+                step(DA, DB, pp + 2, 0, RA, RB);
+                step(DB, DA, pp + 3, 1, RB, RA);
+                pp += 2;
+            }
+            if (np & 1) step(DA, DB, pp + 2, 0, RA, RB);      // (its successor: the next phase's first entry or the tail -- valid offsets, nothing executed)
+            base += np;
+        }
+    } else {
+        for (int j = 0; j + (PLAIN ? 1 : 0) < n; j += 2) {
+            step(DA, DB, pp + 2, 0, RA, RB);
+            step(DB, DA, pp + 3, 1, RB, RA);
+            pp += 2;
+        }
+        if constexpr (PLAIN) { if (n & 1) step(DA, DB, pp + 2, 0, RA, RB); }      // (its successor is the padding entry: valid offsets, nothing executed)
     }
-    if constexpr (PLAIN) { if (n & 1) step(DA, DB, pp + 2, 0, RA, RB); }      // (its successor is the padding entry: valid offsets, nothing executed)
 #undef MBAMD_W4_EXPS
 #undef MBAMD_W4_PREFETCH
     // cumulative exponents of this workgroup's 64 columns: the waves' sums meet in LDS, wave 0 owns the memory update
     // (nobody else touches these 64 entries: no atomics; a fresh buffer is simply stored)
     if (A.cum != nullptr) {
         const int W = (int) (blockDim.x >> 6);
-        if (!PLAIN && W > 1) {
+        if ((!PLAIN || WAVES) && W > 1) {
+            if constexpr (WAVES) walk4_meet();       // (the sums land in the slots: every wave has read what it reads there)
             stage[lane] = cum_e;
-            walk4_barrier();
+            if constexpr (WAVES) walk4_meet(); else walk4_barrier();
             if (wave != 0) return;
             cum_e = 0;
             for (int w = 0; w < W; ++w)
-                cum_e += reinterpret_cast<const int*>(lds + (size_t) w * (MBAMD_W4_STAGE + (size_t) A.nslots * 1024))[lane];
+                cum_e += reinterpret_cast<const int*>(lds + (size_t) w * (WAVES ? (size_t) 256 : MBAMD_W4_STAGE + (size_t) A.nslots * 1024))[lane];
         }
         int32_t* dst = A.cum + (size_t) k * A.Ppad + (size_t) blk * 64 + lane;
         if (A.cumFresh) *dst = cum_e;

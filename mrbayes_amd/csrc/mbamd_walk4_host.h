@@ -61,6 +61,13 @@ struct Walk4Template {
     // wait, barrier or stored exponent) -- the shape of a whole-tree list; such a program runs on k_walk4_t<Walk4Args, true>.  `peel`:
     // the operation count is odd, the last entry in front of the tail is the padding no-op and counts to the tail there.
     bool plain = false, peel = false;
+    // `waves`: a plain program of W > 1 waves (k_walk4_t<Walk4Args, true, true>, Walk4Builder::placePlainWaves).  A wave's program is its
+    // phases' operations one behind the other -- no barrier, prefetch or padding entry between them; phaseCount [phase][wave] says where
+    // the workgroup meets -- `nslots` counts the slots of the WORKGROUP and the entries name them by their place in that one pool: a value
+    // that crosses waves (`crossing` of them) is written by its producer where its consumer reads it after the barrier.
+    bool waves = false;
+    std::vector<int> phaseCount;
+    int crossing = 0;
 };
 
 struct Walk4Scratch {
@@ -93,6 +100,15 @@ public:
     // 4-state walk: a result whose only consumer is the NEXT operation of the same wave -- in a post-order walk every parent
     // follows its last interior child directly -- stays in registers (c?slot = 0xFE): no LDS slot, no write / read-back round trip
     bool forward = false;
+    // 4-state walk, whole-tree lists: cut a list over plainWaves > 1 waves in the PLAIN form (Walk4Template::waves) if every child is a
+    // compact tip or a result of the list, no entry divides by stored exponents, the list has plainMinOps operations per wave and the
+    // workgroup's plainSlots LDS slots hold every live value without an eviction; anything else is built as ever (maxW, maxSlots)
+    // plainShare[W]: the longest wave a cut over W waves may have, in 1/1024 of the list -- the break-even against one wave at this
+    // launch geometry (more waves on a CU make every entry slower: Instance::configureWalk has the measured table), so that a cut
+    // that would not win is not taken; plainDescend: W - 1, W - 2, ... 2 waves are tried where W do not fit or do not win
+    int plainWaves = 0, plainSlots = 0, plainMinOps = 32;
+    int plainShare[9] = {1024, 1024, 1024, 1024, 1024, 1024, 1024, 1024, 1024};
+    bool plainDescend = false;
 
     // ops: one hazard-free segment (no buffer is written twice, none is written after it was read, a buffer read
     // after it was written is a dependency).  Fills `t` (structure) -- the caller turns it into Walk4Entry words.
@@ -101,6 +117,8 @@ public:
 private:
     Walk4Scratch s;
     void suOrder(int root, std::vector<int>& out);
+    int forceSplits = -1, splitsMade = 0;          // (plain form) exactly so many splits in the first phase (-1: the scheduler's choice) / the most a phase of the last cut made
+    bool placePlainWaves(const std::vector<Walk4Op>& ops, Walk4Template& t, const std::vector<std::vector<std::vector<int>>>& seq, int W);
 };
 
 // Sethi-Ullman post-order of the subtree below `root` restricted to operations of the current phase
@@ -152,7 +170,14 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
         if (b >= 0) { if (ncons[b]++ > 0) dag = true; else parent[b] = o; }
     }
     int W = dag ? 1 : std::max(1, std::min(maxW, 8));
+    bool tryPlain = memSlots && forward && !dag && plainWaves > 1 && n >= plainMinOps * plainWaves && leadNops == 0 && unroll == 2 && tailNops == 2;
+    for (int o = 0; o < n && tryPlain; ++o)
+        tryPlain = (ops[o].tip1 || prod1[o] >= 0) && (ops[o].tip2 || prod2[o] >= 0) && !(ops[o].scaleRead >= 0 && ops[o].scaleWrite < 0);
+    if (tryPlain) W = std::min(plainWaves, 8);
     if (n < 2 * smallPhase) W = 1;
+    tryPlain = tryPlain && W > 1;
+    t.waves = false; t.phaseCount.clear(); t.crossing = 0;
+    splitsMade = 0;
 
     // ---- phases and bins -----------------------------------------------------------------------------------
     std::vector<int>&phaseOf = s.phaseOf, &waveOf = s.waveOf, &need = s.need, &size = s.size;
@@ -244,6 +269,7 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
                 if (cost < bestCost) { bestCost = cost; bestSplits = k; }
             }
         }
+        if (tryPlain && forceSplits >= 0 && ph == 0) bestSplits = forceSplits;
         while (!heap.empty() && splits < bestSplits) {
             const int v = heap.top();
             heap.pop();
@@ -258,6 +284,14 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
             for (int o = 0; o < n; ++o) if (phaseOf[o] < 0) { phaseOf[o] = ph; seq[ph][0].push_back(o); }
             remaining = 0;
             break;
+        }
+        if (tryPlain) {
+            // (plain form) a small piece -- the side branches of a spine that the cut took apart node by node -- would hold a slot from
+            // here to the cap for a handful of operations: it stays with the cap, whose wave runs it where its parent needs it
+            std::vector<int>& big = s.pieces;
+            big.clear();
+            for (int r : frontier) if ((long) size[r] * 16 > (long) remaining) big.push_back(r);
+            if ((int) big.size() >= 2) frontier.assign(big.begin(), big.end());
         }
         binLoad.assign(W, 0);
         // mark the phase of every operation below the frontier first (suOrder needs it), then order bin by bin
@@ -277,11 +311,55 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
                 if (b >= 0 && phaseOf[b] < 0 && parent[b] == o) st.push_back(b);
             }
         }
+        if (tryPlain) {
+            // The plain form keeps every piece's result in an LDS slot until the cap reads it.  A cap node whose interior children all ran
+            // on ONE wave in this phase runs there too, behind them (children precede parents in the list): its children's slots are free
+            // again.  Then each wave takes its pieces by need, the neediest first, while it holds the fewest results.
+            splitsMade = std::max(splitsMade, splits);
+            for (int o = 0; o < n; ++o) {
+                if (!cap[o] || phaseOf[o] >= 0) continue;
+                int w = -1;
+                bool same = true;
+                for (const int c : {prod1[o], prod2[o]}) {
+                    if (c < 0) continue;
+                    if (phaseOf[c] != ph || (w >= 0 && waveOf[c] != w)) same = false;
+                    else w = waveOf[c];
+                }
+                if (same && w >= 0) { phaseOf[o] = ph; waveOf[o] = w; }
+            }
+            frontier.clear();
+            for (int o = 0; o < n; ++o)
+                if (phaseOf[o] == ph && (parent[o] < 0 || phaseOf[parent[o]] != ph)) frontier.push_back(o);
+            std::stable_sort(frontier.begin(), frontier.end(), [&](int x, int y) { return need[x] != need[y] ? need[x] > need[y] : size[x] > size[y]; });
+        }
         for (int r : frontier) suOrder(r, seq[ph][waveOf[r]]);
         for (int w = 0; w < W; ++w) remaining -= (int) seq[ph][w].size();
         (void) capSize;
     }
 
+    if (tryPlain) {
+        if (placePlainWaves(ops, t, seq, W)) return true;
+        if (forceSplits >= 0) return false;         // (inside the search below)
+        // the pool does not hold the pieces' results: the coarser cuts -- fewer pieces to hold, less even -- and of those that fit the one
+        // with the shortest longest wave
+        {
+            Walk4Template best, cand;
+            bool have = false;
+            for (int k = splitsMade - 1; k >= W - 1; --k) {
+                forceSplits = k;
+                if (build(ops, cand) && cand.waves && (!have || cand.entries < best.entries)) { best = cand; have = true; }
+            }
+            forceSplits = -1;
+            if (have) { t = best; return true; }
+        }
+        // not plain at this geometry (a value would have to leave LDS, or the cut does not win): fewer waves, then the form and the
+        // geometry the list had
+        const int keep = plainWaves;
+        plainWaves = plainDescend && W > 2 ? W - 1 : 0;
+        const bool ok = build(ops, t);
+        plainWaves = keep;
+        return ok;
+    }
     // ---- per-wave item sequences: phase p >= 1 opens with a NOP|BARRIER entry in every wave ------------------------
     struct Item { int op; uint8_t flags; };
     std::vector<std::vector<Item>> items(W);
@@ -609,6 +687,101 @@ inline bool Walk4Builder::build(const std::vector<Walk4Op>& ops, Walk4Template& 
         t.plain = plain;
         t.peel = plain && (int) fin[0].size() == body - 1;
     }
+    return true;
+}
+
+// The plain form of a list cut over W waves (Walk4Template::waves).  `seq` [phase][wave]: the operations in execution order; the
+// consumer of a result runs on the same wave in the same phase, or in a later phase on any wave (the cut's cap).  One pool of slots for
+// the workgroup; per phase a slot belongs to ONE wave -- the one that touches it first, or the consumer of the value it holds from an
+// earlier phase -- or, holding a value for a later phase, to nobody: two waves never touch a slot between two barriers.  A result whose
+// parent is the next operation of the same phase travels in registers (no forwarding across a barrier: the peeled last entry of an odd
+// phase leaves it in the other register set).  No eviction: false if the pool does not hold every live value.
+inline bool Walk4Builder::placePlainWaves(const std::vector<Walk4Op>& ops, Walk4Template& t, const std::vector<std::vector<std::vector<int>>>& seq, int W)
+{
+    const int n = (int) ops.size(), nphases = (int) seq.size();
+    const int S = std::min(plainSlots, 250);
+    if (S < 1) return false;
+    // One wave with everything is no cut (a ladder), and a cut whose longest wave is beyond the break-even against one wave
+    // (plainShare) is not taken: the scheduler's own where the tree is lopsided, a coarser one where the pool is small.
+    {
+        size_t longest = 0;
+        for (int w = 0; w < W; ++w) {
+            size_t mine = 0;
+            for (const std::vector<std::vector<int>>& phase : seq) mine += phase[(size_t) w].size();
+            longest = std::max(longest, mine);
+        }
+        if (longest >= (size_t) n || longest * 1024 > (size_t) n * (size_t) plainShare[W]) return false;
+    }
+    const std::vector<int>&prod1 = s.prod1, &prod2 = s.prod2, &parent = s.parent, &phaseOf = s.phaseOf, &waveOf = s.waveOf;
+    std::vector<int> owner((size_t) S, -1), holds((size_t) S, -1), slotOf((size_t) n, -1);
+    std::vector<char> inRegs((size_t) n, 0);
+    std::vector<std::vector<Walk4Template::Entry>>& fin = s.fin;
+    if ((int) fin.size() < W) fin.resize(W);
+    for (int w = 0; w < W; ++w) fin[w].clear();
+    int used = 1, crossing = 0;
+    t.phaseCount.assign((size_t) nphases * W, 0);
+    for (int ph = 0; ph < nphases; ++ph) {
+        for (int q = 0; q < S; ++q) {
+            owner[q] = -1;
+            if (holds[q] >= 0) { const int p = parent[holds[q]]; owner[q] = phaseOf[p] == ph ? waveOf[p] : -2; }
+        }
+        for (int w = 0; w < W; ++w) {
+            const std::vector<int>& run = seq[ph][w];
+            t.phaseCount[(size_t) ph * W + w] = (int) run.size();
+            for (size_t i = 0; i < run.size(); ++i) {
+                const int o = run[i];
+                Walk4Template::Entry e;
+                e.op = o;
+                const int pr[2] = {prod1[o], prod2[o]};
+                const bool tip[2] = {ops[o].tip1 != 0, ops[o].tip2 != 0};
+                const bool twice = !tip[0] && !tip[1] && ops[o].c1 == ops[o].c2;
+                uint8_t* cslot[2] = {&e.c1slot, &e.c2slot};
+                for (int c = 0; c < 2; ++c) {
+                    if (tip[c]) continue;
+                    if (c == 1 && twice) { e.c2slot = e.c1slot; continue; }
+                    const int v = pr[c];
+                    if (v < 0) return false;
+                    if (inRegs[v]) { *cslot[c] = 0xFE; continue; }
+                    if (slotOf[v] < 0 || owner[slotOf[v]] != w) return false;
+                    *cslot[c] = (uint8_t) slotOf[v];
+                }
+                // (the reads precede the write: a child's slot may take the result)
+                for (int c = 0; c < (twice ? 1 : 2); ++c)
+                    if (!tip[c] && *cslot[c] != 0xFE) { holds[*cslot[c]] = -1; slotOf[pr[c]] = -1; }
+                const int p = parent[o];
+                if (p >= 0) {
+                    if (phaseOf[p] < ph || (phaseOf[p] == ph && waveOf[p] != w)) return false;
+                    if (phaseOf[p] == ph && i + 1 < run.size() && run[i + 1] == p) {
+                        inRegs[o] = 1;
+                    } else {
+                        int sl = -1;
+                        for (int q = 0; q < S && sl < 0; ++q) if (holds[q] < 0 && owner[q] == w) sl = q;
+                        for (int q = 0; q < S && sl < 0; ++q) if (holds[q] < 0 && owner[q] == -1) sl = q;
+                        if (sl < 0) return false;
+                        owner[sl] = w; holds[sl] = o; slotOf[o] = sl;
+                        e.dslot = (uint8_t) sl;
+                        used = std::max(used, sl + 1);
+                        if (waveOf[p] != w) ++crossing;
+                    }
+                }
+                fin[w].push_back(e);
+            }
+        }
+    }
+    size_t longest = 0;
+    for (int w = 0; w < W; ++w) longest = std::max(longest, fin[w].size());
+    t.W = W;
+    t.phases = nphases;
+    t.reloads = t.externals = t.evictions = 0;
+    t.tail = 2;                                    // (the read-ahead of a phase's last entries: the next phase's, or these)
+    t.entries = (int) longest + t.tail;
+    t.prog.assign((size_t) W * t.entries, Walk4Template::Entry());
+    for (Walk4Template::Entry& e : t.prog) e.flags = MBAMD_W4_NOP;
+    for (int w = 0; w < W; ++w) std::copy(fin[w].begin(), fin[w].end(), t.prog.begin() + (size_t) w * t.entries);
+    t.nslots = used;
+    t.plain = t.waves = true;
+    t.peel = false;
+    t.crossing = crossing;
     return true;
 }
 
