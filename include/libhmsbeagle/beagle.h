@@ -373,6 +373,33 @@ BEAGLE_DLLEXPORT int beagleCalculateEdgeDerivatives(int instance, const int* pos
                                                     const int* derivativeMatrixIndices, const int* categoryWeightsIndices,
                                                     int count, double* outDerivatives, double* outSumDerivatives,
                                                     double* outSumSquaredDerivatives);
+/* The curvature beside the gradient (an engine extension: upstream has no such call): the first AND the second derivative of
+ * every listed branch from one read of its buffers -- what a Newton step over all branch lengths, a Laplace approximation or a
+ * diagonal mass matrix asks for.  Edge e = 0 .. count-1 names its buffers exactly as beagleCalculateEdgeDerivatives does;
+ * D1 = firstDerivativeMatrixIndices[e] and D2 = secondDerivativeMatrixIndices[e] are differential matrices
+ * (beagleSetDifferentialMatrix): for a branch length D1_k = r_k Q and D2_k = r_k^2 Q^2.
+ *     den_k    = sum_l pre[k,c,l] post[k,c,l]
+ *     g1_k(c)  = (sum_l pre[k,c,l] sum_j D1_k[l,j] post[k,c,j]) / den_k,      g2_k(c) the same with D2_k
+ *     d1_c     = sum_k q_k(c) g1_k(c)                      (beagleCalculateEdgeDerivatives' d_c)
+ *     d2_c     = sum_k q_k(c) g2_k(c) - d1_c^2             the second derivative of pattern c's log-likelihood
+ *     outFirstDerivatives[e * patternCount + c] = d1_c,  outSecondDerivatives[e * patternCount + c] = d2_c (unweighted),
+ *     outSumFirstDerivatives[e] = sum_c weight_c d1_c,   outSumSecondDerivatives[e] = sum_c weight_c d2_c;  each of the four may
+ *     be NULL.
+ * q_k(c) are the posterior category probabilities of beagleCalculateEdgeDerivatives (1 with one category); a category whose den
+ * is not positive has underflowed and is skipped in both sums.  A compact tip is its indicator vector; a MISSING state is the
+ * vector of ones in den and contributes nothing to either numerator where the layout stores state codes: differential
+ * matrices are taken to have zero row sums there, as beagleCalculateEdgeDerivatives takes them.  The rules of
+ * beagleCalculateEdgeDerivatives on the latest log-likelihood call, on categoryWeightsIndices, on pre-order buffers, on
+ * multi-partition instances (BEAGLE_ERROR_NO_IMPLEMENTATION), on NULL index arrays and on count == 0 hold unchanged; a second
+ * matrix index out of range is BEAGLE_ERROR_OUT_OF_RANGE like a first.  A refused call writes nothing.  The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdCalculateEdgeSecondDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                                         const int* firstDerivativeMatrixIndices,
+                                                         const int* secondDerivativeMatrixIndices, const int* categoryWeightsIndices,
+                                                         int count, double* outFirstDerivatives, double* outSecondDerivatives,
+                                                         double* outSumFirstDerivatives, double* outSumSecondDerivatives);
+/* its read-out launches since the instance was created: out2[0] on the plain kernel, out2[1] on the matrix-core kernel (16 ... 64
+ * states in single precision unless MBAMD_CURV_GENERIC is set); one per chunk of edges */
+BEAGLE_DLLEXPORT int mbamdGetSecondDerivativeLaunches(int instance, long* out2);
 
 /* The gradient in the rate matrix (upstream's name and argument order): the S x S cross-product matrix a client contracts with
  * dQ / d theta.  Edge e = 0 .. count-1 names postBufferIndices[e] and preBufferIndices[e] exactly as

@@ -66,7 +66,8 @@ EXPORTS = [
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
-    "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
+    "mbamdGetSecondDerivativeLaunches", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -155,6 +156,8 @@ class BeagleLibrary:
         L.beagleSetDifferentialMatrix.argtypes = [C.c_int, C.c_int, _dp]
         L.beagleCalculateEdgeDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp]
         L.beagleCalculateCrossProductDerivative.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp]
+        L.mbamdCalculateEdgeSecondDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp]
+        L.mbamdGetSecondDerivativeLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -444,6 +447,28 @@ class BeagleInstance:
                                                      sums.ctypes.data_as(_dp), sq.ctypes.data_as(_dp))
         self._chk(rc, "beagleCalculateEdgeDerivatives")
         return rc, per, sums, sq
+
+    def calculate_edge_second_derivatives(self, posts, pres, dmats1, dmats2, weights, sites=True):
+        """d lnL / dt and d2 lnL / dt2 over every listed branch in one call (mbamdCalculateEdgeSecondDerivatives), dmats1 / dmats2
+        the differential matrices r Q and r^2 Q^2.  Returns (rc, per-site d1 [count][patterns], per-site d2 -- both None without
+        `sites` --, sums of d1 [count], sums of d2 [count]); an error code raises."""
+        po, pr, m1, m2, w = _i(posts), _i(pres), _i(dmats1), _i(dmats2), _i(weights)
+        n = len(po)
+        per1 = np.empty((n, self.pattern_count)) if sites else None
+        per2 = np.empty((n, self.pattern_count)) if sites else None
+        sums1, sums2 = np.zeros(n), np.zeros(n)
+        rc = self.lib.mbamdCalculateEdgeSecondDerivatives(self.id, po.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), m1.ctypes.data_as(_ip),
+                                                          m2.ctypes.data_as(_ip), w.ctypes.data_as(_ip), n,
+                                                          per1.ctypes.data_as(_dp) if sites else None, per2.ctypes.data_as(_dp) if sites else None,
+                                                          sums1.ctypes.data_as(_dp), sums2.ctypes.data_as(_dp))
+        self._chk(rc, "mbamdCalculateEdgeSecondDerivatives")
+        return rc, per1, per2, sums1, sums2
+
+    def get_second_derivative_launches(self):
+        """(read-out launches of calculate_edge_second_derivatives on the plain kernel, on the matrix-core kernel)"""
+        out = (C.c_long * 2)()
+        self._chk(self.lib.mbamdGetSecondDerivativeLaunches(self.id, out), "mbamdGetSecondDerivativeLaunches")
+        return tuple(int(v) for v in out)
 
     def calculate_cross_products(self, posts, pres, rates, weights, edge_lengths, squared=False):
         """The cross-product matrix of the gradient in the rate matrix over every listed branch in one call

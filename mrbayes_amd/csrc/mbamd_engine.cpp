@@ -1043,6 +1043,50 @@ int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, c
     return BEAGLE_SUCCESS;
 }
 
+// first and second derivative of every listed branch from one read of its buffers (mbamd_preorder.h; semantics: beagle.h)
+int mbamdCalculateEdgeSecondDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                        const int* firstDerivativeMatrixIndices, const int* secondDerivativeMatrixIndices,
+                                        const int* categoryWeightsIndices, int count, double* outFirstDerivatives, double* outSecondDerivatives,
+                                        double* outSumFirstDerivatives, double* outSumSecondDerivatives)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdCalculateEdgeSecondDerivatives(count=%d%s)", count, outFirstDerivatives || outSecondDerivatives ? ", per site" : "");
+    const char* const who = "mbamdCalculateEdgeSecondDerivatives";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!postBufferIndices || !preBufferIndices || !firstDerivativeMatrixIndices || !secondDerivativeMatrixIndices ||
+                                    !categoryWeightsIndices)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    if (h->f64)
+        return h->f64->edgeSecondDerivatives(postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
+                                             categoryWeightsIndices, count, outFirstDerivatives, outSecondDerivatives, outSumFirstDerivatives,
+                                             outSumSecondDerivatives);
+    // pattern shards: the children's sums are added (in pattern order), their per-site values concatenated
+    const size_t n = (size_t) std::max(count, 0), stride = (size_t) h->dim.patternCount;
+    std::vector<double> sum1(n, 0.0), sum2(n, 0.0), part1(n), part2(n);
+    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
+        const int crc = c->edgeSecondDerivatives(postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
+                                                 categoryWeightsIndices, count, outFirstDerivatives ? outFirstDerivatives + ch.start : nullptr,
+                                                 outSecondDerivatives ? outSecondDerivatives + ch.start : nullptr, stride, part1.data(), part2.data());
+        if (crc) return crc;
+        for (size_t e = 0; e < n; ++e) { sum1[e] += part1[e]; sum2[e] += part2[e]; }
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    if (outSumFirstDerivatives) std::copy(sum1.begin(), sum1.end(), outSumFirstDerivatives);
+    if (outSumSecondDerivatives) std::copy(sum2.begin(), sum2.end(), outSumSecondDerivatives);
+    return BEAGLE_SUCCESS;
+}
+// its read-out launches so far: out2[0] of the plain kernel, out2[1] of the matrix-core kernel (children: the sums over them)
+int mbamdGetSecondDerivativeLaunches(int instance, long* out2)
+{
+    GET_INSTANCE_NOFLUSH(instance);
+    if (!out2) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetSecondDerivativeLaunches: null output");
+    out2[0] = out2[1] = 0;
+    if (h->f64) { h->f64->secondLaunchCounts(out2); return BEAGLE_SUCCESS; }
+    EACH_ENGINE(false, (c->secondLaunchCounts(out2), BEAGLE_SUCCESS));
+}
+
 // the cross-product matrix of the gradient in the rate matrix (mbamd_crossproducts.h; semantics: beagle.h)
 int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryRateIndices,
                                           const int* categoryWeightsIndices, const double* edgeLengths, int count, double* outSumDerivatives,

@@ -191,6 +191,10 @@ struct Instance {
                      double* sums, double* sumsSq);
     // crossProducts (beagleCalculateCrossProductDerivative on this engine's patterns): synchronous; out[S * S] is overwritten
     int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
+    // edgeSecondDerivatives (mbamdCalculateEdgeSecondDerivatives on this engine's patterns): as edgeGradient, with d1 and d2 of every edge
+    int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
+                              double* sites2, size_t siteStride, double* sums1, double* sums2);
+    void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -356,6 +360,7 @@ private:
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued or held runs first
@@ -411,6 +416,7 @@ private:
     void afterSync() { syncedClock = launchClock; }
     // launches for kernelTiming to report
     void countLaunches(int n) { pendingLaunches += n; }
+    long secondLaunches[2] = {0, 0};  // read-out launches of edge_second_derivatives: plain / matrix-core kernel
     int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
@@ -3519,6 +3525,11 @@ inline int Instance::edgeGradient(const int* post, const int* pre, const int* dm
 inline int Instance::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
     return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
+}
+inline int Instance::edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
+                                           double* sites1, double* sites2, size_t siteStride, double* sums1, double* sums2)
+{
+    return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, siteStride, sums1, sums2);
 }
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked and in memory, and room for q
 inline int Instance::posteriorOperands(DerivArgs& a)

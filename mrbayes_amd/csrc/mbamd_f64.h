@@ -90,6 +90,9 @@ public:
     int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
     int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq);
     int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
+    int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
+                              double* sites2, double* sums1, double* sums2);
+    void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel (none here)
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -162,6 +165,7 @@ private:
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
+    template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued runs first
@@ -195,6 +199,7 @@ private:
     void afterSync() {}
     // launches for kernelTiming to report
     void countLaunches(int n) { preLaunches += (uint64_t) n; }
+    long secondLaunches[2] = {0, 0};  // read-out launches of edge_second_derivatives: plain / matrix-core kernel
     // f(this engine's layout as a compile-time constant)
     template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }
     int posteriorOperands(DerivArgs& a);
@@ -1297,6 +1302,11 @@ inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dm
 inline int Engine64::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
     return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
+}
+inline int Engine64::edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
+                                           double* sites1, double* sites2, double* sums1, double* sums2)
+{
+    return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, (size_t) P, sums1, sums2);
 }
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked, and room for q
 inline int Engine64::posteriorOperands(DerivArgs& a)

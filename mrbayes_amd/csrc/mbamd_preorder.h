@@ -16,6 +16,9 @@
 //
 // Arithmetic as everywhere: products in the engine's precision (FMA chains over the states, ascending), sums over states and
 // categories of the read-outs in double, block sums through mbd_wave_sum_store (fixed order).
+//
+// The same read with a second differential matrix gives the second derivative beside the first (mbamdCalculateEdgeSecondDerivatives:
+// k_edge_second, k_edge_second_mfma and edge_second_derivatives below).
 #ifndef MBAMD_PREORDER_H_
 #define MBAMD_PREORDER_H_
 
@@ -271,9 +274,218 @@ k_gradient_sums(const double* __restrict__ sums, int nb, int edges, double* __re
     mbd_wave_sum_store(s, out + row);
 }
 
+// ---- first AND second derivative of every branch (mbamdCalculateEdgeSecondDerivatives; semantics: beagle.h) --------
+// With a second differential matrix D2_k (r_k^2 Q^2 for a branch length) beside D1_k, per category
+//     g1_k(c), g2_k(c) = (sum_l pre[l] sum_j D1_k / D2_k [l,j] post[j]) / (sum_l pre[l] post[l])
+// from ONE read of the two columns, and
+//     d1_c = sum_k q_k(c) g1_k(c),     d2_c = sum_k q_k(c) g2_k(c) - d1_c^2
+// d1 is k_edge_gradient's, operation for operation.  A compact tip with a missing state: the vector of ones in the denominator and
+// nothing in either numerator (the rows of a differential matrix sum to zero) where the layout stores state codes; the four-state
+// bitplanes add the compatible columns, as k_edge_gradient does.
+struct SecondArgs {
+    DerivArgs          g;
+    const GradEdge*    edges;     // the edges of this launch (grid y); D = the first differential matrix
+    const void* const* D2;        // ... and their second differential matrices
+    const double*      q;         // [K][Ppad] posterior category probabilities, or null (one category: q = 1)
+    const double*      pattern_weights;
+    double*            site1;     // [edges][Ppad] unweighted d1_c, or null
+    double*            site2;     // [edges][Ppad] unweighted d2_c, or null
+    double*            sums;      // [2][edges][nb]: weight_c d1_c and weight_c d2_c, one per 64-pattern block
+    int                nb, edgeCount;
+};
+
+// The plain kernel, the sibling of k_edge_gradient: grid (64-pattern blocks, edges), one thread per pattern, looping over the
+// categories; the post-order value a row of D1 meets is the one the same row of D2 meets.
+template <int LAYOUT, class Real>
+__global__ void __launch_bounds__(64)
+k_edge_second(SecondArgs a)
+{
+    const DerivArgs& g = a.g;
+    const int S = g.S, K = g.K;
+    const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
+    const GradEdge ed = a.edges[blockIdx.y];
+    const void* const D2 = a.D2[blockIdx.y];
+    double d = 0.0, d2 = 0.0, pw = 0.0;
+    if (c < g.last) {
+        const unsigned tip = ed.postTip ? deriv_tip<LAYOUT>(ed.post, g, c) : 0u;
+        for (int k = 0; k < K; ++k) {
+            double num = 0.0, num2 = 0.0, den = 0.0;
+            if constexpr (LAYOUT == DERIV_S4) {
+                const size_t at = blk_index(c, g.pstride) + (size_t) k * 64;
+                const f4 p4 = reinterpret_cast<const f4*>(ed.pre)[at];
+                const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+                float v[4];
+                if (ed.postTip) {
+                    for (int j = 0; j < 4; ++j) v[j] = (tip >> j & 1u) ? 1.0f : 0.0f;
+                } else {
+                    const f4 q4 = reinterpret_cast<const f4*>(ed.post)[at];
+                    v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
+                }
+                const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(ed.D)) + k * 16;          // m[j * 4 + l] = D(l -> j)
+                const MBAMD_AS_CONST float* m2 = as_const(reinterpret_cast<const float*>(D2)) + k * 16;
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    const float f = fmaf(m[12 + l], v[3], fmaf(m[8 + l], v[2], fmaf(m[4 + l], v[1], m[l] * v[0])));
+                    const float f2 = fmaf(m2[12 + l], v[3], fmaf(m2[8 + l], v[2], fmaf(m2[4 + l], v[1], m2[l] * v[0])));
+                    num += (double) (p[l] * f);
+                    num2 += (double) (p[l] * f2);
+                    den += (double) (p[l] * v[l]);
+                }
+            } else {
+                for (int l = 0; l < S; ++l) {
+                    const Real p = deriv_partial<LAYOUT, Real>(ed.pre, g, k, l, c);
+                    Real f = (Real) 0, f2 = (Real) 0, v;
+                    if (ed.postTip) {
+                        v = (tip >= (unsigned) S || tip == (unsigned) l) ? (Real) 1 : (Real) 0;
+                        if (tip < (unsigned) S) {
+                            f = deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, (int) tip);
+                            f2 = deriv_matrix<LAYOUT, Real>(D2, g, k, l, (int) tip);
+                        }
+                    } else {
+                        for (int j = 0; j < S; ++j) {
+                            const Real x = deriv_partial<LAYOUT, Real>(ed.post, g, k, j, c);
+                            f = deriv_fma(deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, j), x, f);
+                            f2 = deriv_fma(deriv_matrix<LAYOUT, Real>(D2, g, k, l, j), x, f2);
+                        }
+                        v = deriv_partial<LAYOUT, Real>(ed.post, g, k, l, c);
+                    }
+                    num += (double) (p * f);
+                    num2 += (double) (p * f2);
+                    den += (double) (p * v);
+                }
+            }
+            if (den > 0.0) {
+                const double qk = a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0;
+                d += qk * (num / den);
+                d2 += qk * (num2 / den);
+            }
+        }
+        d2 -= d * d;
+        if (a.site1 != nullptr) a.site1[(size_t) blockIdx.y * g.Ppad + c] = d;
+        if (a.site2 != nullptr) a.site2[(size_t) blockIdx.y * g.Ppad + c] = d2;
+        pw = a.pattern_weights[c];
+    }
+    mbd_wave_sum_store(pw * d, a.sums + (size_t) blockIdx.y * a.nb + blockIdx.x);
+    mbd_wave_sum_store(pw * d2, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
+}
+
+// dynamic LDS of the matrix-core kernel: the post-order and the pre-order column of the block, [state][thread], 32 TILES rows each
+inline size_t second_lds_bytes(int tiles) { return (size_t) 2 * 32 * tiles * 64 * sizeof(float); }
+
+// 16 .. 64 states on the fp32 engine: grid (64-pattern blocks, edges), one wave per workgroup, ONE EDGE per workgroup (the two
+// matrices change with the edge and the category, so a wave that looped over edges would keep nothing but its sums; see DESIGN
+// 4.4.6 for the register and LDS budget).  Per category the wave stages its 64 patterns' columns (thread = pattern; den is summed
+// there, in k_edge_gradient's order) and forms F1 = D1 post, F2 = D2 post, 32 TILES states x 64 patterns each, with
+// mbd_mfma_f32_32x32x2: row tiles hold states, the two column tiles patterns 0 .. 31 and 32 .. 63, the reduction runs over the
+// post-order state j, two per instruction -- lane l feeds A[l & 31][l >> 5] = D(32 rt + (l & 31) -> 2 s + (l >> 5)), read from the
+// matrix buffer where it lies (zero beyond S), and B[l >> 5][l & 31] = post[2 s + (l >> 5)][pattern 32 ct + (l & 31)] from LDS.
+// 4 TILES independent accumulators.  Then lane l holds, of column 32 ct + (l & 31), the rows (r & 3) + 8 (r >> 2) + 4 (l >> 5) of
+// every row tile (mbd_mfma_f32_32x32x2's layout): it multiplies them with the pre-order column from LDS, adds the products in
+// double, the two half-waves of a column are joined by mbd_shfl_xor(., 32), and lane l takes the column of ITS pattern.
+template <int LAYOUT, int TILES>
+__global__ void __launch_bounds__(64)
+k_edge_second_mfma(SecondArgs a)
+{
+    constexpr int ROWS = 32 * TILES;
+    const DerivArgs& g = a.g;
+    const int S = g.S, K = g.K, lane = (int) threadIdx.x, half = lane >> 5, col = lane & 31;
+    const int c = (int) blockIdx.x * 64 + lane;
+    const bool live = c < g.last;
+    const GradEdge ed = a.edges[blockIdx.y];
+    const void* const D2 = a.D2[blockIdx.y];
+    float* const post = mbd_dyn_lds<float>() + lane;          // element j of this thread's column: post[j * 64]
+    float* const pre = post + (size_t) ROWS * 64;
+    const float* const readPost = mbd_dyn_lds<float>() + half * 64 + col;
+    const float* const readPre = mbd_dyn_lds<float>() + (size_t) ROWS * 64 + col;
+    const unsigned tip = live && ed.postTip ? deriv_tip<LAYOUT>(ed.post, g, c) : 0u;
+    // (a reduction index beyond S meets a zero of the matrix: the column holds a zero there too, not whatever LDS held)
+    if (S & 1) post[S * 64] = 0.0f;
+    if (!live) for (int l = 0; l < S; ++l) { post[l * 64] = 0.0f; pre[l * 64] = 0.0f; }
+    double d = 0.0, d2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+        double den = 0.0;
+        if (live) {
+            // (sixteen states at a time, as cross_stage: their loads are issued together)
+            for (int l0 = 0; l0 < S; l0 += 16) {
+                float p[16], v[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int l = l0 + u < S ? l0 + u : S - 1;
+                    p[u] = deriv_partial<LAYOUT, float>(ed.pre, g, k, l, c);
+                    if (ed.postTip) v[u] = (tip >= (unsigned) S || tip == (unsigned) l) ? 1.0f : 0.0f;
+                    else v[u] = deriv_partial<LAYOUT, float>(ed.post, g, k, l, c);
+                }
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    if (l0 + u < S) {
+                        pre[(l0 + u) * 64] = p[u];
+                        post[(l0 + u) * 64] = (ed.postTip && tip >= (unsigned) S) ? 0.0f : v[u];
+                        den += (double) (p[u] * v[u]);
+                    }
+                }
+            }
+        }
+        MBAMD_SYNC();
+        mbd_acc16 acc1[TILES][2], acc2[TILES][2];
+#pragma unroll
+        for (int rt = 0; rt < TILES; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) { acc1[rt][ct] = (mbd_acc16) (0.0f); acc2[rt][ct] = (mbd_acc16) (0.0f); }
+        for (int s = 0; 2 * s < S; ++s) {
+            const int j = 2 * s + half;
+            const float b0 = readPost[2 * s * 64], b1 = readPost[2 * s * 64 + 32];
+#pragma unroll
+            for (int rt = 0; rt < TILES; ++rt) {
+                const int l = 32 * rt + col;
+                const bool in = l < S && j < S;
+                const float x1 = in ? deriv_matrix<LAYOUT, float>(ed.D, g, k, l, j) : 0.0f;
+                const float x2 = in ? deriv_matrix<LAYOUT, float>(D2, g, k, l, j) : 0.0f;
+                acc1[rt][0] = mbd_mfma_f32_32x32x2(x1, b0, acc1[rt][0]);
+                acc1[rt][1] = mbd_mfma_f32_32x32x2(x1, b1, acc1[rt][1]);
+                acc2[rt][0] = mbd_mfma_f32_32x32x2(x2, b0, acc2[rt][0]);
+                acc2[rt][1] = mbd_mfma_f32_32x32x2(x2, b1, acc2[rt][1]);
+            }
+        }
+        double n1[2] = {0.0, 0.0}, n2[2] = {0.0, 0.0};
+#pragma unroll
+        for (int rt = 0; rt < TILES; ++rt) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (row < S) {
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        const float p = readPre[row * 64 + 32 * ct];
+                        n1[ct] += (double) (acc1[rt][ct][r] * p);
+                        n2[ct] += (double) (acc2[rt][ct][r] * p);
+                    }
+                }
+            }
+        }
+        MBAMD_SYNC();
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) { n1[ct] += mbd_shfl_xor(n1[ct], 32); n2[ct] += mbd_shfl_xor(n2[ct], 32); }
+        const double num = half ? n1[1] : n1[0], num2 = half ? n2[1] : n2[0];
+        if (live && den > 0.0) {
+            const double qk = a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0;
+            d += qk * (num / den);
+            d2 += qk * (num2 / den);
+        }
+    }
+    double pw = 0.0;
+    if (live) {
+        d2 -= d * d;
+        if (a.site1 != nullptr) a.site1[(size_t) blockIdx.y * g.Ppad + c] = d;
+        if (a.site2 != nullptr) a.site2[(size_t) blockIdx.y * g.Ppad + c] = d2;
+        pw = a.pattern_weights[c];
+    }
+    mbd_wave_sum_store(pw * d, a.sums + (size_t) blockIdx.y * a.nb + blockIdx.x);
+    mbd_wave_sum_store(pw * d2, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
+}
+
 // ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
 // The calls are written once, as templates on the engine (Instance, Engine64).  They read its members of the same name -- the sizes
-// S, K, P, Ppad, nBuffers, nMatrices, stream, valid, preOrder, lastLnl, qStamp, d_q, d_pweights, rateSets, sw, layoutArgs(),
+// S, K, P, Ppad, nBuffers, nMatrices, stream, valid, preOrder, lastLnl, qStamp, d_q, d_pweights, rateSets, sw, secondLaunches, layoutArgs(),
 // partialsPtr(), matrixPtr() -- and ask it for the rest through a few small hooks, which each engine keeps in one block:
 //     runQueued, refuses                  before anything else: what is queued or held runs; an instance the calls do not serve
 //     holdsTip, readable, operandPtr      a buffer holds compact tip states / something to read; where that is
@@ -522,6 +734,105 @@ inline int edge_gradient(Engine& e, const int* post, const int* pre, const int* 
             if (sites) std::memcpy(sites + (size_t) (e0 + i) * siteStride, h.data() + (size_t) i * Ppad, (size_t) P * sizeof(double));
             if (sums) sums[e0 + i] = h[nSite + (size_t) i];
             if (sumsSq) sumsSq[e0 + i] = h[nSite + (size_t) ne + i];
+        }
+    }
+    return BEAGLE_SUCCESS;
+}
+
+// edges of a second-derivative call per launch: as gradient_chunk for its larger staging ([edges][Ppad] per per-site array asked
+// for -- siteArrays of them, 0 .. 2 --, [2][edges][nb] block sums, [2][edges] sums)
+inline int second_chunk(int count, int Ppad, int siteArrays)
+{
+    const size_t per = (size_t) 2 * (Ppad / 64) + 2 + (size_t) siteArrays * Ppad;
+    return (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
+}
+
+// the read-out launch of one chunk; returns whether the matrix-core kernel took it
+template <int LAYOUT, class Real>
+inline bool launch_edge_second(hipStream_t stream, const SecondArgs& a, int ne, bool mfma)
+{
+    const dim3 grid((unsigned) a.nb, (unsigned) ne);
+    if constexpr (LAYOUT == DERIV_WG || LAYOUT == DERIV_LEVELS) {
+        if (mfma) {
+            const int tiles = a.g.S <= 32 ? 1 : 2;
+            const size_t lds = second_lds_bytes(tiles);
+            if (tiles == 1) { auto kernel = k_edge_second_mfma<LAYOUT, 1>; MBAMD_LAUNCH_BARRIER(kernel, grid, 64, lds, stream, a); }
+            else { auto kernel = k_edge_second_mfma<LAYOUT, 2>; MBAMD_LAUNCH_BARRIER(kernel, grid, 64, lds, stream, a); }
+            return true;
+        }
+    }
+    auto kernel = k_edge_second<LAYOUT, Real>;
+    MBAMD_LAUNCH(kernel, grid, 64, 0, stream, a);
+    return false;
+}
+
+// mbamdCalculateEdgeSecondDerivatives on the engine's patterns, as edge_gradient: the edges in chunks (second_chunk), per chunk one
+// launch of the read-out kernel -- k_edge_second, or k_edge_second_mfma for 16 .. 64 states in single precision (MBAMD_CURV_GENERIC:
+// the plain one) -- and one of k_gradient_sums, then the chunk's results come back.  Synchronous; sums1[i] and sums2[i] are the
+// weighted sums of d1 and d2 of edge i, sites1 / sites2 (or null) take d1_c / d2_c of edge i at [i * siteStride + c].  The engine's
+// secondLaunches[0 / 1] count the read-out launches of the plain and of the matrix-core kernel.
+template <class Engine>
+inline int edge_second_derivatives(Engine& e, const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
+                                   double* sites1, double* sites2, size_t siteStride, double* sums1, double* sums2)
+{
+    const char* const who = "mbamdCalculateEdgeSecondDerivatives";
+    { const int rc = edge_list_begin(e, who); if (rc) return rc; }
+    for (int i = 0; i < count; ++i) {
+        const int rc = edge_check(e, who, post[i], pre[i], wIdx[i]);
+        if (rc) return rc;
+        if (dmat1[i] < 0 || dmat1[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
+        if (dmat2[i] < 0 || dmat2[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "second differential matrix index");
+    }
+    if (count <= 0) return BEAGLE_SUCCESS;
+    // the table: the edges, then their second matrices
+    const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
+    std::vector<unsigned char> table(edgeBytes + (size_t) count * sizeof(void*), 0);
+    GradEdge* const edges = reinterpret_cast<GradEdge*>(table.data());
+    { const int rc = edge_list_fill(e, post, pre, count, edges); if (rc) return rc; }
+    const void** const second = reinterpret_cast<const void**>(table.data() + edgeBytes);
+    for (int i = 0; i < count; ++i) { edges[i].D = e.matrixPtr(dmat1[i]); second[i] = e.matrixPtr(dmat2[i]); }
+    void* d_table = nullptr;
+    { const int rc = e.stageTable(table.data(), table.size(), &d_table); if (rc) return rc; }
+    const int P = e.P, Ppad = e.Ppad, nb = Ppad / 64;
+    const int siteArrays = (sites1 ? 1 : 0) + (sites2 ? 1 : 0);
+    const int chunk = second_chunk(count, Ppad, siteArrays);
+    const size_t nSite = (size_t) chunk * Ppad, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
+    double* d_site = nullptr;
+    { const int rc = e.resultScratch((siteArrays * nSite + nBlock + nOut) * sizeof(double), &d_site); if (rc) return rc; }
+    double* const d_block = d_site + siteArrays * nSite;
+    double* const d_out = d_block + nBlock;
+    std::vector<double> h(siteArrays * nSite + nOut);
+    double* const h_out = h.data() + siteArrays * nSite;
+    SecondArgs a;
+    a.g = e.layoutArgs();
+    a.q = e.K > 1 ? e.d_q : nullptr;
+    a.pattern_weights = e.d_pweights;
+    a.site1 = sites1 ? d_site : nullptr;
+    a.site2 = sites2 ? d_site + (sites1 ? nSite : 0) : nullptr;
+    a.sums = d_block;
+    a.nb = nb;
+    const bool mfma = e.S >= 16 && e.S <= 64 && !e.sw.curvGeneric;
+    for (int e0 = 0; e0 < count; e0 += chunk) {
+        const int ne = std::min(chunk, count - e0);
+        a.edges = static_cast<const GradEdge*>(d_table) + e0;
+        a.D2 = reinterpret_cast<const void* const*>(static_cast<const unsigned char*>(d_table) + edgeBytes) + e0;
+        a.edgeCount = ne;
+        const bool core = e.withLayout([&](auto L) { return launch_edge_second<L(), deriv_real<L()>>(e.stream, a, ne, mfma); });
+        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, e.stream, (const double*) d_block, nb, ne, d_out);
+        HIP_TRY(hipGetLastError());
+        e.countLaunches(2);
+        ++e.secondLaunches[core ? 1 : 0];
+        HIP_TRY(hipStreamSynchronize(e.stream));
+        e.afterSync();
+        for (int s = 0; s < siteArrays; ++s)
+            HIP_TRY(hipMemcpy(h.data() + s * nSite, d_site + s * nSite, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_out, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < ne; ++i) {
+            const double* hs = h.data() + (size_t) i * Ppad;
+            if (sites1) { std::memcpy(sites1 + (size_t) (e0 + i) * siteStride, hs, (size_t) P * sizeof(double)); hs += nSite; }
+            if (sites2) std::memcpy(sites2 + (size_t) (e0 + i) * siteStride, hs, (size_t) P * sizeof(double));
+            if (sums1) sums1[e0 + i] = h_out[i];
+            if (sums2) sums2[e0 + i] = h_out[(size_t) ne + i];
         }
     }
     return BEAGLE_SUCCESS;

@@ -40,9 +40,11 @@ class BeagleDivision:
 
     def __init__(self, div: Division, lib: Optional[bg.BeagleLibrary] = None, nchains: int = 1,
                  scaling: int = MB_BEAGLE_SCALE_ALWAYS, resource: Optional[int] = None, device_eigen: bool = False,
-                 double_precision: bool = False, pre_order: bool = False):
+                 double_precision: bool = False, pre_order: bool = False, second_order: bool = False):
         self.div = div
+        pre_order = pre_order or second_order
         self.pre_order = pre_order                      # reserve the buffers of BranchGradient (behind every existing one)
+        self.second_order = second_order                # ... and the second differential matrix of BranchCurvature (behind those)
         self.double_precision = double_precision        # `set beagleprecision=double` (src/command.c:6765-6766): a preference flag
         self.device_eigen = device_eigen and div.rate_matrices is not None and bool(np.all(np.asarray(div.pi) > 0))
         self.lib = lib or bg.library()
@@ -95,6 +97,9 @@ class BeagleDivision:
                 self.numPreOrder = nNodes + 2
                 self.identityMatrixIndex = (self.numTiProbs + 1) * step
                 self.numDiffMatrices = 2
+            if second_order:
+                self.diffMatrix2Index = (self.numTiProbs + self.numDiffMatrices) * step
+                self.numDiffMatrices += 1
         # --- dirty flags ("touch" state), per chain ----------------------------------------------
         self.upDateCl = [[True] * nNodes for _ in range(nchains)]
         self.upDateTi = [[True] * nNodes for _ in range(nchains)]
@@ -461,23 +466,44 @@ class BeagleDivision:
         t = self.div.tree
         return [self.preOrderRootIndex if self.div.complex_eigen and n == t.root_left else self.preOrderIndex[n] for n in nodes]
 
+    def _RateMatrix(self):
+        es = self.div.eigen[0]
+        if es.imag is None:
+            return (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
+        # Q = U D U^-1 with D in block form
+        return np.asarray(es.evec, dtype=np.float64) @ eigen_blocks(es, es.eval + 1j * es.imag) @ np.asarray(es.ivec, dtype=np.float64)
+
     def BranchGradient(self, chain=0, sites=False):
         """{node: d lnL / d t_node} for all 2N-3 branches of the chain's current tree, after LogLike: the start vector
         pi_i tip_root[c,i] and D_k = r_k Q are set, the pre-order list of the whole tree is issued and ONE
         calculate_edge_gradient call reads every branch.  sites=True: (that, {node: per-site derivatives})."""
         self._PreOrderPass(chain, "BranchGradient")
         d, t = self.div, self.div.tree
-        es = d.eigen[0]
-        if es.imag is None:
-            q = (np.asarray(es.evec, dtype=np.float64) * np.asarray(es.eval, dtype=np.float64)[None, :]) @ np.asarray(es.ivec, dtype=np.float64)
-        else:                                # Q = U D U^-1 with D in block form
-            q = np.asarray(es.evec, dtype=np.float64) @ eigen_blocks(es, es.eval + 1j * es.imag) @ np.asarray(es.ivec, dtype=np.float64)
+        q = self._RateMatrix()
         self.inst.set_differential_matrix(self.diffMatrixIndex, np.asarray(d.cat_rates, dtype=np.float64)[:, None, None] * q[None, :, :])
         nodes = list(t.all_down_pass)
         rc, per, sums, _ = self.inst.calculate_edge_gradient(self._EdgePosts(chain, nodes), self._EdgePres(nodes),
                                                              [self.diffMatrixIndex] * len(nodes), [self.cijkIndex[chain]] * len(nodes), sites=sites)
         grad = {n: float(sums[i]) for i, n in enumerate(nodes)}
         return (grad, {n: per[i] for i, n in enumerate(nodes)}) if sites else grad
+
+    def BranchCurvature(self, chain=0, sites=False):
+        """{node: (d lnL / d t_node, d2 lnL / d t_node^2)} for all 2N-3 branches of the chain's current tree, after LogLike: as
+        BranchGradient with D1_k = r_k Q and D2_k = r_k^2 Q^2, and ONE calculate_edge_second_derivatives call reads every branch
+        once.  sites=True: (that, {node: (per-site d1, per-site d2)}).  Needs BeagleDivision(..., second_order=True)."""
+        if not self.second_order:
+            raise ValueError("BranchCurvature needs BeagleDivision(..., second_order=True)")
+        self._PreOrderPass(chain, "BranchCurvature")
+        d, t = self.div, self.div.tree
+        q, r = self._RateMatrix(), np.asarray(d.cat_rates, dtype=np.float64)
+        self.inst.set_differential_matrix(self.diffMatrixIndex, r[:, None, None] * q[None, :, :])
+        self.inst.set_differential_matrix(self.diffMatrix2Index, (r * r)[:, None, None] * (q @ q)[None, :, :])
+        nodes = list(t.all_down_pass)
+        rc, per1, per2, sums1, sums2 = self.inst.calculate_edge_second_derivatives(
+            self._EdgePosts(chain, nodes), self._EdgePres(nodes), [self.diffMatrixIndex] * len(nodes), [self.diffMatrix2Index] * len(nodes),
+            [self.cijkIndex[chain]] * len(nodes), sites=sites)
+        curv = {n: (float(sums1[i]), float(sums2[i])) for i, n in enumerate(nodes)}
+        return (curv, {n: (per1[i], per2[i]) for i, n in enumerate(nodes)}) if sites else curv
 
     def RateMatrixCrossProducts(self, chain=0):
         """X [S][S], the cross-product matrix of the gradient in the rate matrix, for the chain's current tree after LogLike: the same

@@ -10,7 +10,13 @@ buffer is 4 S bytes per (pattern, category); divided by 8 TB/s.
 
 A second line times ONE beagleCalculateCrossProductDerivative call over the same branches (the gradient in the rate matrix, DESIGN
 4.4.3; MBAMD_XPROD_GENERIC=1 selects the plain kernel) next to the same byte model -- two partials buffers per branch -- and, from 16
-states, the matrix-core flop model 2 (32 TILES)^2 x patterns x categories x branches at 157.3 TFLOP/s."""
+states, the matrix-core flop model 2 (32 TILES)^2 x patterns x categories x branches at 157.3 TFLOP/s.
+
+A third line times ONE mbamdCalculateEdgeSecondDerivatives call over the same branches, no per-site values (first and second
+derivative of every branch; MBAMD_CURV_GENERIC=1 selects the plain kernel), ALTERNATING with the first-derivative call
+of the first line: medians and the spread (min ... max) of both, the same byte model -- the curvature call reads the same two
+buffers per branch -- and, from 16 states, the matrix-core flop model 2 matrices x 2 x 32 TILES x S x patterns x categories x
+branches at 157.3 TFLOP/s."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -25,7 +31,7 @@ if ":" in case:
     div = synthetic_division(kind, int(ntaxa), int(npat), seed=11, tree_seed=5, alpha=0.7, ncat=int(ncat))
 else:
     div = division_from_golden(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"), case)
-bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, pre_order=True)
+bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, second_order=True)
 try:
     inst, t = bd.inst, div.tree
     lnl = bd.LogLike(0)
@@ -89,5 +95,29 @@ try:
           (case, len(nodes), "plain kernel" if os.environ.get("MBAMD_XPROD_GENERIC") and tiles else "matrix core" if tiles else "plain kernel",
            cross, launches // repeats, model_read, 100.0 * model_read / cross,
            "; flop model %.3f ms: %.0f %%" % (model_flop, 100.0 * model_flop / cross) if tiles else "", lhs, rhs))
+    curv = bd.BranchCurvature(0)                 # (sets D1 and D2; the warm-up)
+    sx = dict(posts=ix["posts"], pres=ix["pres"], dmats1=ix["dmats"], dmats2=[bd.diffMatrix2Index] * len(nodes), weights=ix["weights"])
+    before = inst.get_second_derivative_launches()
+    first_ms, second_ms = [], []
+    for i in range(repeats):
+        t0 = time.perf_counter()
+        rc, _, sums, _ = inst.calculate_edge_gradient(sites=False, **ix)
+        t1 = time.perf_counter()
+        rc2, _, _, s1, s2 = inst.calculate_edge_second_derivatives(sites=False, **sx)
+        t2 = time.perf_counter()
+        first_ms.append((t1 - t0) * 1e3)
+        second_ms.append((t2 - t1) * 1e3)
+    after = inst.get_second_derivative_launches()
+    assert rc == 0 and rc2 == 0 and all(curv[n] == (s1[i], s2[i]) for i, n in enumerate(nodes))
+    core = after[1] > before[1]
+    assert core or all(grad[n] == s1[i] for i, n in enumerate(nodes))
+    first, second = float(np.median(first_ms)), float(np.median(second_ms))
+    flops = 2.0 * 2.0 * (32 * tiles) * S * div.npatterns * div.ncat * len(nodes)
+    model_flop = flops / 157.3e12 * 1e3
+    print("%s: first and second derivatives of %d branches (%s): %.3f ms a call (%.3f ... %.3f; byte model %.3f ms: %.0f %%%s) against "
+          "the first-derivative call alternating with it %.3f ms (%.3f ... %.3f; %.0f %%); sum of d2 over the branches %.6g" %
+          (case, len(nodes), "matrix core" if core else "plain kernel", second, min(second_ms), max(second_ms), model_read,
+           100.0 * model_read / second, "; flop model %.3f ms: %.0f %%" % (model_flop, 100.0 * model_flop / second) if core else "",
+           first, min(first_ms), max(first_ms), 100.0 * model_read / first, sum(v[1] for v in curv.values())))
 finally:
     bd.finalize()
