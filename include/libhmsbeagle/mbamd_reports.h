@@ -43,6 +43,39 @@ BEAGLE_DLLEXPORT int mbamdUpdateFinalPartials(int instance, const MbamdFinalOper
 BEAGLE_DLLEXPORT int mbamdGetScaledPartials(int instance, int bufferIndex, int cumulativeScaleIndex, float* outPartials,
                                             float* outLnScale);
 
+/* The same reports from the buffers the gradient calls read, on the single- AND the double-precision engine: the marginal
+ * posterior of every state at every listed node, all nodes of a tree in one call.  Node i = 0 .. count-1 names
+ * postBufferIndices[i] (its post-order partials, or compact tip states) and preBufferIndices[i] (pre(node), written by
+ * beagleUpdatePrePartials and by nothing since) exactly as an edge of beagleCalculateEdgeDerivatives does.  Per pattern c:
+ *     j_k(a)  = pre[k,c,a] * post[k,c,a]                     the joint of state a with all the data, in category k
+ *     den_k   = sum_a j_k(a)
+ *     p_c(a)  = sum_k q_k(c) j_k(a) / den_k                  the posterior of state a at the node
+ *     outPosteriors[(i * patternCount + c) * stateCount + a] = p_c(a)                                     (or NULL)
+ *     outBestStates[i * patternCount + c]     = the smallest a that attains max_a p_c(a)                  (or NULL)
+ *     outBestPosteriors[i * patternCount + c] = that maximum                                              (or NULL)
+ *     outSumPosteriors[i * stateCount + a]    = sum_c weight_c p_c(a)      the expected number of sites in state a; never NULL
+ * The products are formed in the engine's precision, the sums in double.  Whatever scale a column (pattern, category) of
+ * either buffer carries leaves the ratio j_k / den_k: no scale buffer is named.  q_k(c) are the posterior category
+ * probabilities of beagleCalculateEdgeDerivatives (1 with one category: nothing is then asked of a log-likelihood call); a
+ * category whose den is not positive has underflowed and is skipped.  A compact tip is its indicator vector, a MISSING state the
+ * vector of ones (p_c is then the normalised mixture of the pre-order columns), four-state bitplanes give the compatible
+ * states; where exactly one state is compatible p_c is that indicator, exactly 1 and 0.  The sums are reduced on the device in a
+ * fixed order and do not depend on which per-pattern outputs are asked for.  The rules of beagleCalculateEdgeDerivatives on the
+ * latest log-likelihood call, on categoryWeightsIndices, on pre-order and post-order buffers, on multi-partition instances
+ * (BEAGLE_ERROR_NO_IMPLEMENTATION), on NULL index arrays and on count == 0 hold unchanged; a NULL outSumPosteriors is
+ * BEAGLE_ERROR_OUT_OF_RANGE.  A refused call writes nothing.  The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdCalculateNodePosteriors(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                                  const int* categoryWeightsIndices, int count, double* outPosteriors,
+                                                  int* outBestStates, double* outBestPosteriors, double* outSumPosteriors);
+
+/* q_k(c), the posterior probability of rate category k at pattern c under the operands of the latest
+ * beagleCalculate{Root,Edge}LogLikelihoods call as they are now: outPosteriors[k * patternCount + c].  From them come the site
+ * rates (sum_k q_k(c) r_k) and, where the categories are omega classes, the positive-selection probabilities and site omegas.
+ * One category: ones.  With more: no log-likelihood call yet is BEAGLE_ERROR_GENERAL, one with count > 1
+ * BEAGLE_ERROR_NO_IMPLEMENTATION, and categoryWeightsIndex must be that call's weights index (BEAGLE_ERROR_OUT_OF_RANGE).  Not on
+ * a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).  The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdGetCategoryPosteriors(int instance, int categoryWeightsIndex, double* outPosteriors);
+
 #ifdef __cplusplus
 }
 #endif

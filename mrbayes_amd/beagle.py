@@ -67,7 +67,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
-    "mbamdGetSecondDerivativeLaunches", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -158,6 +158,8 @@ class BeagleLibrary:
         L.beagleCalculateCrossProductDerivative.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp]
         L.mbamdCalculateEdgeSecondDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp]
         L.mbamdGetSecondDerivativeLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdCalculateNodePosteriors.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, _dp, _ip, _dp, _dp]
+        L.mbamdGetCategoryPosteriors.argtypes = [C.c_int, C.c_int, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -469,6 +471,29 @@ class BeagleInstance:
         out = (C.c_long * 2)()
         self._chk(self.lib.mbamdGetSecondDerivativeLaunches(self.id, out), "mbamdGetSecondDerivativeLaunches")
         return tuple(int(v) for v in out)
+
+    def calculate_node_posteriors(self, posts, pres, weights, sites=True, best=False):
+        """The marginal posterior of every state at every listed node in one call (mbamdCalculateNodePosteriors).  Returns (rc,
+        posteriors [count][patterns][states] or None without `sites`, best states [count][patterns] and their posteriors
+        [count][patterns] -- both None without `best` --, sums [count][states]); an error code raises."""
+        po, pr, w = _i(posts), _i(pres), _i(weights)
+        n, P, S = len(po), self.pattern_count, self.state_count
+        per = np.empty((n, P, S)) if sites else None
+        states = np.empty((n, P), dtype=np.int32) if best else None
+        values = np.empty((n, P)) if best else None
+        sums = np.zeros((n, S))
+        rc = self.lib.mbamdCalculateNodePosteriors(self.id, po.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), w.ctypes.data_as(_ip), n,
+                                                   per.ctypes.data_as(_dp) if sites else None, states.ctypes.data_as(_ip) if best else None,
+                                                   values.ctypes.data_as(_dp) if best else None, sums.ctypes.data_as(_dp))
+        self._chk(rc, "mbamdCalculateNodePosteriors")
+        return rc, per, states, values, sums
+
+    def get_category_posteriors(self, weights_index):
+        """q [categories][patterns]: the posterior category probabilities of the latest log-likelihood call
+        (mbamdGetCategoryPosteriors)."""
+        q = np.empty((self.category_count, self.pattern_count))
+        self._chk(self.lib.mbamdGetCategoryPosteriors(self.id, weights_index, q.ctypes.data_as(_dp)), "mbamdGetCategoryPosteriors")
+        return q
 
     def calculate_cross_products(self, posts, pres, rates, weights, edge_lengths, squared=False):
         """The cross-product matrix of the gradient in the rate matrix over every listed branch in one call

@@ -1087,6 +1087,47 @@ int mbamdGetSecondDerivativeLaunches(int instance, long* out2)
     EACH_ENGINE(false, (c->secondLaunchCounts(out2), BEAGLE_SUCCESS));
 }
 
+// node-state and category posteriors from the pre-order buffers (mbamd_posteriors.h; semantics: mbamd_reports.h)
+int mbamdCalculateNodePosteriors(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryWeightsIndices,
+                                 int count, double* outPosteriors, int* outBestStates, double* outBestPosteriors, double* outSumPosteriors)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdCalculateNodePosteriors(count=%d%s%s)", count, outPosteriors ? ", per site" : "", outBestStates || outBestPosteriors ? ", best" : "");
+    const char* const who = "mbamdCalculateNodePosteriors";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!postBufferIndices || !preBufferIndices || !categoryWeightsIndices)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    if (!outSumPosteriors) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "outSumPosteriors is null");
+    if (h->f64)
+        return h->f64->nodePosteriors(postBufferIndices, preBufferIndices, categoryWeightsIndices, count, outPosteriors, outBestStates,
+                                      outBestPosteriors, outSumPosteriors);
+    // pattern shards: the children's sums are added (in pattern order), their per-pattern values concatenated
+    const size_t S = (size_t) h->dim.stateCount, n = (size_t) std::max(count, 0) * S, stride = (size_t) h->dim.patternCount;
+    std::vector<double> sum(n, 0.0), part(n);
+    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
+        const int crc = c->nodePosteriors(postBufferIndices, preBufferIndices, categoryWeightsIndices, count,
+                                          outPosteriors ? outPosteriors + (size_t) ch.start * S : nullptr, outBestStates ? outBestStates + ch.start : nullptr,
+                                          outBestPosteriors ? outBestPosteriors + ch.start : nullptr, stride, part.data());
+        if (crc) return crc;
+        for (size_t i = 0; i < n; ++i) sum[i] += part[i];
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    std::copy(sum.begin(), sum.end(), outSumPosteriors);
+    return BEAGLE_SUCCESS;
+}
+int mbamdGetCategoryPosteriors(int instance, int categoryWeightsIndex, double* outPosteriors)
+{
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdGetCategoryPosteriors(weights=%d)", categoryWeightsIndex);
+    const char* const who = "mbamdGetCategoryPosteriors";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (!outPosteriors) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null output");
+    if (h->f64) return h->f64->categoryPosteriors(categoryWeightsIndex, outPosteriors);
+    EACH_ENGINE(true, c->categoryPosteriors(categoryWeightsIndex, outPosteriors + ch.start, (size_t) h->dim.patternCount));
+}
+
 // the cross-product matrix of the gradient in the rate matrix (mbamd_crossproducts.h; semantics: beagle.h)
 int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryRateIndices,
                                           const int* categoryWeightsIndices, const double* edgeLengths, int count, double* outSumDerivatives,

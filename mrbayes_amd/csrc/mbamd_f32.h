@@ -18,6 +18,7 @@
 #include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
+#include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
 
 namespace mbamd {
@@ -195,6 +196,11 @@ struct Instance {
     int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
                               double* sites2, size_t siteStride, double* sums1, double* sums2);
     void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel
+    // nodePosteriors / categoryPosteriors (mbamdCalculateNodePosteriors / mbamdGetCategoryPosteriors on this engine's patterns;
+    // mbamd_posteriors.h): synchronous; sums[i * S + a], per-pattern outputs (or null) at [(i * siteStride + c) * S + a] and [i * siteStride + c]
+    int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
+                       size_t siteStride, double* sums);
+    int categoryPosteriors(int wIdx, double* out, size_t stride);
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -361,6 +367,8 @@ private:
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
     template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
+    template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued or held runs first
@@ -3531,6 +3539,12 @@ inline int Instance::edgeSecondDerivatives(const int* post, const int* pre, cons
 {
     return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, siteStride, sums1, sums2);
 }
+inline int Instance::nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
+                                    size_t siteStride, double* sums)
+{
+    return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, siteStride, sums);
+}
+inline int Instance::categoryPosteriors(int wIdx, double* out, size_t stride) { return category_posteriors(*this, wIdx, out, stride); }
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked and in memory, and room for q
 inline int Instance::posteriorOperands(DerivArgs& a)
 {

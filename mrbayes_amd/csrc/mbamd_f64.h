@@ -30,6 +30,7 @@
 #include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient <DERIV_F64, double>: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
+#include "mbamd_posteriors.h"    // k_node_posteriors <DERIV_F64, double>: node-state and category posteriors from the pre-order buffers
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
 
 namespace mbamd {
@@ -93,6 +94,9 @@ public:
     int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
                               double* sites2, double* sums1, double* sums2);
     void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel (none here)
+    // node-state and category posteriors (mbamd_posteriors.h), as on the single-precision engine: synchronous
+    int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues, double* sums);
+    int categoryPosteriors(int wIdx, double* out);
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -166,6 +170,8 @@ private:
     template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
     template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
+    template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued runs first
@@ -1308,6 +1314,12 @@ inline int Engine64::edgeSecondDerivatives(const int* post, const int* pre, cons
 {
     return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, (size_t) P, sums1, sums2);
 }
+inline int Engine64::nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
+                                    double* sums)
+{
+    return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, (size_t) P, sums);
+}
+inline int Engine64::categoryPosteriors(int wIdx, double* out) { return category_posteriors(*this, wIdx, out, (size_t) P); }
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked, and room for q
 inline int Engine64::posteriorOperands(DerivArgs& a)
 {

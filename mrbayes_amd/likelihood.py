@@ -505,6 +505,28 @@ class BeagleDivision:
         curv = {n: (float(sums1[i]), float(sums2[i])) for i, n in enumerate(nodes)}
         return (curv, {n: (per1[i], per2[i]) for i, n in enumerate(nodes)}) if sites else curv
 
+    def NodePosteriors(self, chain=0, sites=False, best=False):
+        """{node: expected number of sites in every state [states]} for the lower end of all 2N-3 branches of the chain's current
+        tree (every interior node and every tip but the root tip), after LogLike: the pre-order pass of BranchGradient, then ONE
+        calculate_node_posteriors call.  sites=True adds {node: posteriors [patterns][states]}, best=True {node: (best states
+        [patterns], their posteriors [patterns])}: the return value is the tuple of the dictionaries asked for, the sums first."""
+        self._PreOrderPass(chain, "NodePosteriors")
+        nodes = list(self.div.tree.all_down_pass)
+        rc, per, states, values, sums = self.inst.calculate_node_posteriors(
+            [self.condLikeIndex[chain][n] for n in nodes], [self.preOrderIndex[n] for n in nodes], [self.cijkIndex[chain]] * len(nodes),
+            sites=sites, best=best)
+        out = [{n: sums[i] for i, n in enumerate(nodes)}]
+        if sites:
+            out.append({n: per[i] for i, n in enumerate(nodes)})
+        if best:
+            out.append({n: (states[i], values[i]) for i, n in enumerate(nodes)})
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def CategoryPosteriors(self, chain=0):
+        """q [categories][patterns], the posterior category probabilities of the chain's latest LogLike: site rates are
+        (q * cat_rates[:, None]).sum(0)."""
+        return self.inst.get_category_posteriors(self.cijkIndex[chain])
+
     def RateMatrixCrossProducts(self, chain=0):
         """X [S][S], the cross-product matrix of the gradient in the rate matrix, for the chain's current tree after LogLike: the same
         steps as BranchGradient (start vector, pre-order list of the whole tree), then ONE calculate_cross_products call over all

@@ -16,7 +16,12 @@ A third line times ONE mbamdCalculateEdgeSecondDerivatives call over the same br
 derivative of every branch; MBAMD_CURV_GENERIC=1 selects the plain kernel), ALTERNATING with the first-derivative call
 of the first line: medians and the spread (min ... max) of both, the same byte model -- the curvature call reads the same two
 buffers per branch -- and, from 16 states, the matrix-core flop model 2 matrices x 2 x 32 TILES x S x patterns x categories x
-branches at 157.3 TFLOP/s."""
+branches at 157.3 TFLOP/s.
+
+A fourth line times ONE mbamdCalculateNodePosteriors call over the same (post-order, pre-order) pairs (the posterior of every state at
+every node) without per-pattern outputs, ALTERNATING with the first-derivative call, against the same byte model: the
+call reads the same two buffers per node and has no matrix; then with best states only, alternating with the first-derivative call
+that returns its per-site values (count x patterns results cross the host link in both)."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -119,5 +124,38 @@ try:
           (case, len(nodes), "matrix core" if core else "plain kernel", second, min(second_ms), max(second_ms), model_read,
            100.0 * model_read / second, "; flop model %.3f ms: %.0f %%" % (model_flop, 100.0 * model_flop / second) if core else "",
            first, min(first_ms), max(first_ms), 100.0 * model_read / first, sum(v[1] for v in curv.values())))
+    px = dict(posts=ix["posts"], pres=ix["pres"], weights=ix["weights"])
+    rc, _, _, _, expect = inst.calculate_node_posteriors(sites=False, **px)            # (the warm-up)
+    rc, _, _, _, _ = inst.calculate_node_posteriors(sites=False, best=True, **px)
+    # (two loops: best states and their posteriors are count x patterns values that cross the host link, so their yardstick is the
+    #  first-derivative call WITH its per-site values, which are as many doubles)
+    first_ms, sums_ms, first2_ms, best_ms = [], [], [], []
+    for i in range(repeats):
+        t0 = time.perf_counter()
+        rc, _, sums, _ = inst.calculate_edge_gradient(sites=False, **ix)
+        t1 = time.perf_counter()
+        rc2, _, _, _, psums = inst.calculate_node_posteriors(sites=False, **px)
+        t2 = time.perf_counter()
+        first_ms.append((t1 - t0) * 1e3)
+        sums_ms.append((t2 - t1) * 1e3)
+    assert rc == 0 and rc2 == 0 and np.array_equal(psums, expect)
+    for i in range(repeats):
+        t0 = time.perf_counter()
+        rc, per, sums, _ = inst.calculate_edge_gradient(sites=True, **ix)
+        t1 = time.perf_counter()
+        rc2, _, states, _, psums = inst.calculate_node_posteriors(sites=False, best=True, **px)
+        t2 = time.perf_counter()
+        first2_ms.append((t1 - t0) * 1e3)
+        best_ms.append((t2 - t1) * 1e3)
+    assert rc == 0 and rc2 == 0 and np.array_equal(psums, expect)
+    first, psum, first2, pbest = (float(np.median(v)) for v in (first_ms, sums_ms, first2_ms, best_ms))
+    out_mib = len(nodes) * div.npatterns * 12.0 / 2 ** 20
+    print("%s: node posteriors of %d nodes: sums only %.3f ms a call (%.3f ... %.3f; byte model %.3f ms: %.0f %%) against the "
+          "first-derivative call alternating with it %.3f ms (%.3f ... %.3f; %.0f %%); with best states (%.1f MiB to the host) %.3f ms "
+          "(%.3f ... %.3f) against the first-derivative call WITH its per-site values (%.1f MiB) alternating with it %.3f ms (%.3f ... %.3f); "
+          "largest |sum over states - sum of weights| %.3g" %
+          (case, len(nodes), psum, min(sums_ms), max(sums_ms), model_read, 100.0 * model_read / psum, first, min(first_ms), max(first_ms),
+           100.0 * model_read / first, out_mib, pbest, min(best_ms), max(best_ms), out_mib * 2.0 / 3.0, first2, min(first2_ms), max(first2_ms),
+           float(np.abs(psums.sum(1) - float(np.asarray(div.weights, dtype=np.float64).sum())).max())))
 finally:
     bd.finalize()
