@@ -8,10 +8,10 @@
 //     X[i,j]  += (weight_c q_k(c) t_e r_k / den) pre_e[k,c,i] post_e[k,c,j]
 // -- per edge and category a product A B^T of two [S x patterns] matrices, A the pre-order columns times one coefficient per pattern,
 // B the post-order columns: a GEMM with an S x S result whose reduction runs over edges x categories x patterns.  Every scale factor
-// of either buffer cancels per (pattern, category); a category with den <= 0 has underflowed and is skipped, as in k_edge_gradient.
+// of either buffer cancels per (pattern, category); a category with den <= 0 has underflowed and is skipped, as in k_edge_readout.
 //
 // Grid (64-pattern blocks, edge chunks), one wave per workgroup; the wave LOOPS over the edges of its chunk, so that what a launch
-// leaves behind is one S x S double matrix per (block, chunk) -- never one per edge.  Arithmetic as in k_edge_gradient: products in
+// leaves behind is one S x S double matrix per (block, chunk) -- never one per edge.  Arithmetic as in k_edge_readout: products in
 // the engine's precision, den summed in double; the coefficient is formed in double, rounded ONCE to the engine's precision and
 // multiplied into the pre-order column; the products A[i,c] B[j,c] are
 //   * added in double as they come (k_cross_products: four states in registers, other layouts from LDS), or
@@ -263,7 +263,7 @@ k_cross_product_sums(const double* __restrict__ partial, int n, int SS, double* 
 
 // ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
 
-// the check of the edge lengths (those on buffers and indices: edge_check, as in edge_gradient)
+// the check of the edge lengths (those on buffers and indices: edge_check, as in edge_readout)
 inline int cross_check_lengths(const char* who, const double* t, int count)
 {
     for (int e = 0; e < count; ++e)

@@ -201,6 +201,20 @@ static void copy_rows(T* dst, size_t dstRow, const T* src, size_t srcRow, int K,
 {
     for (int k = 0; k < K; ++k) std::memcpy(dst + (size_t) k * dstRow, src + (size_t) k * srcRow, n * sizeof(T));
 }
+// Every pattern shard answers with n doubles that are added in child order (pattern order): call(c, ch, part) has engine c fill
+// part[0 .. n); sum[0 .. n) is complete, from zeros, once every engine has answered
+template <class F>
+static int each_engine_sum(Handle* h, size_t n, std::vector<double>& sum, F&& call)
+{
+    sum.assign(n, 0.0);
+    std::vector<double> part(n);
+    return each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
+        const int crc = call(c, ch, part.data());
+        if (crc) return crc;
+        for (size_t i = 0; i < n; ++i) sum[i] += part[i];
+        return BEAGLE_SUCCESS;
+    });
+}
 
 // the engine proper for one log-likelihood call; children: per-child sums, FLOATING_POINT if any child says so
 static int integrate_any(Handle* h, const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
@@ -1014,6 +1028,22 @@ int beagleSetDifferentialMatrix(int instance, int matrixIndex, const double* inM
     if (h->f64) return h->f64->setMatrix(matrixIndex, inMatrix);
     EACH_ENGINE(true, c->setMatrix(matrixIndex, inMatrix));
 }
+// the gradient call (dmat2, sites2 null) and the second-derivative call on the pattern shards: the children's sums are added (in
+// pattern order), their per-site values concatenated
+static int edge_readout_shards(Handle* h, const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
+                               double* sites2, double* sums1, double* sums2)
+{
+    const size_t n = (size_t) std::max(count, 0), stride = (size_t) h->dim.patternCount;
+    std::vector<double> sum;
+    const int rc = each_engine_sum(h, 2 * n, sum, [&](Instance* c, const Handle::Span& ch, double* part) {
+        return c->edgeReadout(post, pre, dmat1, dmat2, wIdx, count, sites1 ? sites1 + ch.start : nullptr, sites2 ? sites2 + ch.start : nullptr, stride,
+                              part, part + n);
+    });
+    if (rc) return rc;
+    if (sums1) std::copy(sum.begin(), sum.begin() + n, sums1);
+    if (sums2) std::copy(sum.begin() + n, sum.end(), sums2);
+    return BEAGLE_SUCCESS;
+}
 int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* derivativeMatrixIndices,
                                    const int* categoryWeightsIndices, int count, double* outDerivatives, double* outSumDerivatives,
                                    double* outSumSquaredDerivatives)
@@ -1025,22 +1055,10 @@ int beagleCalculateEdgeDerivatives(int instance, const int* postBufferIndices, c
     if (count < 0 || (count > 0 && (!postBufferIndices || !preBufferIndices || !derivativeMatrixIndices || !categoryWeightsIndices)))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCalculateEdgeDerivatives: null index array");
     if (h->f64)
-        return h->f64->edgeGradient(postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices, count, outDerivatives,
-                                    outSumDerivatives, outSumSquaredDerivatives);
-    // pattern shards: the children's sums are added (in pattern order), their per-site values concatenated
-    const size_t n = (size_t) std::max(count, 0);
-    std::vector<double> sum(n, 0.0), sq(n, 0.0), part(n), partSq(n);
-    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
-        const int crc = c->edgeGradient(postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices, count,
-                                        outDerivatives ? outDerivatives + ch.start : nullptr, (size_t) h->dim.patternCount, part.data(), partSq.data());
-        if (crc) return crc;
-        for (size_t e = 0; e < n; ++e) { sum[e] += part[e]; sq[e] += partSq[e]; }
-        return BEAGLE_SUCCESS;
-    });
-    if (rc) return rc;
-    if (outSumDerivatives) std::copy(sum.begin(), sum.end(), outSumDerivatives);
-    if (outSumSquaredDerivatives) std::copy(sq.begin(), sq.end(), outSumSquaredDerivatives);
-    return BEAGLE_SUCCESS;
+        return h->f64->edgeReadout(postBufferIndices, preBufferIndices, derivativeMatrixIndices, nullptr, categoryWeightsIndices, count, outDerivatives,
+                                   nullptr, outSumDerivatives, outSumSquaredDerivatives);
+    return edge_readout_shards(h, postBufferIndices, preBufferIndices, derivativeMatrixIndices, nullptr, categoryWeightsIndices, count, outDerivatives,
+                               nullptr, outSumDerivatives, outSumSquaredDerivatives);
 }
 
 // first and second derivative of every listed branch from one read of its buffers (mbamd_preorder.h; semantics: beagle.h)
@@ -1058,24 +1076,11 @@ int mbamdCalculateEdgeSecondDerivatives(int instance, const int* postBufferIndic
                                     !categoryWeightsIndices)))
         return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
     if (h->f64)
-        return h->f64->edgeSecondDerivatives(postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
-                                             categoryWeightsIndices, count, outFirstDerivatives, outSecondDerivatives, outSumFirstDerivatives,
-                                             outSumSecondDerivatives);
-    // pattern shards: the children's sums are added (in pattern order), their per-site values concatenated
-    const size_t n = (size_t) std::max(count, 0), stride = (size_t) h->dim.patternCount;
-    std::vector<double> sum1(n, 0.0), sum2(n, 0.0), part1(n), part2(n);
-    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
-        const int crc = c->edgeSecondDerivatives(postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
-                                                 categoryWeightsIndices, count, outFirstDerivatives ? outFirstDerivatives + ch.start : nullptr,
-                                                 outSecondDerivatives ? outSecondDerivatives + ch.start : nullptr, stride, part1.data(), part2.data());
-        if (crc) return crc;
-        for (size_t e = 0; e < n; ++e) { sum1[e] += part1[e]; sum2[e] += part2[e]; }
-        return BEAGLE_SUCCESS;
-    });
-    if (rc) return rc;
-    if (outSumFirstDerivatives) std::copy(sum1.begin(), sum1.end(), outSumFirstDerivatives);
-    if (outSumSecondDerivatives) std::copy(sum2.begin(), sum2.end(), outSumSecondDerivatives);
-    return BEAGLE_SUCCESS;
+        return h->f64->edgeReadout(postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
+                                   categoryWeightsIndices, count, outFirstDerivatives, outSecondDerivatives, outSumFirstDerivatives,
+                                   outSumSecondDerivatives);
+    return edge_readout_shards(h, postBufferIndices, preBufferIndices, firstDerivativeMatrixIndices, secondDerivativeMatrixIndices,
+                               categoryWeightsIndices, count, outFirstDerivatives, outSecondDerivatives, outSumFirstDerivatives, outSumSecondDerivatives);
 }
 // its read-out launches so far: out2[0] of the plain kernel, out2[1] of the matrix-core kernel (children: the sums over them)
 int mbamdGetSecondDerivativeLaunches(int instance, long* out2)
@@ -1103,15 +1108,12 @@ int mbamdCalculateNodePosteriors(int instance, const int* postBufferIndices, con
         return h->f64->nodePosteriors(postBufferIndices, preBufferIndices, categoryWeightsIndices, count, outPosteriors, outBestStates,
                                       outBestPosteriors, outSumPosteriors);
     // pattern shards: the children's sums are added (in pattern order), their per-pattern values concatenated
-    const size_t S = (size_t) h->dim.stateCount, n = (size_t) std::max(count, 0) * S, stride = (size_t) h->dim.patternCount;
-    std::vector<double> sum(n, 0.0), part(n);
-    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
-        const int crc = c->nodePosteriors(postBufferIndices, preBufferIndices, categoryWeightsIndices, count,
-                                          outPosteriors ? outPosteriors + (size_t) ch.start * S : nullptr, outBestStates ? outBestStates + ch.start : nullptr,
-                                          outBestPosteriors ? outBestPosteriors + ch.start : nullptr, stride, part.data());
-        if (crc) return crc;
-        for (size_t i = 0; i < n; ++i) sum[i] += part[i];
-        return BEAGLE_SUCCESS;
+    const size_t S = (size_t) h->dim.stateCount, stride = (size_t) h->dim.patternCount;
+    std::vector<double> sum;
+    const int rc = each_engine_sum(h, (size_t) std::max(count, 0) * S, sum, [&](Instance* c, const Handle::Span& ch, double* part) {
+        return c->nodePosteriors(postBufferIndices, preBufferIndices, categoryWeightsIndices, count,
+                                 outPosteriors ? outPosteriors + (size_t) ch.start * S : nullptr, outBestStates ? outBestStates + ch.start : nullptr,
+                                 outBestPosteriors ? outBestPosteriors + ch.start : nullptr, stride, part);
     });
     if (rc) return rc;
     std::copy(sum.begin(), sum.end(), outSumPosteriors);
@@ -1145,13 +1147,9 @@ int beagleCalculateCrossProductDerivative(int instance, const int* postBufferInd
     if (h->f64)
         return h->f64->crossProducts(postBufferIndices, preBufferIndices, categoryRateIndices, categoryWeightsIndices, edgeLengths, count, outSumDerivatives);
     // pattern shards: the children's matrices are added, in child order
-    const size_t SS = (size_t) h->dim.stateCount * h->dim.stateCount;
-    std::vector<double> sum(SS, 0.0), part(SS);
-    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span&) -> int {
-        const int crc = c->crossProducts(postBufferIndices, preBufferIndices, categoryRateIndices, categoryWeightsIndices, edgeLengths, count, part.data());
-        if (crc) return crc;
-        for (size_t ij = 0; ij < SS; ++ij) sum[ij] += part[ij];
-        return BEAGLE_SUCCESS;
+    std::vector<double> sum;
+    const int rc = each_engine_sum(h, (size_t) h->dim.stateCount * h->dim.stateCount, sum, [&](Instance* c, const Handle::Span&, double* part) {
+        return c->crossProducts(postBufferIndices, preBufferIndices, categoryRateIndices, categoryWeightsIndices, edgeLengths, count, part);
     });
     if (rc) return rc;
     std::copy(sum.begin(), sum.end(), outSumDerivatives);

@@ -16,7 +16,7 @@
 #include "mbamd_walk4_host.h"
 #include "mbamd_kernels_mfma.h"
 #include "mbamd_derivatives.h"   // k_edge_derivatives: lnL, d lnL / dt and d2 lnL / dt2 over one branch
-#include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient: the pre-order pass and the gradient in all branch lengths
+#include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
@@ -185,16 +185,15 @@ struct Instance {
     bool hasDerivatives() const { return derivValid; }
     const double* siteDerivatives(int order) const { return h_deriv + (size_t) order * Ppad; }
     // The pre-order pass and the gradient in all branch lengths (mbamd_preorder.h; semantics: beagle.h), both after everything queued
-    // or held.  updatePrePartials: one launch per group of mutually independent operations.  edgeGradient: synchronous; sums[e] and
-    // sumsSq[e] are this engine's weighted sums of edge e, sites (or null) takes d_c of edge e at sites[e * siteStride + c].
+    // or held.  updatePrePartials: one launch per group of mutually independent operations.  edgeReadout (beagleCalculateEdgeDerivatives
+    // with dmat2 and sites2 null, mbamdCalculateEdgeSecondDerivatives otherwise, on this engine's patterns): synchronous; sums1[e] and
+    // sums2[e] are this engine's weighted sums of d_c and of d_c^2 (with dmat2: of d2_c) of edge e, sites1 / sites2 (or null) take d_c /
+    // d2_c of edge e at [e * siteStride + c].
     int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
-    int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
-                     double* sums, double* sumsSq);
+    int edgeReadout(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1, double* sites2,
+                    size_t siteStride, double* sums1, double* sums2);
     // crossProducts (beagleCalculateCrossProductDerivative on this engine's patterns): synchronous; out[S * S] is overwritten
     int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
-    // edgeSecondDerivatives (mbamdCalculateEdgeSecondDerivatives on this engine's patterns): as edgeGradient, with d1 and d2 of every edge
-    int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
-                              double* sites2, size_t siteStride, double* sums1, double* sums2);
     void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel
     // nodePosteriors / categoryPosteriors (mbamdCalculateNodePosteriors / mbamdGetCategoryPosteriors on this engine's patterns;
     // mbamd_posteriors.h): synchronous; sums[i * S + a], per-pattern outputs (or null) at [(i * siteStride + c) * S + a] and [i * siteStride + c]
@@ -364,9 +363,9 @@ private:
     template <class E> friend int edge_list_begin(E&, const char*);
     template <class E> friend int edge_check(const E&, const char*, int, int, int);
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
-    template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
-    template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E> friend int edge_readout(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
@@ -424,7 +423,7 @@ private:
     void afterSync() { syncedClock = launchClock; }
     // launches for kernelTiming to report
     void countLaunches(int n) { pendingLaunches += n; }
-    long secondLaunches[2] = {0, 0};  // read-out launches of edge_second_derivatives: plain / matrix-core kernel
+    long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
@@ -3525,19 +3524,14 @@ inline int Instance::lnlOperands(DerivArgs& a, int parent, int child, int prob, 
 // The pre-order pass, the gradient in all branch lengths and the cross products: the bodies are shared with the double-precision
 // engine (mbamd_preorder.h, mbamd_crossproducts.h).
 inline int Instance::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx) { return update_pre_partials(*this, ops, n, cumIdx); }
-inline int Instance::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
-                                  double* sums, double* sumsSq)
+inline int Instance::edgeReadout(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
+                                 double* sites2, size_t siteStride, double* sums1, double* sums2)
 {
-    return edge_gradient(*this, post, pre, dmat, wIdx, count, sites, siteStride, sums, sumsSq);
+    return edge_readout(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, siteStride, sums1, sums2);
 }
 inline int Instance::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
     return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
-}
-inline int Instance::edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
-                                           double* sites1, double* sites2, size_t siteStride, double* sums1, double* sums2)
-{
-    return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, siteStride, sums1, sums2);
 }
 inline int Instance::nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
                                     size_t siteStride, double* sums)

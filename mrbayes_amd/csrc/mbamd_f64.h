@@ -28,7 +28,7 @@
 #include "mbamd_f64_kernels.h"   // Op64, Walk64Entry / Walk64Args, MatrixJob64, IntegrateArgs64 and the k64_* kernels
 #include "mbamd_walk4_host.h"    // Walk4Builder: the program compiler of the four-state walk
 #include "mbamd_derivatives.h"   // k_edge_derivatives<DERIV_F64, double>: branch-length derivatives over one edge
-#include "mbamd_preorder.h"      // k_pre_partials, k_edge_gradient <DERIV_F64, double>: the pre-order pass and the gradient in all branch lengths
+#include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout <DERIV_F64, double, 1 and 2>: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors <DERIV_F64, double>: node-state and category posteriors from the pre-order buffers
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
@@ -87,12 +87,11 @@ public:
     bool hasDerivatives() const { return derivValid; }
     const double* siteDerivatives(int order) const { return derivSite.data() + (size_t) order * Ppad; }
     // The pre-order pass and the gradient in all branch lengths (mbamd_preorder.h; semantics: beagle.h), as on the single-precision
-    // engine: one launch per group of independent operations; the gradient call is synchronous.
+    // engine: one launch per group of independent operations; the gradient and second-derivative call (edgeReadout) is synchronous.
     int updatePrePartials(const BeagleOperation* ops, int n, int cumIdx);
-    int edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq);
+    int edgeReadout(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1, double* sites2,
+                    double* sums1, double* sums2);
     int crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out);
-    int edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
-                              double* sites2, double* sums1, double* sums2);
     void secondLaunchCounts(long out2[2]) const { out2[0] += secondLaunches[0]; out2[1] += secondLaunches[1]; }   // its read-out launches: plain / matrix-core kernel (none here)
     // node-state and category posteriors (mbamd_posteriors.h), as on the single-precision engine: synchronous
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues, double* sums);
@@ -167,9 +166,9 @@ private:
     template <class E> friend int edge_list_begin(E&, const char*);
     template <class E> friend int edge_check(const E&, const char*, int, int, int);
     template <class E> friend int edge_list_fill(E&, const int*, const int*, int, GradEdge*);
-    template <class E> friend int edge_gradient(E&, const int*, const int*, const int*, const int*, int, double*, size_t, double*, double*);
     template <class E> friend int cross_products(E&, const int*, const int*, const int*, const int*, const double*, int, double*);
-    template <class E> friend int edge_second_derivatives(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E> friend int edge_readout(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
+    template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
@@ -205,7 +204,7 @@ private:
     void afterSync() {}
     // launches for kernelTiming to report
     void countLaunches(int n) { preLaunches += (uint64_t) n; }
-    long secondLaunches[2] = {0, 0};  // read-out launches of edge_second_derivatives: plain / matrix-core kernel
+    long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     // f(this engine's layout as a compile-time constant)
     template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }
     int posteriorOperands(DerivArgs& a);
@@ -1301,18 +1300,14 @@ inline DerivArgs Engine64::layoutArgs() const
     return a;
 }
 inline int Engine64::updatePrePartials(const BeagleOperation* ops, int n, int cumIdx) { return update_pre_partials(*this, ops, n, cumIdx); }
-inline int Engine64::edgeGradient(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, double* sums, double* sumsSq)
+inline int Engine64::edgeReadout(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count, double* sites1,
+                                 double* sites2, double* sums1, double* sums2)
 {
-    return edge_gradient(*this, post, pre, dmat, wIdx, count, sites, (size_t) P, sums, sumsSq);
+    return edge_readout(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, (size_t) P, sums1, sums2);
 }
 inline int Engine64::crossProducts(const int* post, const int* pre, const int* rateIdx, const int* wIdx, const double* lengths, int count, double* out)
 {
     return cross_products(*this, post, pre, rateIdx, wIdx, lengths, count, out);
-}
-inline int Engine64::edgeSecondDerivatives(const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
-                                           double* sites1, double* sites2, double* sums1, double* sums2)
-{
-    return edge_second_derivatives(*this, post, pre, dmat1, dmat2, wIdx, count, sites1, sites2, (size_t) P, sums1, sums2);
 }
 inline int Engine64::nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
                                     double* sums)

@@ -9,11 +9,11 @@
 //     j_k(a) = pre_n[k,c,a] post_n[k,c,a],     den_k = sum_a j_k(a),     p_c(a) = sum_k q_k(c) j_k(a) / den_k
 // with q the posterior category probabilities of the pattern (k_category_posteriors; one category: q = 1).  This is DESIGN 4.4.2's
 // argument with the identity in the place of the differential matrix: no matrix, no quotient of two buffers, no exponents.  A
-// category whose den_k is zero has underflowed and is skipped, as k_edge_gradient skips it.  A compact tip is the indicator of its
+// category whose den_k is zero has underflowed and is skipped, as k_edge_readout skips it.  A compact tip is the indicator of its
 // state, a missing state the vector of ones, the four-state bitplanes give the compatible columns; where ONE state is compatible
 // the posterior is that indicator and is written as such -- exactly 1 and 0, where the formula would give sum_k q_k.
 //
-// Arithmetic as in k_edge_gradient: the product in the engine's precision, den_k and the sum over the categories in double (the
+// Arithmetic as in k_edge_readout: the product in the engine's precision, den_k and the sum over the categories in double (the
 // division once per category: q_k / den_k), block sums through mbd_wave_sum_store, then k_gradient_sums over the S rows of a node.
 #ifndef MBAMD_POSTERIORS_H_
 #define MBAMD_POSTERIORS_H_
@@ -37,7 +37,7 @@ struct PosteriorArgs {
 // dynamic LDS of the general form: one column of S doubles per thread, [state][thread]
 inline size_t posterior_lds_bytes(int S) { return (size_t) S * 64 * sizeof(double); }
 
-// Grid (64-pattern blocks, nodes), one thread per pattern, looping over the categories: the sibling of k_edge_gradient.
+// Grid (64-pattern blocks, nodes), one thread per pattern, looping over the categories: the sibling of k_edge_readout.
 // Four states (DERIV_S4): two f4 loads per category (one and the bitplanes at a compact tip), the four running sums in registers.
 // Other layouts: the thread's running column p(.) lies in LDS, [state][thread] (as a private array indexed at run time it would be
 // scratch: k_final_pass, k_pre_partials), and a category is walked twice -- den_k, then the accumulation; the second walk finds the
@@ -130,17 +130,6 @@ k_node_posteriors(PosteriorArgs a)
 
 // ---- host side, shared by the two engines (the hooks: mbamd_preorder.h) ------------------------------------------------------
 
-// nodes of a posterior call per launch: the staging behind one launch ([nodes][S][Ppad] per-site values if asked for, [nodes][Ppad]
-// best values and as many best states if asked for, [nodes][S][nb] block sums, [nodes][S] sums) stays within 4 Mi doubles.
-// cap > 0 (MBAMD_POSTERIOR_NODES, test only): at most that many.
-inline int posterior_chunk(int count, int S, int Ppad, bool sites, bool best, int cap)
-{
-    const size_t per = (size_t) S * (Ppad / 64) + (size_t) S + (sites ? (size_t) S * Ppad : 0) + (best ? (size_t) 2 * Ppad : 0);
-    size_t n = std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
-    if (cap > 0) n = std::min<size_t>(n, (size_t) cap);
-    return (int) n;
-}
-
 template <int LAYOUT, class Real>
 inline void launch_node_posteriors(hipStream_t stream, const PosteriorArgs& a, int nn)
 {
@@ -156,11 +145,10 @@ inline void launch_node_posteriors(hipStream_t stream, const PosteriorArgs& a, i
     }
 }
 
-// mbamdCalculateNodePosteriors on the engine's patterns, as edge_gradient: the nodes in chunks (posterior_chunk), per chunk one launch
-// of k_node_posteriors and one of k_gradient_sums over the chunk's nodes x S rows, then the chunk's results come back.  Synchronous.
-// sums[i * S + a] is this engine's weighted sum of state a at node i; sites (or null) takes p_c(a) of node i at
-// sites[(i * siteStride + c) * S + a] -- the staging is [state][pattern], the copy transposes --, bestStates / bestValues (or null,
-// each) the best state of pattern c and its posterior at [i * siteStride + c].
+// mbamdCalculateNodePosteriors on the engine's patterns, through chunked_readout (mbamd_preorder.h): per chunk of nodes one launch
+// of k_node_posteriors and k_gradient_sums over the chunk's nodes x S rows.  sums[i * S + a] is this engine's weighted sum of state
+// a at node i; sites (or null) takes p_c(a) of node i at sites[(i * siteStride + c) * S + a] -- the staging is [state][pattern], the
+// copy transposes --, bestStates / bestValues (or null, each) the best state of pattern c and its posterior at [i * siteStride + c].
 template <class Engine>
 inline int node_posteriors(Engine& e, const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates,
                            double* bestValues, size_t siteStride, double* sums)
@@ -176,58 +164,45 @@ inline int node_posteriors(Engine& e, const int* post, const int* pre, const int
     { const int rc = edge_list_fill(e, post, pre, count, table.data()); if (rc) return rc; }
     void* d_table = nullptr;
     { const int rc = e.stageTable(table.data(), table.size() * sizeof(GradEdge), &d_table); if (rc) return rc; }
-    const int S = e.S, P = e.P, Ppad = e.Ppad, nb = Ppad / 64;
+    const int S = e.S, P = e.P;
+    const size_t Ppad = (size_t) e.Ppad;
     const bool best = bestStates != nullptr || bestValues != nullptr;
-    const int chunk = posterior_chunk(count, S, Ppad, sites != nullptr, best, e.sw.posteriorNodes.value_or(0));
-    const size_t nSite = sites ? (size_t) chunk * S * Ppad : 0, nBest = best ? (size_t) chunk * Ppad : 0;
-    const size_t nBlock = (size_t) chunk * S * nb, nOut = (size_t) chunk * S;
-    double* d_site = nullptr;
-    { const int rc = e.resultScratch((nSite + 2 * nBest + nBlock + nOut) * sizeof(double), &d_site); if (rc) return rc; }
-    double* const d_best = d_site + nSite;
-    int* const d_bestState = reinterpret_cast<int*>(d_best + nBest);          // (nBest ints in the room of nBest doubles)
-    double* const d_block = d_best + 2 * nBest;
-    double* const d_out = d_block + nBlock;
-    std::vector<double> h(nSite + nBest + nOut);
-    std::vector<int> hState(nBest);
-    double* const h_best = h.data() + nSite;
-    double* const h_out = h_best + nBest;
+    // the per-pattern outputs: the posteriors, then the best values and the best states
+    ReadoutShape shape = {};
+    if (sites) shape.site[shape.siteCount++] = {S, sizeof(double)};
+    const int bestAt = shape.siteCount;
+    if (best) {
+        shape.site[shape.siteCount++] = {1, sizeof(double)};
+        shape.site[shape.siteCount++] = {1, sizeof(int)};
+    }
+    shape.sumPlanes = 1;
+    shape.sumRows = S;
+    shape.cap = e.sw.posteriorNodes.value_or(0);
     PosteriorArgs a;
     a.g = e.layoutArgs();
     a.q = e.K > 1 ? e.d_q : nullptr;
     a.pattern_weights = e.d_pweights;
-    a.site = sites ? d_site : nullptr;
-    a.best = best ? d_best : nullptr;
-    a.bestState = best ? d_bestState : nullptr;
-    a.sums = d_block;
-    a.nb = nb;
-    for (int n0 = 0; n0 < count; n0 += chunk) {
-        const int nn = std::min(chunk, count - n0);
-        a.nodes = static_cast<const GradEdge*>(d_table) + n0;
-        e.withLayout([&](auto L) { launch_node_posteriors<L(), deriv_real<L()>>(e.stream, a, nn); });
-        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) (nn * S), 1u), 64, 0, e.stream, (const double*) d_block, nb, nn * S, d_out);
-        HIP_TRY(hipGetLastError());
-        e.countLaunches(2);
-        HIP_TRY(hipStreamSynchronize(e.stream));
-        e.afterSync();
-        if (sites) HIP_TRY(hipMemcpy(h.data(), d_site, (size_t) nn * S * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-        if (best) {
-            HIP_TRY(hipMemcpy(h_best, d_best, (size_t) nn * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(hState.data(), d_bestState, (size_t) nn * Ppad * sizeof(int), hipMemcpyDeviceToHost));
-        }
-        HIP_TRY(hipMemcpy(h_out, d_out, (size_t) nn * S * sizeof(double), hipMemcpyDeviceToHost));
-        for (int i = 0; i < nn; ++i) {
-            const size_t to = (size_t) (n0 + i) * siteStride;
+    a.nb = e.Ppad / 64;
+    return chunked_readout(e, count, shape,
+        [&](const ReadoutChunk& ch) {
+            a.nodes = static_cast<const GradEdge*>(d_table) + ch.first;
+            a.site = sites ? static_cast<double*>(ch.site[0]) : nullptr;
+            a.best = best ? static_cast<double*>(ch.site[bestAt]) : nullptr;
+            a.bestState = best ? static_cast<int*>(ch.site[bestAt + 1]) : nullptr;
+            a.sums = ch.sums;
+            e.withLayout([&](auto L) { launch_node_posteriors<L(), deriv_real<L()>>(e.stream, a, ch.count); });
+        },
+        [&](const ReadoutChunk& ch, int i) {
+            const size_t to = (size_t) (ch.first + i) * siteStride;
             if (sites) {
-                const double* const from = h.data() + (size_t) i * S * Ppad;
+                const double* const from = static_cast<const double*>(ch.site[0]) + (size_t) i * S * Ppad;
                 for (int s = 0; s < S; ++s)
                     for (int c = 0; c < P; ++c) sites[(to + c) * S + s] = from[(size_t) s * Ppad + c];
             }
-            if (bestValues) std::memcpy(bestValues + to, h_best + (size_t) i * Ppad, (size_t) P * sizeof(double));
-            if (bestStates) std::memcpy(bestStates + to, hState.data() + (size_t) i * Ppad, (size_t) P * sizeof(int));
-            std::memcpy(sums + (size_t) (n0 + i) * S, h_out + (size_t) i * S, (size_t) S * sizeof(double));
-        }
-    }
-    return BEAGLE_SUCCESS;
+            if (bestValues) std::memcpy(bestValues + to, static_cast<const double*>(ch.site[bestAt]) + (size_t) i * Ppad, (size_t) P * sizeof(double));
+            if (bestStates) std::memcpy(bestStates + to, static_cast<const int*>(ch.site[bestAt + 1]) + (size_t) i * Ppad, (size_t) P * sizeof(int));
+            std::memcpy(sums + (size_t) (ch.first + i) * S, ch.sums + (size_t) i * S, (size_t) S * sizeof(double));
+        });
 }
 
 // mbamdGetCategoryPosteriors on the engine's patterns: q_k(c) of the latest log-likelihood call at out[k * stride + c] (d_q without

@@ -18,7 +18,7 @@
 // categories of the read-outs in double, block sums through mbd_wave_sum_store (fixed order).
 //
 // The same read with a second differential matrix gives the second derivative beside the first (mbamdCalculateEdgeSecondDerivatives:
-// k_edge_second, k_edge_second_mfma and edge_second_derivatives below).
+// k_edge_readout at order 2, k_edge_second_mfma and edge_readout below).
 #ifndef MBAMD_PREORDER_H_
 #define MBAMD_PREORDER_H_
 
@@ -56,14 +56,17 @@ struct GradEdge {
     int         postTip;
     int         pad_;
 };
-struct GradArgs {
-    DerivArgs       g;
-    const GradEdge* edges;        // the edges of this launch (grid y)
-    const double*   q;            // [K][Ppad] posterior category probabilities, or null (one category: q = 1)
-    const double*   pattern_weights;
-    double*         site;         // [edges][Ppad] unweighted d_c, or null: block sums only
-    double*         sums;         // [2][edges][nb]: weight_c d_c and weight_c d_c^2, one per 64-pattern block
-    int             nb, edgeCount;
+// the arguments of the read-out kernels of the gradient call (order 1) and of the second-derivative call (order 2)
+struct ReadoutArgs {
+    DerivArgs          g;
+    const GradEdge*    edges;     // the edges of this launch (grid y); D = the first differential matrix
+    const void* const* D2;        // order 2: the edges' second differential matrices (they follow the edge table); order 1: not read
+    const double*      q;         // [K][Ppad] posterior category probabilities, or null (one category: q = 1)
+    const double*      pattern_weights;
+    double*            site;      // [edges][Ppad] unweighted d_c (order 2: d1_c), or null: block sums only
+    double*            site2;     // order 2: [edges][Ppad] unweighted d2_c, or null; order 1: not read
+    double*            sums;      // [2][edges][nb]: weight_c d_c and weight_c d_c^2 (order 2: weight_c d2_c), one per 64-pattern block
+    int                nb, edgeCount;
 };
 
 __device__ __forceinline__ int pre_exponent(float mx) { return (mx > 0.0f && mx < 3.0e38f) ? mbd_frexp_exp(mx) : 0; }
@@ -206,105 +209,18 @@ k_category_posteriors(DerivArgs a)
     for (int k = 0; k < K; ++k) a.site[(size_t) k * a.Ppad + c] = L > 0.0 ? a.site[(size_t) k * a.Ppad + c] / L : 0.0;
 }
 
-// d_c of every edge of the launch: grid (64-pattern blocks, edges), one thread per pattern, looping over the categories.
-template <int LAYOUT, class Real>
+// d_c of every edge of the launch: grid (64-pattern blocks, edges), one thread per pattern, looping over the categories.  ORDER 2 meets
+// every row of D2 with the post-order value the same row of D meets, and its d is the d of ORDER 1, operation for operation.
+template <int LAYOUT, class Real, int ORDER>
 __global__ void __launch_bounds__(64)
-k_edge_gradient(GradArgs a)
+k_edge_readout(ReadoutArgs a)
 {
     const DerivArgs& g = a.g;
     const int S = g.S, K = g.K;
     const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
     const GradEdge ed = a.edges[blockIdx.y];
-    double d = 0.0, pw = 0.0;
-    if (c < g.last) {
-        const unsigned tip = ed.postTip ? deriv_tip<LAYOUT>(ed.post, g, c) : 0u;
-        for (int k = 0; k < K; ++k) {
-            double num = 0.0, den = 0.0;
-            if constexpr (LAYOUT == DERIV_S4) {
-                const size_t at = blk_index(c, g.pstride) + (size_t) k * 64;
-                const f4 p4 = reinterpret_cast<const f4*>(ed.pre)[at];
-                const float p[4] = {p4.x, p4.y, p4.z, p4.w};
-                float v[4];
-                if (ed.postTip) {
-                    for (int j = 0; j < 4; ++j) v[j] = (tip >> j & 1u) ? 1.0f : 0.0f;
-                } else {
-                    const f4 q4 = reinterpret_cast<const f4*>(ed.post)[at];
-                    v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
-                }
-                const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(ed.D)) + k * 16;          // m[j * 4 + l] = D(l -> j)
-#pragma unroll
-                for (int l = 0; l < 4; ++l) {
-                    const float f = fmaf(m[12 + l], v[3], fmaf(m[8 + l], v[2], fmaf(m[4 + l], v[1], m[l] * v[0])));
-                    num += (double) (p[l] * f);
-                    den += (double) (p[l] * v[l]);
-                }
-            } else {
-                for (int l = 0; l < S; ++l) {
-                    const Real p = deriv_partial<LAYOUT, Real>(ed.pre, g, k, l, c);
-                    Real f = (Real) 0, v;
-                    if (ed.postTip) {
-                        // (a missing state is the vector of ones: the rows of D sum to zero)
-                        v = (tip >= (unsigned) S || tip == (unsigned) l) ? (Real) 1 : (Real) 0;
-                        if (tip < (unsigned) S) f = deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, (int) tip);
-                    } else {
-                        for (int j = 0; j < S; ++j)
-                            f = deriv_fma(deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, j), deriv_partial<LAYOUT, Real>(ed.post, g, k, j, c), f);
-                        v = deriv_partial<LAYOUT, Real>(ed.post, g, k, l, c);
-                    }
-                    num += (double) (p * f);
-                    den += (double) (p * v);
-                }
-            }
-            if (den > 0.0) d += (a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0) * (num / den);
-        }
-        if (a.site != nullptr) a.site[(size_t) blockIdx.y * g.Ppad + c] = d;
-        pw = a.pattern_weights[c];
-    }
-    mbd_wave_sum_store(pw * d, a.sums + (size_t) blockIdx.y * a.nb + blockIdx.x);
-    mbd_wave_sum_store(pw * d * d, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
-}
-
-// out[q * edges + e] = the sum of the nb block sums of (q, e), in a fixed order: grid (edges, 2), one wave each
-__global__ void __launch_bounds__(64)
-k_gradient_sums(const double* __restrict__ sums, int nb, int edges, double* __restrict__ out)
-{
-    const size_t row = (size_t) blockIdx.y * edges + blockIdx.x;
-    double s = 0.0;
-    for (int b = (int) threadIdx.x; b < nb; b += 64) s += sums[row * nb + b];
-    mbd_wave_sum_store(s, out + row);
-}
-
-// ---- first AND second derivative of every branch (mbamdCalculateEdgeSecondDerivatives; semantics: beagle.h, DESIGN 4.4.6) --------
-// With a second differential matrix D2_k (r_k^2 Q^2 for a branch length) beside D1_k, per category
-//     g1_k(c), g2_k(c) = (sum_l pre[l] sum_j D1_k / D2_k [l,j] post[j]) / (sum_l pre[l] post[l])
-// from ONE read of the two columns, and
-//     d1_c = sum_k q_k(c) g1_k(c),     d2_c = sum_k q_k(c) g2_k(c) - d1_c^2
-// d1 is k_edge_gradient's, operation for operation.  A compact tip with a missing state: the vector of ones in the denominator and
-// nothing in either numerator (the rows of a differential matrix sum to zero) where the layout stores state codes; the four-state
-// bitplanes add the compatible columns, as k_edge_gradient does.
-struct SecondArgs {
-    DerivArgs          g;
-    const GradEdge*    edges;     // the edges of this launch (grid y); D = the first differential matrix
-    const void* const* D2;        // ... and their second differential matrices
-    const double*      q;         // [K][Ppad] posterior category probabilities, or null (one category: q = 1)
-    const double*      pattern_weights;
-    double*            site1;     // [edges][Ppad] unweighted d1_c, or null
-    double*            site2;     // [edges][Ppad] unweighted d2_c, or null
-    double*            sums;      // [2][edges][nb]: weight_c d1_c and weight_c d2_c, one per 64-pattern block
-    int                nb, edgeCount;
-};
-
-// The plain kernel, the sibling of k_edge_gradient: grid (64-pattern blocks, edges), one thread per pattern, looping over the
-// categories; the post-order value a row of D1 meets is the one the same row of D2 meets.
-template <int LAYOUT, class Real>
-__global__ void __launch_bounds__(64)
-k_edge_second(SecondArgs a)
-{
-    const DerivArgs& g = a.g;
-    const int S = g.S, K = g.K;
-    const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
-    const GradEdge ed = a.edges[blockIdx.y];
-    const void* const D2 = a.D2[blockIdx.y];
+    const void* D2 = nullptr;
+    if constexpr (ORDER == 2) D2 = a.D2[blockIdx.y];
     double d = 0.0, d2 = 0.0, pw = 0.0;
     if (c < g.last) {
         const unsigned tip = ed.postTip ? deriv_tip<LAYOUT>(ed.post, g, c) : 0u;
@@ -322,13 +238,15 @@ k_edge_second(SecondArgs a)
                     v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
                 }
                 const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(ed.D)) + k * 16;          // m[j * 4 + l] = D(l -> j)
-                const MBAMD_AS_CONST float* m2 = as_const(reinterpret_cast<const float*>(D2)) + k * 16;
 #pragma unroll
                 for (int l = 0; l < 4; ++l) {
                     const float f = fmaf(m[12 + l], v[3], fmaf(m[8 + l], v[2], fmaf(m[4 + l], v[1], m[l] * v[0])));
-                    const float f2 = fmaf(m2[12 + l], v[3], fmaf(m2[8 + l], v[2], fmaf(m2[4 + l], v[1], m2[l] * v[0])));
                     num += (double) (p[l] * f);
-                    num2 += (double) (p[l] * f2);
+                    if constexpr (ORDER == 2) {
+                        const MBAMD_AS_CONST float* m2 = as_const(reinterpret_cast<const float*>(D2)) + k * 16;
+                        const float f2 = fmaf(m2[12 + l], v[3], fmaf(m2[8 + l], v[2], fmaf(m2[4 + l], v[1], m2[l] * v[0])));
+                        num2 += (double) (p[l] * f2);
+                    }
                     den += (double) (p[l] * v[l]);
                 }
             } else {
@@ -336,38 +254,58 @@ k_edge_second(SecondArgs a)
                     const Real p = deriv_partial<LAYOUT, Real>(ed.pre, g, k, l, c);
                     Real f = (Real) 0, f2 = (Real) 0, v;
                     if (ed.postTip) {
+                        // (a missing state is the vector of ones: the rows of a differential matrix sum to zero)
                         v = (tip >= (unsigned) S || tip == (unsigned) l) ? (Real) 1 : (Real) 0;
                         if (tip < (unsigned) S) {
                             f = deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, (int) tip);
-                            f2 = deriv_matrix<LAYOUT, Real>(D2, g, k, l, (int) tip);
+                            if constexpr (ORDER == 2) f2 = deriv_matrix<LAYOUT, Real>(D2, g, k, l, (int) tip);
                         }
                     } else {
                         for (int j = 0; j < S; ++j) {
                             const Real x = deriv_partial<LAYOUT, Real>(ed.post, g, k, j, c);
                             f = deriv_fma(deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, j), x, f);
-                            f2 = deriv_fma(deriv_matrix<LAYOUT, Real>(D2, g, k, l, j), x, f2);
+                            if constexpr (ORDER == 2) f2 = deriv_fma(deriv_matrix<LAYOUT, Real>(D2, g, k, l, j), x, f2);
                         }
                         v = deriv_partial<LAYOUT, Real>(ed.post, g, k, l, c);
                     }
                     num += (double) (p * f);
-                    num2 += (double) (p * f2);
+                    if constexpr (ORDER == 2) num2 += (double) (p * f2);
                     den += (double) (p * v);
                 }
             }
             if (den > 0.0) {
                 const double qk = a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0;
                 d += qk * (num / den);
-                d2 += qk * (num2 / den);
+                if constexpr (ORDER == 2) d2 += qk * (num2 / den);
             }
         }
-        d2 -= d * d;
-        if (a.site1 != nullptr) a.site1[(size_t) blockIdx.y * g.Ppad + c] = d;
-        if (a.site2 != nullptr) a.site2[(size_t) blockIdx.y * g.Ppad + c] = d2;
+        if constexpr (ORDER == 2) d2 -= d * d;
+        if (a.site != nullptr) a.site[(size_t) blockIdx.y * g.Ppad + c] = d;
+        if constexpr (ORDER == 2) { if (a.site2 != nullptr) a.site2[(size_t) blockIdx.y * g.Ppad + c] = d2; }
         pw = a.pattern_weights[c];
     }
     mbd_wave_sum_store(pw * d, a.sums + (size_t) blockIdx.y * a.nb + blockIdx.x);
-    mbd_wave_sum_store(pw * d2, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
+    mbd_wave_sum_store(ORDER == 2 ? pw * d2 : pw * d * d, a.sums + ((size_t) a.edgeCount + blockIdx.y) * a.nb + blockIdx.x);
 }
+
+// out[q * edges + e] = the sum of the nb block sums of (q, e), in a fixed order: grid (edges, 2), one wave each
+__global__ void __launch_bounds__(64)
+k_gradient_sums(const double* __restrict__ sums, int nb, int edges, double* __restrict__ out)
+{
+    const size_t row = (size_t) blockIdx.y * edges + blockIdx.x;
+    double s = 0.0;
+    for (int b = (int) threadIdx.x; b < nb; b += 64) s += sums[row * nb + b];
+    mbd_wave_sum_store(s, out + row);
+}
+
+// ---- first AND second derivative of every branch (mbamdCalculateEdgeSecondDerivatives; semantics: beagle.h, DESIGN 4.4.6) --------
+// With a second differential matrix D2_k (r_k^2 Q^2 for a branch length) beside D1_k, per category
+//     g1_k(c), g2_k(c) = (sum_l pre[l] sum_j D1_k / D2_k [l,j] post[j]) / (sum_l pre[l] post[l])
+// from ONE read of the two columns, and
+//     d1_c = sum_k q_k(c) g1_k(c),     d2_c = sum_k q_k(c) g2_k(c) - d1_c^2
+// The plain kernel is k_edge_readout at ORDER 2.  A compact tip with a missing state: the vector of ones in the denominator and
+// nothing in either numerator (the rows of a differential matrix sum to zero) where the layout stores state codes; the four-state
+// bitplanes add the compatible columns.
 
 // dynamic LDS of the matrix-core kernel: the post-order and the pre-order column of the block, [state][thread], 32 TILES rows each
 inline size_t second_lds_bytes(int tiles) { return (size_t) 2 * 32 * tiles * 64 * sizeof(float); }
@@ -375,7 +313,7 @@ inline size_t second_lds_bytes(int tiles) { return (size_t) 2 * 32 * tiles * 64 
 // 16 .. 64 states on the fp32 engine: grid (64-pattern blocks, edges), one wave per workgroup, ONE EDGE per workgroup (the two
 // matrices change with the edge and the category, so a wave that looped over edges would keep nothing but its sums; see DESIGN
 // 4.4.6 for the register and LDS budget).  Per category the wave stages its 64 patterns' columns (thread = pattern; den is summed
-// there, in k_edge_gradient's order) and forms F1 = D1 post, F2 = D2 post, 32 TILES states x 64 patterns each, with
+// there, in k_edge_readout's order) and forms F1 = D1 post, F2 = D2 post, 32 TILES states x 64 patterns each, with
 // mbd_mfma_f32_32x32x2: row tiles hold states, the two column tiles patterns 0 .. 31 and 32 .. 63, the reduction runs over the
 // post-order state j, two per instruction -- lane l feeds A[l & 31][l >> 5] = D(32 rt + (l & 31) -> 2 s + (l >> 5)), read from the
 // matrix buffer where it lies (zero beyond S), and B[l >> 5][l & 31] = post[2 s + (l >> 5)][pattern 32 ct + (l & 31)] from LDS.
@@ -384,7 +322,7 @@ inline size_t second_lds_bytes(int tiles) { return (size_t) 2 * 32 * tiles * 64 
 // double, the two half-waves of a column are joined by mbd_shfl_xor(., 32), and lane l takes the column of ITS pattern.
 template <int LAYOUT, int TILES>
 __global__ void __launch_bounds__(64)
-k_edge_second_mfma(SecondArgs a)
+k_edge_second_mfma(ReadoutArgs a)
 {
     constexpr int ROWS = 32 * TILES;
     const DerivArgs& g = a.g;
@@ -475,7 +413,7 @@ k_edge_second_mfma(SecondArgs a)
     double pw = 0.0;
     if (live) {
         d2 -= d * d;
-        if (a.site1 != nullptr) a.site1[(size_t) blockIdx.y * g.Ppad + c] = d;
+        if (a.site != nullptr) a.site[(size_t) blockIdx.y * g.Ppad + c] = d;
         if (a.site2 != nullptr) a.site2[(size_t) blockIdx.y * g.Ppad + c] = d2;
         pw = a.pattern_weights[c];
     }
@@ -547,14 +485,6 @@ inline void launch_pre_partials(hipStream_t stream, const PreArgs& a, int count)
             (void) hipGetLastError();
         MBAMD_LAUNCH_BARRIER(kernel, dim3((unsigned) (a.g.Ppad / 64), (unsigned) a.g.K, (unsigned) count), 64, lds, stream, a);
     }
-}
-
-// edges of a gradient call per launch: the staging behind one launch ([edges][Ppad] per-site values if asked for, [2][edges][nb] block
-// sums, [2][edges] sums) stays within 4 Mi doubles
-inline int gradient_chunk(int count, int Ppad, bool sites)
-{
-    const size_t per = (size_t) 2 * (Ppad / 64) + 2 + (sites ? (size_t) Ppad : 0);
-    return (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
 }
 
 // beagleUpdatePrePartials: the list is checked as a whole, cut into launches (pre_order_groups) and run, one launch per group.
@@ -681,78 +611,87 @@ inline int edge_list_fill(Engine& e, const int* post, const int* pre, int count,
     return BEAGLE_SUCCESS;
 }
 
-// beagleCalculateEdgeDerivatives on the engine's patterns: the edges in chunks (gradient_chunk), per chunk one launch of k_edge_gradient
-// and one of k_gradient_sums, then the chunk's results come back.  Synchronous; sums[i] and sumsSq[i] are the weighted sums of edge i,
-// sites (or null) takes d_c of edge i at sites[i * siteStride + c].
-template <class Engine>
-inline int edge_gradient(Engine& e, const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* sites, size_t siteStride,
-                         double* sums, double* sumsSq)
+// ---- the chunked read-out: the gradient and second-derivative call below, the node posteriors of mbamd_posteriors.h ---------------
+// Such a call answers, per item of its list (an edge, a node), with rows of [Ppad] per-pattern values, if asked for, and with
+// weighted sums over the patterns.  The items pass through the device in chunks; per chunk the call's own read-out kernel leaves the
+// per-pattern rows and one block sum per sum row and 64-pattern block, k_gradient_sums adds the block sums, and the chunk's
+// results come back.  Synchronous.
+
+// one per-pattern output: `rows` rows of [Ppad] values of `elem` bytes (at most a double's) per item, staged [item][row][Ppad]
+struct ReadoutSites {
+    int    rows;
+    size_t elem;
+};
+// what a call stages per item: siteCount per-pattern outputs, and block sums [sumPlanes][items][sumRows][nb]
+struct ReadoutShape {
+    ReadoutSites site[3];
+    int          siteCount;
+    int          sumPlanes, sumRows;
+    int          cap;             // > 0 (MBAMD_POSTERIOR_NODES, test only): at most that many items per chunk
+};
+// items first .. first + count of the list as the launch of their chunk sees them (device memory: site[s] to fill, sums = the block
+// sums to fill) and, afterwards, its scatter (the host's copy: sums = the sums, [sumPlanes][count][sumRows])
+struct ReadoutChunk {
+    int     first, count;
+    void*   site[3];              // in the order of ReadoutShape::site
+    double* sums;
+};
+
+// items per chunk: the staging behind one launch (`per` doubles per item: per-pattern rows, block sums, sums) stays within 4 Mi doubles
+inline int readout_chunk(int count, size_t per, int cap)
 {
-    const char* const who = "beagleCalculateEdgeDerivatives";
-    { const int rc = edge_list_begin(e, who); if (rc) return rc; }
-    for (int i = 0; i < count; ++i) {
-        const int rc = edge_check(e, who, post[i], pre[i], wIdx[i]);
-        if (rc) return rc;
-        if (dmat[i] < 0 || dmat[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
-    }
-    if (count <= 0) return BEAGLE_SUCCESS;
-    std::vector<GradEdge> table((size_t) count);
-    { const int rc = edge_list_fill(e, post, pre, count, table.data()); if (rc) return rc; }
-    for (int i = 0; i < count; ++i) table[(size_t) i].D = e.matrixPtr(dmat[i]);
-    void* d_table = nullptr;
-    { const int rc = e.stageTable(table.data(), table.size() * sizeof(GradEdge), &d_table); if (rc) return rc; }
-    const int P = e.P, Ppad = e.Ppad, nb = Ppad / 64;
-    const int chunk = gradient_chunk(count, Ppad, sites != nullptr);
-    const size_t nSite = sites ? (size_t) chunk * Ppad : 0, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
+    size_t n = std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
+    if (cap > 0) n = std::min<size_t>(n, (size_t) cap);
+    return (int) n;
+}
+
+// launch(chunk) enqueues the read-out kernel of a chunk, scatter(chunk, i) takes the results of its item i to the caller's arrays
+template <class Engine, class Launch, class Scatter>
+inline int chunked_readout(Engine& e, int count, const ReadoutShape& shape, Launch&& launch, Scatter&& scatter)
+{
+    const size_t Ppad = (size_t) e.Ppad, nb = Ppad / 64, sumRows = (size_t) shape.sumPlanes * shape.sumRows;
+    size_t siteRows = 0;
+    for (int s = 0; s < shape.siteCount; ++s) siteRows += (size_t) shape.site[s].rows;
+    const int chunk = readout_chunk(count, sumRows * nb + sumRows + siteRows * Ppad, shape.cap);
+    const size_t nSite = (size_t) chunk * siteRows * Ppad, nBlock = (size_t) chunk * sumRows * nb, nOut = (size_t) chunk * sumRows;
     double* d_site = nullptr;
     { const int rc = e.resultScratch((nSite + nBlock + nOut) * sizeof(double), &d_site); if (rc) return rc; }
-    double* const d_block = d_site + nSite;
-    double* const d_out = d_block + nBlock;
+    double* const d_out = d_site + nSite + nBlock;
     std::vector<double> h(nSite + nOut);
-    GradArgs a;
-    a.g = e.layoutArgs();
-    a.q = e.K > 1 ? e.d_q : nullptr;
-    a.pattern_weights = e.d_pweights;
-    a.site = sites ? d_site : nullptr;
-    a.sums = d_block;
-    a.nb = nb;
-    for (int e0 = 0; e0 < count; e0 += chunk) {
-        const int ne = std::min(chunk, count - e0);
-        a.edges = static_cast<const GradEdge*>(d_table) + e0;
-        a.edgeCount = ne;
-        e.withLayout([&](auto L) {
-            auto kernel = k_edge_gradient<L(), deriv_real<L()>>;
-            MBAMD_LAUNCH(kernel, dim3((unsigned) nb, (unsigned) ne), 64, 0, e.stream, a);
-        });
-        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, e.stream, (const double*) d_block, nb, ne, d_out);
+    ReadoutChunk dev, host;
+    size_t at = 0;
+    for (int s = 0; s < shape.siteCount; ++s) {
+        dev.site[s] = d_site + at;
+        host.site[s] = h.data() + at;
+        at += (size_t) chunk * shape.site[s].rows * Ppad;         // (a narrower element in the room of a double)
+    }
+    dev.sums = d_site + nSite;
+    host.sums = h.data() + nSite;
+    for (int first = 0; first < count; first += chunk) {
+        const int n = std::min(chunk, count - first);
+        dev.first = host.first = first;
+        dev.count = host.count = n;
+        launch(dev);
+        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) (n * shape.sumRows), (unsigned) shape.sumPlanes), 64, 0, e.stream, (const double*) dev.sums,
+                     (int) nb, n * shape.sumRows, d_out);
         HIP_TRY(hipGetLastError());
+        e.countLaunches(2);
         HIP_TRY(hipStreamSynchronize(e.stream));
         e.afterSync();
-        if (sites) HIP_TRY(hipMemcpy(h.data(), d_site, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h.data() + nSite, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
-        for (int i = 0; i < ne; ++i) {
-            if (sites) std::memcpy(sites + (size_t) (e0 + i) * siteStride, h.data() + (size_t) i * Ppad, (size_t) P * sizeof(double));
-            if (sums) sums[e0 + i] = h[nSite + (size_t) i];
-            if (sumsSq) sumsSq[e0 + i] = h[nSite + (size_t) ne + i];
-        }
+        for (int s = 0; s < shape.siteCount; ++s)
+            HIP_TRY(hipMemcpy(host.site[s], dev.site[s], (size_t) n * shape.site[s].rows * Ppad * shape.site[s].elem, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(host.sums, d_out, (size_t) n * sumRows * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) scatter(host, i);
     }
     return BEAGLE_SUCCESS;
 }
 
-// edges of a second-derivative call per launch: as gradient_chunk for its larger staging ([edges][Ppad] per per-site array asked
-// for -- siteArrays of them, 0 .. 2 --, [2][edges][nb] block sums, [2][edges] sums)
-inline int second_chunk(int count, int Ppad, int siteArrays)
+// the read-out launch of one chunk of edges; returns whether the matrix-core kernel took it
+template <int LAYOUT, class Real, int ORDER>
+inline bool launch_edge_readout(hipStream_t stream, const ReadoutArgs& a, bool mfma)
 {
-    const size_t per = (size_t) 2 * (Ppad / 64) + 2 + (size_t) siteArrays * Ppad;
-    return (int) std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t) count, 32768), ((size_t) 4 << 20) / per));
-}
-
-// the read-out launch of one chunk; returns whether the matrix-core kernel took it
-template <int LAYOUT, class Real>
-inline bool launch_edge_second(hipStream_t stream, const SecondArgs& a, int ne, bool mfma)
-{
-    const dim3 grid((unsigned) a.nb, (unsigned) ne);
-    if constexpr (LAYOUT == DERIV_WG || LAYOUT == DERIV_LEVELS) {
+    const dim3 grid((unsigned) a.nb, (unsigned) a.edgeCount);
+    if constexpr (ORDER == 2 && (LAYOUT == DERIV_WG || LAYOUT == DERIV_LEVELS)) {
         if (mfma) {
             const int tiles = a.g.S <= 32 ? 1 : 2;
             const size_t lds = second_lds_bytes(tiles);
@@ -761,81 +700,75 @@ inline bool launch_edge_second(hipStream_t stream, const SecondArgs& a, int ne, 
             return true;
         }
     }
-    auto kernel = k_edge_second<LAYOUT, Real>;
+    auto kernel = k_edge_readout<LAYOUT, Real, ORDER>;
     MBAMD_LAUNCH(kernel, grid, 64, 0, stream, a);
     return false;
 }
 
-// mbamdCalculateEdgeSecondDerivatives on the engine's patterns, as edge_gradient: the edges in chunks (second_chunk), per chunk one
-// launch of the read-out kernel -- k_edge_second, or k_edge_second_mfma for 16 .. 64 states in single precision (MBAMD_CURV_GENERIC:
-// the plain one) -- and one of k_gradient_sums, then the chunk's results come back.  Synchronous; sums1[i] and sums2[i] are the
-// weighted sums of d1 and d2 of edge i, sites1 / sites2 (or null) take d1_c / d2_c of edge i at [i * siteStride + c].  The engine's
-// secondLaunches[0 / 1] count the read-out launches of the plain and of the matrix-core kernel.
+// beagleCalculateEdgeDerivatives (dmat2 null: order 1) and mbamdCalculateEdgeSecondDerivatives (order 2) on the engine's patterns,
+// through chunked_readout.  The read-out kernel is k_edge_readout at that order, or at order 2, for 16 .. 64 states in single
+// precision, k_edge_second_mfma (MBAMD_CURV_GENERIC: the plain one); the engine's secondLaunches[0 / 1] count the order-2 launches
+// of the plain and of the matrix-core kernel.  sums1[i] is the weighted sum of d_c of edge i, sums2[i] that of d_c^2 (order 1) or of
+// d2_c (order 2); sites1 (or null) takes d_c of edge i at [i * siteStride + c], sites2 (or null; order 2) d2_c.
 template <class Engine>
-inline int edge_second_derivatives(Engine& e, const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
-                                   double* sites1, double* sites2, size_t siteStride, double* sums1, double* sums2)
+inline int edge_readout(Engine& e, const int* post, const int* pre, const int* dmat1, const int* dmat2, const int* wIdx, int count,
+                        double* sites1, double* sites2, size_t siteStride, double* sums1, double* sums2)
 {
-    const char* const who = "mbamdCalculateEdgeSecondDerivatives";
+    const char* const who = dmat2 ? "mbamdCalculateEdgeSecondDerivatives" : "beagleCalculateEdgeDerivatives";
     { const int rc = edge_list_begin(e, who); if (rc) return rc; }
     for (int i = 0; i < count; ++i) {
         const int rc = edge_check(e, who, post[i], pre[i], wIdx[i]);
         if (rc) return rc;
         if (dmat1[i] < 0 || dmat1[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "differential matrix index");
-        if (dmat2[i] < 0 || dmat2[i] >= e.nMatrices) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "second differential matrix index");
+        if (dmat2 && (dmat2[i] < 0 || dmat2[i] >= e.nMatrices)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "second differential matrix index");
     }
     if (count <= 0) return BEAGLE_SUCCESS;
-    // the table: the edges, then their second matrices
+    // the table: the edges, then (order 2) their second matrices
     const size_t edgeBytes = (size_t) count * sizeof(GradEdge);
-    std::vector<unsigned char> table(edgeBytes + (size_t) count * sizeof(void*), 0);
+    std::vector<unsigned char> table(edgeBytes + (dmat2 ? (size_t) count * sizeof(void*) : 0), 0);
     GradEdge* const edges = reinterpret_cast<GradEdge*>(table.data());
     { const int rc = edge_list_fill(e, post, pre, count, edges); if (rc) return rc; }
     const void** const second = reinterpret_cast<const void**>(table.data() + edgeBytes);
-    for (int i = 0; i < count; ++i) { edges[i].D = e.matrixPtr(dmat1[i]); second[i] = e.matrixPtr(dmat2[i]); }
+    for (int i = 0; i < count; ++i) {
+        edges[i].D = e.matrixPtr(dmat1[i]);
+        if (dmat2) second[i] = e.matrixPtr(dmat2[i]);
+    }
     void* d_table = nullptr;
     { const int rc = e.stageTable(table.data(), table.size(), &d_table); if (rc) return rc; }
-    const int P = e.P, Ppad = e.Ppad, nb = Ppad / 64;
-    const int siteArrays = (sites1 ? 1 : 0) + (sites2 ? 1 : 0);
-    const int chunk = second_chunk(count, Ppad, siteArrays);
-    const size_t nSite = (size_t) chunk * Ppad, nBlock = (size_t) 2 * chunk * nb, nOut = (size_t) 2 * chunk;
-    double* d_site = nullptr;
-    { const int rc = e.resultScratch((siteArrays * nSite + nBlock + nOut) * sizeof(double), &d_site); if (rc) return rc; }
-    double* const d_block = d_site + siteArrays * nSite;
-    double* const d_out = d_block + nBlock;
-    std::vector<double> h(siteArrays * nSite + nOut);
-    double* const h_out = h.data() + siteArrays * nSite;
-    SecondArgs a;
+    ReadoutShape shape = {};
+    if (sites1) shape.site[shape.siteCount++] = {1, sizeof(double)};
+    if (sites2) shape.site[shape.siteCount++] = {1, sizeof(double)};
+    shape.sumPlanes = 2;
+    shape.sumRows = 1;
+    ReadoutArgs a;
     a.g = e.layoutArgs();
     a.q = e.K > 1 ? e.d_q : nullptr;
     a.pattern_weights = e.d_pweights;
-    a.site1 = sites1 ? d_site : nullptr;
-    a.site2 = sites2 ? d_site + (sites1 ? nSite : 0) : nullptr;
-    a.sums = d_block;
-    a.nb = nb;
+    a.nb = e.Ppad / 64;
     const bool mfma = e.S >= 16 && e.S <= 64 && !e.sw.curvGeneric;
-    for (int e0 = 0; e0 < count; e0 += chunk) {
-        const int ne = std::min(chunk, count - e0);
-        a.edges = static_cast<const GradEdge*>(d_table) + e0;
-        a.D2 = reinterpret_cast<const void* const*>(static_cast<const unsigned char*>(d_table) + edgeBytes) + e0;
-        a.edgeCount = ne;
-        const bool core = e.withLayout([&](auto L) { return launch_edge_second<L(), deriv_real<L()>>(e.stream, a, ne, mfma); });
-        MBAMD_LAUNCH(k_gradient_sums, dim3((unsigned) ne, 2u), 64, 0, e.stream, (const double*) d_block, nb, ne, d_out);
-        HIP_TRY(hipGetLastError());
-        e.countLaunches(2);
-        ++e.secondLaunches[core ? 1 : 0];
-        HIP_TRY(hipStreamSynchronize(e.stream));
-        e.afterSync();
-        for (int s = 0; s < siteArrays; ++s)
-            HIP_TRY(hipMemcpy(h.data() + s * nSite, d_site + s * nSite, (size_t) ne * Ppad * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h_out, d_out, (size_t) 2 * ne * sizeof(double), hipMemcpyDeviceToHost));
-        for (int i = 0; i < ne; ++i) {
-            const double* hs = h.data() + (size_t) i * Ppad;
-            if (sites1) { std::memcpy(sites1 + (size_t) (e0 + i) * siteStride, hs, (size_t) P * sizeof(double)); hs += nSite; }
-            if (sites2) std::memcpy(sites2 + (size_t) (e0 + i) * siteStride, hs, (size_t) P * sizeof(double));
-            if (sums1) sums1[e0 + i] = h_out[i];
-            if (sums2) sums2[e0 + i] = h_out[(size_t) ne + i];
-        }
-    }
-    return BEAGLE_SUCCESS;
+    const size_t P = (size_t) e.P;
+    return chunked_readout(e, count, shape,
+        [&](const ReadoutChunk& ch) {
+            a.edges = static_cast<const GradEdge*>(d_table) + ch.first;
+            a.D2 = dmat2 ? reinterpret_cast<const void* const*>(static_cast<const unsigned char*>(d_table) + edgeBytes) + ch.first : nullptr;
+            a.edgeCount = ch.count;
+            a.site = sites1 ? static_cast<double*>(ch.site[0]) : nullptr;
+            a.site2 = sites2 ? static_cast<double*>(ch.site[sites1 ? 1 : 0]) : nullptr;
+            a.sums = ch.sums;
+            if (dmat2) {
+                const bool core = e.withLayout([&](auto L) { return launch_edge_readout<L(), deriv_real<L()>, 2>(e.stream, a, mfma); });
+                ++e.secondLaunches[core ? 1 : 0];
+            } else {
+                e.withLayout([&](auto L) { launch_edge_readout<L(), deriv_real<L()>, 1>(e.stream, a, false); });
+            }
+        },
+        [&](const ReadoutChunk& ch, int i) {
+            const size_t to = (size_t) (ch.first + i), from = (size_t) i * e.Ppad;
+            if (sites1) std::memcpy(sites1 + to * siteStride, static_cast<const double*>(ch.site[0]) + from, P * sizeof(double));
+            if (sites2) std::memcpy(sites2 + to * siteStride, static_cast<const double*>(ch.site[sites1 ? 1 : 0]) + from, P * sizeof(double));
+            if (sums1) sums1[to] = ch.sums[i];
+            if (sums2) sums2[to] = ch.sums[(size_t) ch.count + i];
+        });
 }
 
 }  // namespace mbamd

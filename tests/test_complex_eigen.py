@@ -54,8 +54,8 @@ from tests import matrix_reference as mr
 from tests.engine_checks import ABS_F64, REL_F64, REL_FP64, engine_lnl
 from tests.hostemu import build_emu
 from tests.operation_reference import LONGDOUBLE_QUALIFIES
+from tests.preorder_reference import bound_factor
 from tests.pruning_reference import NTAXA, U32, U64, branch_length
-from tests.test_cross_products import bound_factor
 from tests.test_matrix_bounds import CHILD_KINDS, COPY_CASES, Held, bound_ratio, tag
 from tests.test_operation_bounds import column_scaled, element_scaled, expected_layout, f64_launches, preference, stored
 
@@ -379,7 +379,7 @@ def kappa_max(div):
 
 @functools.lru_cache(maxsize=None)
 def gradient_reference(states, ncat, npat):
-    """tests/test_preorder_gradient.reference for the non-reversible division, its matrices from expm: per node d, N, A, L and the
+    """tests/preorder_reference.reference for the non-reversible division, its matrices from expm: per node d, N, A, L and the
     S x S matrix M_n of tests/test_cross_products.reference"""
     div = division(states, ncat, npat)
     t = div.tree

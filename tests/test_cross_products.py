@@ -36,11 +36,12 @@ import pytest
 from mrbayes_amd import beagle as bg
 from mrbayes_amd import likelihood as lk
 from tests.hostemu import build_emu
+from tests.preorder_reference import bound_factor
+from tests.preorder_reference import bounds as gradient_bounds
+from tests.preorder_reference import division, gradient_indices, post_order, rate_matrix, tip_vector, unit_roundoff
+from tests.preorder_reference import reference as gradient_reference
 from tests.pruning_reference import NTAXA, U32, branch_length
 from tests.test_derivatives import expected_layout
-from tests.test_preorder_gradient import bounds as gradient_bounds
-from tests.test_preorder_gradient import division, gradient_indices, post_order, rate_matrix, tip_vector, unit_roundoff
-from tests.test_preorder_gradient import reference as gradient_reference
 
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 
@@ -88,10 +89,6 @@ def reference(states, ncat, npat, ntaxa=NTAXA):
 
 def x_ref(ref, nodes, lengths):
     return sum(t * ref[n] for n, t in zip(nodes, lengths))
-
-
-def bound_factor(div, ref, u):
-    return (4 * (div.nstates + 8) * (1 + 2 * ref["h"]) + 64 * div.ncat + 8) * u
 
 
 def log_likelihood(div, lengths, lam):

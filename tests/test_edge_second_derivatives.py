@@ -22,7 +22,7 @@ states -- the zero rows and zero reduction indices of its tiles add exact zeros 
 the reduction length S of this kernel in the place of 64 K).  Weighted with pre and divided by L it adds
     S u A_c / L_c to b1_c       and       S u A2_c / L_c to the first term of b2_c,
 and b2_c takes the enlarged b1_c in its other two terms.  The sums get sum_c weight_c b_c.  u = 2^-24 on the single-precision
-engine; u = 2^-53 kappa on the double-precision engine (unit_roundoff of tests/test_preorder_gradient.py).
+engine; u = 2^-53 kappa on the double-precision engine (unit_roundoff of tests/preorder_reference.py).
 """
 import ctypes as C
 import functools
@@ -33,11 +33,11 @@ import pytest
 from mrbayes_amd import beagle as bg
 from mrbayes_amd import likelihood as lk
 from tests.hostemu import build_emu
+from tests.preorder_reference import bounds as gradient_bounds
+from tests.preorder_reference import division, post_order, pre_order, rate_matrix, tip_vector, unit_roundoff
+from tests.preorder_reference import reference as gradient_reference
 from tests.pruning_reference import NTAXA, U32, branch_length, spectral
 from tests.test_derivatives import expected_layout
-from tests.test_preorder_gradient import bounds as gradient_bounds
-from tests.test_preorder_gradient import division, post_order, rate_matrix, tip_vector, unit_roundoff
-from tests.test_preorder_gradient import reference as gradient_reference
 
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 
@@ -56,19 +56,6 @@ def gpu():
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------
-def pre_order(div, post, mats):
-    """un-normalised pre-order partials [K][P][S] of every node below the root tip"""
-    t = div.tree
-    pi = np.asarray(div.pi, dtype=np.float64)
-    top = t.root_left
-    pre = {top: np.einsum("kij,ci->kcj", mats[top], pi[None, :] * tip_vector(div, t.root))}
-    for p in reversed(t.int_down_pass):
-        for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
-            tmp = pre[p] * np.einsum("kij,kcj->kci", mats[sib], post[sib])
-            pre[n] = np.einsum("kij,kci->kcj", mats[n], tmp)
-    return pre
-
-
 def second_matrices(div):
     """D2_k = r_k^2 Q^2, [K][S][S]"""
     Q = rate_matrix(div)

@@ -15,7 +15,7 @@ either buffer is a sum of non-negative terms carrying at most (S + 8) 2 h' u rel
 den, the ratio j / den and q (itself such a ratio) carry at most f = (S + 8) (1 + 2 h) u each, to first order:
     |p - p_ref| <= b = 4 f p_ref        per component,        |q - q_ref| <= 2 f q_ref
 the sums get sum_c weight_c b_c(a).  u = 2^-24 on the single-precision engine; u = 2^-53 kappa on the double-precision engine
-(unit_roundoff of tests/test_preorder_gradient.py).  Where p_ref is exactly 0 (a state a compact tip excludes) the engine's value
+(unit_roundoff of tests/preorder_reference.py).  Where p_ref is exactly 0 (a state a compact tip excludes) the engine's value
 must be exactly 0.
 """
 import ctypes as C
@@ -27,11 +27,10 @@ import pytest
 from mrbayes_amd import beagle as bg
 from mrbayes_amd import likelihood as lk
 from tests.hostemu import build_emu
+from tests.preorder_reference import CASES, CASES_F64, division, post_order, pre_order, unit_roundoff
+from tests.preorder_reference import reference as gradient_reference
 from tests.pruning_reference import NTAXA
 from tests.test_derivatives import expected_layout
-from tests.test_edge_second_derivatives import pre_order
-from tests.test_preorder_gradient import CASES, CASES_F64, division, post_order, unit_roundoff
-from tests.test_preorder_gradient import reference as gradient_reference
 
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 SENTINEL = -7.5

@@ -4,8 +4,8 @@ beagleSetDifferentialMatrix, beagleCalculateEdgeDerivatives; csrc/mbamd_preorder
   * CPU (`not gpu`): the host-emulation build of the same sources (the product's kernel bodies on the host);
   * GPU (`gpu`): the product library on a MI355X.
 
-The reference is numpy float64 from the `Division` alone: post-order pruning as in tests/pruning_reference.py, the pre-order
-recursion un-normalised,
+The reference (tests/preorder_reference.py) is numpy float64 from the `Division` alone: post-order pruning as in
+tests/pruning_reference.py, the pre-order recursion un-normalised,
     pre_top[k,c,j] = sum_i P_top,k[i,j] pi_i tip_root[c,i]
     tmp[k,c,i]     = pre_parent[k,c,i] sum_j P_sib,k[i,j] post_sib[k,c,j],      pre_n[k,c,j] = sum_i P_n,k[i,j] tmp[k,c,i]
 and Q = U diag(lambda) U^-1, D_k = r_k Q.  Per branch (node n) and pattern c
@@ -22,16 +22,15 @@ single-precision engine; u = 2^-53 kappa on the double-precision engine, kappa t
 matrices (tests/pruning_reference.py), the largest over the branches of the tree.
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 from mrbayes_amd import beagle as bg
 from mrbayes_amd import likelihood as lk
-from mrbayes_amd.division import synthetic_division
 from tests.hostemu import build_emu
-from tests.pruning_reference import NTAXA, U32, U64, branch_length, kappa, make_division, spectral
+from tests.preorder_reference import CASES, CASES_F64, bounds, division, gradient_indices, post_order, reference, unit_roundoff
+from tests.pruning_reference import NTAXA, U32
 from tests.test_derivatives import expected_layout
 
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
@@ -51,94 +50,12 @@ def gpu():
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def division(states, ncat, npat, ntaxa=NTAXA):
-    if ntaxa == NTAXA:
-        return make_division(states, ncat, npat)
-    kind = {4: "gtr", 20: "wag"}.get(states, "gen%d" % states)
-    div = synthetic_division(kind, ntaxa, npat, seed=11, tree_seed=5, alpha=0.7, ncat=ncat, p_gap=0.05)
-    div.weights = 1.0 + (np.arange(npat) % 3).astype(np.float64)
-    return div
-
-
-def tip_vector(div, tip):
-    S, P = div.nstates, div.npatterns
-    st = np.asarray(div.tip_states[tip])
-    one = np.ones((P, S))
-    ok = st < S
-    one[ok] = 0.0
-    one[np.arange(P)[ok], st[ok]] = 1.0
-    return one
-
-
-def post_order(div, lengths):
-    """post-order partials [K][P][S] of every node, and P [K][S][S] of every branch, at the branch lengths `lengths`"""
-    t, K = div.tree, div.ncat
-    mats = {n: spectral(div, lengths[n], 0)[0] for n in t.all_down_pass}
-    cl = {tip: np.broadcast_to(tip_vector(div, tip), (K, div.npatterns, div.nstates)) for tip in range(t.ntaxa)}
-    for p in t.int_down_pass:
-        out = np.ones((K, div.npatterns, div.nstates))
-        for c in (t.left[p], t.right[p]):
-            out = out * np.einsum("kij,kcj->kci", mats[c], cl[c])
-        cl[p] = out
-    return cl, mats
-
-
 def log_likelihood(div, lengths):
     t = div.tree
     cl, mats = post_order(div, lengths)
     top = t.root_left
     L = np.einsum("k,i,kci,kij,kcj->c", div.category_weights(0), np.asarray(div.pi, dtype=np.float64), cl[top], mats[top], cl[t.root])
     return float((div.weights * np.log(L)).sum())
-
-
-def rate_matrix(div):
-    es = div.eigen[0]
-    U, Ui, lam = (np.asarray(x, dtype=np.float64) for x in (es.evec, es.ivec, es.eval))
-    return (U * lam[None, :]) @ Ui
-
-
-def depth_of(t, n):
-    """pre-order operations from the start vector down to pre(n)"""
-    d = 1
-    while n != t.root_left:
-        n = t.anc[n]
-        d += 1
-    return d
-
-
-@functools.lru_cache(maxsize=None)
-def reference(states, ncat, npat, ntaxa=NTAXA):
-    """per node n of all_down_pass: d [P], N, A, L; plus h, the smallest L and the smallest un-normalised pre-order column maximum"""
-    div = division(states, ncat, npat, ntaxa)
-    t = div.tree
-    lengths = {n: branch_length(t, n) for n in t.all_down_pass}
-    post, mats = post_order(div, lengths)
-    w, pi = div.category_weights(0), np.asarray(div.pi, dtype=np.float64)
-    D = np.asarray(div.cat_rates, dtype=np.float64)[:, None, None] * rate_matrix(div)[None, :, :]
-    top = t.root_left
-    pre = {top: np.einsum("kij,ci->kcj", mats[top], pi[None, :] * tip_vector(div, t.root))}
-    for p in reversed(t.int_down_pass):
-        for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
-            tmp = pre[p] * np.einsum("kij,kcj->kci", mats[sib], post[sib])
-            pre[n] = np.einsum("kij,kci->kcj", mats[n], tmp)
-    res = {"nodes": list(t.all_down_pass), "lengths": lengths}
-    dmax = max(depth_of(t, n) for n in range(t.ntaxa) if n != t.root)
-    res["h"] = (dmax - 1) + dmax
-    res["min_column"] = min(float(v.max(axis=2).min()) for v in pre.values())
-    for n in t.all_down_pass:
-        N = np.einsum("k,kcl,klj,kcj->c", w, pre[n], D, post[n])
-        A = np.einsum("k,kcl,klj,kcj->c", w, pre[n], np.abs(D), post[n])
-        L = np.einsum("k,kcl,kcl->c", w, pre[n], post[n])
-        res[n] = dict(d=N / L, N=N, A=A, L=L)
-    res["min_L"] = min(float(res[n]["L"].min()) for n in t.all_down_pass)
-    # the root branch as tests/test_derivatives.py sees it: parent = the top node, child = the root tip, P' from the eigen-system
-    m1 = spectral(div, lengths[top], 1)[0]
-    L0 = np.einsum("k,i,kci,kij,kcj->c", w, pi, post[top], mats[top], post[t.root])
-    D1 = np.einsum("k,i,kci,kij,kcj->c", w, pi, post[top], m1, post[t.root])
-    A1 = np.einsum("k,i,kci,kij,kcj->c", w, pi, post[top], np.abs(m1), post[t.root])
-    res["root_scale1"] = (A1 + np.abs(D1)) / L0
-    return res
 
 
 def test_reference_against_finite_differences():
@@ -163,23 +80,6 @@ def test_reference_against_finite_differences():
 
 
 # ---- the per-case check -------------------------------------------------------------------------------------------------------
-def gradient_indices(bd):
-    nodes = list(bd.div.tree.all_down_pass)
-    return dict(posts=[bd.condLikeIndex[0][n] for n in nodes], pres=[bd.preOrderIndex[n] for n in nodes],
-                dmats=[bd.diffMatrixIndex] * len(nodes), weights=[bd.cijkIndex[0]] * len(nodes))
-
-
-def unit_roundoff(div, ref, double_precision):
-    if not double_precision:
-        return U32
-    return U64 * max(kappa(div, tl) for tl in set(ref["lengths"].values()))
-
-
-def bounds(div, ref, u):
-    S = div.nstates
-    return {n: (S + 8) * (1 + 2 * ref["h"]) * u * (ref[n]["A"] + np.abs(ref[n]["N"])) / ref[n]["L"] for n in ref["nodes"]}
-
-
 def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
     div = division(states, ncat, npat, ntaxa)
     ref = reference(states, ncat, npat, ntaxa)
@@ -226,17 +126,6 @@ def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
         return worst
     finally:
         bd.finalize()
-
-
-#        states, categories, patterns                     what it reaches
-CASES = [(4, 4, 130),             # two full 64-pattern blocks plus 2 patterns
-         (4, 9, 70),              # a second batch of eight categories
-         (20, 4, 70),             # two 32-pattern tiles plus 6 patterns
-         (61, 1, 40),             # one category: no posteriors
-         (12, 2, 70),             # the MFMA level layout
-         (12, 6, 70),             # the generic level layout
-         (3, 2, 70)]              # a small state count
-CASES_F64 = [(4, 4, 130), (20, 2, 70)]
 
 
 @pytest.mark.parametrize("states,ncat,npat", CASES)
@@ -442,6 +331,35 @@ def check_launch_grouping(lib, double_precision=False):
         assert launches == groups, (launches, groups, len(ops))
     finally:
         bd.finalize()
+
+
+def check_gradient_launches(lib, monkeypatch, double_precision=False):
+    """one gradient call over every branch at 4 states x 4 categories x 130 patterns is one chunk on one engine: the read-out
+    launch and the launch that adds its block sums"""
+    monkeypatch.delenv("MBAMD_SHARD", raising=False)
+    bd = lk.BeagleDivision(division(4, 4, 130), lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, pre_order=True)
+    try:
+        bd.LogLike(0)
+        bd.AcceptMove(0)
+        bd.BranchGradient(0)
+        assert bd.inst.child_count() == 1
+        bd.inst.get_kernel_timing(reset=True)
+        assert bd.inst.calculate_edge_gradient(sites=False, **gradient_indices(bd))[0] == 0
+        _, launches = bd.inst.get_kernel_timing(reset=True)
+        assert launches == 2, launches
+    finally:
+        bd.finalize()
+
+
+def test_gradient_launches_on_emulation(emu, monkeypatch):
+    check_gradient_launches(emu, monkeypatch)
+    check_gradient_launches(emu, monkeypatch, double_precision=True)
+
+
+@pytest.mark.gpu
+def test_gradient_launches(gpu, monkeypatch):
+    check_gradient_launches(gpu, monkeypatch)
+    check_gradient_launches(gpu, monkeypatch, double_precision=True)
 
 
 def test_launch_grouping_on_emulation(emu):
