@@ -508,6 +508,11 @@ BEAGLE_DLLEXPORT int mbamdSetRateMatrices(int instance, int firstEigenIndex, int
  * of reference UpDateCijk, src/likelihood.c:10476-10804: integration/mrbayes/mbamd_eigen_glue.c). */
 BEAGLE_DLLEXPORT int mbamdSetRateMatricesFrom(int instance, int firstEigenIndex, int count, const double* q, const double* pi, int mode,
                                               int warmFirstEigenIndex);
+/* The doubles of an eigen buffer read back (single-precision engine; waits for the instance's stream): outU, outUi S x S each,
+ * outLambda S values -- what the matrix kernels read, whoever wrote them.  outV (may be NULL): the S x S orthonormal eigenvectors of
+ * the symmetrised matrix that the device solver keeps for warm starts; BEAGLE_ERROR_OUT_OF_RANGE where the buffer was last written by
+ * beagleSetEigenDecomposition (it holds no such basis) and for an index out of range.  Made for tests of the solver's accuracy. */
+BEAGLE_DLLEXPORT int mbamdGetEigenDecomposition(int instance, int eigenIndex, double* outU, double* outUi, double* outLambda, double* outV);
 /* Last HIP/engine error text of the calling thread ("" if none). */
 BEAGLE_DLLEXPORT const char* mbamdGetLastError(void);
 /* Device-side timing of the partials kernels: accumulates HIP-event time (ms) and launch count of every

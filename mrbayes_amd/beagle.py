@@ -69,7 +69,7 @@ EXPORTS = [
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
     "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
-    "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom",
+    "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
     "beagleSetCategoryRatesWithIndex", "beagleUpdateTransitionMatricesWithMultipleModels", "beagleUpdatePartialsByPartition",
@@ -286,6 +286,16 @@ class BeagleInstance:
         self.lib.mbamdSetRateMatricesFrom.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int]
         self._chk(self.lib.mbamdSetRateMatricesFrom(self.id, first, n, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                                     (1 if exchangeabilities else 0) | (2 if shield else 0), warm_first), "mbamdSetRateMatricesFrom")
+
+    def get_eigen_decomposition(self, idx, basis=False):
+        """Extension: the doubles of an eigen buffer read back (mbamdGetEigenDecomposition): (U, U^-1, lambda), with basis=True also
+        V, the orthonormal eigenvectors the device solver keeps for warm starts (an error where the solver did not write the buffer)."""
+        S = self.state_count
+        U, Ui, lam, V = np.empty((S, S)), np.empty((S, S)), np.empty(S), np.empty((S, S)) if basis else None
+        self.lib.mbamdGetEigenDecomposition.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+        self._chk(self.lib.mbamdGetEigenDecomposition(self.id, idx, U.ctypes.data_as(_dp), Ui.ctypes.data_as(_dp), lam.ctypes.data_as(_dp),
+                                                      V.ctypes.data_as(_dp) if basis else None), "mbamdGetEigenDecomposition")
+        return (U, Ui, lam, V) if basis else (U, Ui, lam)
 
     def set_state_frequencies(self, idx, f):
         a = _d(f)

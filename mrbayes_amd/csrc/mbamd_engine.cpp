@@ -594,6 +594,20 @@ int mbamdSetRateMatricesFrom(int instance, int firstEigenIndex, int count, const
     if (!q || !pi) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdSetRateMatricesFrom: null");
     EACH_ENGINE(true, c->setRateMatrices(firstEigenIndex, count, q, pi, mode, warmFirstEigenIndex));
 }
+// extension: the doubles [U | U^-1 | lambda] of an eigen buffer read back, and the orthonormal basis V the device solver keeps beside
+// them (outV may be null).  Every child of a sharded or multi-partition handle is given the same systems: the first one answers.
+int mbamdGetEigenDecomposition(int instance, int eigenIndex, double* outU, double* outUi, double* outLambda, double* outV)
+{
+    GET_INSTANCE(instance);
+    if (h->f64) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "mbamdGetEigenDecomposition: not on a double-precision instance");
+    if (!outU || !outUi || !outLambda) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetEigenDecomposition: null");
+    if (in) return in->getEigen(eigenIndex, outU, outUi, outLambda, outV);
+    Instance* c = h->first();
+    if (!c) return fail(BEAGLE_ERROR_GENERAL, "mbamdGetEigenDecomposition: the instance has no engine");
+    (void) hipSetDevice(c->device);
+    if (c->hasWork()) { int frc = c->flushPending(); if (frc) return frc; }
+    return c->getEigen(eigenIndex, outU, outUi, outLambda, outV);
+}
 int beagleSetStateFrequencies(int instance, int idx, const double* f)
 {
     StatTimer st_(ST_SET);

@@ -151,6 +151,7 @@ struct Instance {
     int setPatternWeights(const double* w, int count) { return upload(d_pweights, w, sizeof(double) * count); }
     int setEigen(int idx, const double* U, const double* Ui, const double* lam);
     int setRateMatrices(int first, int count, const double* q, const double* pi, int mode, int warmFirst = -1);
+    int getEigen(int idx, double* U, double* Ui, double* lam, double* V);
     int setRates(int index, const double* r);
     // d1Idx / d2Idx: the matrix buffers that take dP/dt and d2P/dt2 of the same branches (either may be null)
     int updateMatrices(int eigenIndex, const int* probIdx, const double* lengths, int count, int rateSet = 0,
@@ -1169,6 +1170,24 @@ inline int Instance::setEigen(int idx, const double* U, const double* Ui, const 
             return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleSetEigenDecomposition: an imaginary part without its adjacent conjugate, or a non-finite eigenvalue");
     }
     return upload(d_eigen + (size_t) idx * eigenDoubles, h.data(), h.size() * sizeof(double));
+}
+
+// The doubles of an eigen buffer as the matrix kernels read them: [U | U^-1 | lambda]; V (optional) only where the device solver wrote
+// the buffer last -- after beagleSetEigenDecomposition the basis there belongs to no system.
+inline int Instance::getEigen(int idx, double* U, double* Ui, double* lam, double* V)
+{
+    if (idx < 0 || idx >= nEigen) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetEigenDecomposition: eigen index");
+    if (V && (eigenWarm.size() != (size_t) nEigen || eigenWarm[idx] < 0))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetEigenDecomposition: the device solver did not write this buffer, it holds no orthonormal basis");
+    const size_t SS = (size_t) S * S;
+    std::vector<double> h(2 * SS + S + (V ? SS : 0));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(h.data(), d_eigen + (size_t) idx * eigenDoubles, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(U, h.data(), SS * sizeof(double));
+    std::memcpy(Ui, h.data() + SS, SS * sizeof(double));
+    std::memcpy(lam, h.data() + 2 * SS, (size_t) S * sizeof(double));
+    if (V) std::memcpy(V, h.data() + 2 * SS + S, SS * sizeof(double));
+    return BEAGLE_SUCCESS;
 }
 
 // beagleUpdateTransitionMatrices only queues its jobs: MrBayes calls it once per eigen-system part (reference

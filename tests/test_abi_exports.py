@@ -21,7 +21,7 @@ def _declared():
 def test_headers_declare_the_expected_surface():
     names = _declared()
     for must in ("beagleCreateInstance", "beagleUpdatePartials", "beagleCalculateEdgeLogLikelihoods", "beagleGetSiteLogLikelihoods",
-                 "beagleUpdatePartialsByPartition", "beagleSetPatternPartitions", "mbamdSetRateMatrices",
+                 "beagleUpdatePartialsByPartition", "beagleSetPatternPartitions", "mbamdSetRateMatrices", "mbamdGetEigenDecomposition",
                  "mbamdParsCreateInstance", "mbamdParsDownPass", "mbamdParsFinalPass", "mbamdParsScore",
                  "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdGetStepTiming"):
         assert must in names, must
