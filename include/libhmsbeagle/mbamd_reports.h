@@ -76,6 +76,62 @@ BEAGLE_DLLEXPORT int mbamdCalculateNodePosteriors(int instance, const int* postB
  * a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).  The call is synchronous. */
 BEAGLE_DLLEXPORT int mbamdGetCategoryPosteriors(int instance, int categoryWeightsIndex, double* outPosteriors);
 
+/* One draw of ALL ancestral states from their JOINT posterior given the data, on the single- AND the double-precision engine: what
+ * a stochastic character map, a count of substitutions per branch, a posterior-predictive check or a data-augmentation move starts
+ * from.  (The posteriors above are marginal: the best states of two adjacent nodes can be jointly impossible.)  Only post-order
+ * buffers and transition matrices are read: no pre-order pass is needed.
+ *
+ * Slots.  Slot 0 is the TOP: the parent buffer of the latest beagleCalculate{Root,Edge}LogLikelihoods call.  Slot i + 1 is the
+ * lower end of edge i = 0 .. count-1, which hangs from slot parentSlots[i], 0 <= parentSlots[i] <= i (anything else:
+ * BEAGLE_ERROR_OUT_OF_RANGE) -- a parent is listed before its children by construction.  postBufferIndices[i] is the child's
+ * post-order partials or its compact tip states, matrixIndices[i] the transition matrix of its branch.  Where the latest
+ * log-likelihood call was an edge call, its child (MrBayes' root tip) may be listed as an ordinary edge from slot 0 with that call's
+ * matrix.  Edges are launched in groups of consecutive edges whose parent slots all lie before the group's first slot (at most
+ * 32768 each): a breadth-first list costs one launch per level of the tree, a depth-first list up to one per edge; the draw is the
+ * same.
+ *
+ * Distribution.  Per pattern c, with k* the drawn category:
+ *     P(k)                    = q_k(c)                                   the doubles mbamdGetCategoryPosteriors returns; one
+ *                                                                        category: k* = 0 and nothing is drawn
+ *     P(a at the top | k)     ~ freqs[a] * parent[k,c,a] * f_k(a)        f_k(a) = sum_j P_k[a,j] child[k,c,j], the factor of the
+ *                                                                        log-likelihood call's child across its matrix (a root
+ *                                                                        call: f = 1); freqs: that call's state frequencies
+ *     P(b at a child | a, k)  ~ P_k[a,b] * post_child[k,c,b]             a = the state drawn at its parent slot
+ * A compact tip contributes its indicator: exactly one compatible state is that state, WITHOUT arithmetic; a missing state leaves
+ * the row P_k[a,.]; four-state bitplanes leave the compatible columns.
+ *
+ * Arithmetic.  Each weight is ONE product in the engine's precision (the top's: (parent * f) in the engine's precision, f an
+ * ascending FMA chain, times freqs[a] in double), widened to double; sums are in double, in ascending state order.
+ *
+ * Selection rule.  With the weights v_0 .. v_{n-1} and T their ascending sum: unless T > 0 the answer is -1.  Otherwise x = u * T
+ * and the answer is the smallest index with x < v_0 + ... + v_index (the same running sum); if rounding leaves none, the largest
+ * index of positive weight.  A state of weight 0 is never chosen.  A slot whose parent slot holds -1, and every slot of a pattern
+ * whose category is -1, is -1.
+ *
+ * Uniforms: counter-based, so that a client can reproduce a draw.  All arithmetic mod 2^64:
+ *     mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     G = 0x9E3779B97F4A7C15
+ *     u(seed, stream, c) = (mix(mix(seed + G * (stream + 1)) + G * (c + 1)) >> 11) * 2^-53
+ * Stream 0 draws the category, stream 1 the top, stream 2 + i edge i; c is the pattern's index IN THE INSTANCE: a pattern-sharded
+ * instance returns the draw of an unsharded one.
+ *
+ * Outputs.
+ *     outStates[slot * patternCount + c]     count + 1 rows; never NULL
+ *     outCategories[c]                       k* (or NULL)
+ *     outChangeCounts[i] = sum_c weight_c [state(child) != state(parent), both >= 0]      the sampled number of substitutions on
+ *                                            branch i (or NULL); reduced on the device in a fixed order, summed over pattern
+ *                                            shards in pattern order
+ *
+ * Refusals.  Not on a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).  No log-likelihood call yet is
+ * BEAGLE_ERROR_GENERAL -- with one category too: the top's frequencies come from it --, one with count > 1
+ * BEAGLE_ERROR_NO_IMPLEMENTATION; categoryWeightsIndex must be that call's weights index, every post buffer readable, every matrix
+ * index in range, no index array NULL with count > 0, outStates not NULL (BEAGLE_ERROR_OUT_OF_RANGE each).  A refused call writes
+ * nothing.  count == 0 is legal and samples the top alone.  The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdSampleAncestralStates(int instance, const int* parentSlots, const int* postBufferIndices,
+                                                const int* matrixIndices, int count, int categoryWeightsIndex,
+                                                unsigned long long seed, int* outStates, int* outCategories,
+                                                double* outChangeCounts);
+
 #ifdef __cplusplus
 }
 #endif

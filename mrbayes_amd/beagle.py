@@ -67,7 +67,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
-    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -160,6 +160,7 @@ class BeagleLibrary:
         L.mbamdGetSecondDerivativeLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdCalculateNodePosteriors.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, _dp, _ip, _dp, _dp]
         L.mbamdGetCategoryPosteriors.argtypes = [C.c_int, C.c_int, _dp]
+        L.mbamdSampleAncestralStates.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, C.c_int, C.c_ulonglong, _ip, _ip, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -504,6 +505,24 @@ class BeagleInstance:
         q = np.empty((self.category_count, self.pattern_count))
         self._chk(self.lib.mbamdGetCategoryPosteriors(self.id, weights_index, q.ctypes.data_as(_dp)), "mbamdGetCategoryPosteriors")
         return q
+
+    def sample_ancestral_states(self, parent_slots, posts, matrices, weights_index, seed, categories=False, changes=False):
+        """One draw of all ancestral states from their joint posterior (mbamdSampleAncestralStates): slot 0 is the parent buffer of the
+        latest log-likelihood call, slot i + 1 the lower end of edge i, which hangs from slot parent_slots[i] <= i.  Returns (rc,
+        states [count + 1][patterns] with -1 where nothing could be drawn, categories [patterns] or None, sampled changes per edge
+        [count] or None); an error code raises."""
+        ps, po, m = _i(parent_slots), _i(posts), _i(matrices)
+        n, P = len(ps), self.pattern_count
+        if not len(po) == len(m) == n:
+            raise ValueError("sample_ancestral_states: the three index lists differ in length")
+        states = np.empty((n + 1, P), dtype=np.int32)
+        cats = np.empty(P, dtype=np.int32) if categories else None
+        counts = np.empty(n) if changes else None
+        rc = self.lib.mbamdSampleAncestralStates(self.id, ps.ctypes.data_as(_ip), po.ctypes.data_as(_ip), m.ctypes.data_as(_ip), n, weights_index,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, states.ctypes.data_as(_ip), _ptr(cats),
+                                                 counts.ctypes.data_as(_dp) if changes else None)
+        self._chk(rc, "mbamdSampleAncestralStates")
+        return rc, states, cats, counts
 
     def calculate_cross_products(self, posts, pres, rates, weights, edge_lengths, squared=False):
         """The cross-product matrix of the gradient in the rate matrix over every listed branch in one call

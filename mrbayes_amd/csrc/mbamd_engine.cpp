@@ -1144,6 +1144,37 @@ int mbamdGetCategoryPosteriors(int instance, int categoryWeightsIndex, double* o
     EACH_ENGINE(true, c->categoryPosteriors(categoryWeightsIndex, outPosteriors + ch.start, (size_t) h->dim.patternCount));
 }
 
+// one draw of all ancestral states from their joint posterior (mbamd_ancestral_sampling.h; semantics: mbamd_reports.h)
+int mbamdSampleAncestralStates(int instance, const int* parentSlots, const int* postBufferIndices, const int* matrixIndices, int count,
+                               int categoryWeightsIndex, unsigned long long seed, int* outStates, int* outCategories, double* outChangeCounts)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdSampleAncestralStates(count=%d, seed=%llu%s%s)", count, seed, outCategories ? ", categories" : "", outChangeCounts ? ", changes" : "");
+    const char* const who = "mbamdSampleAncestralStates";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!parentSlots || !postBufferIndices || !matrixIndices))) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    if (!outStates) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "outStates is null");
+    const size_t stride = (size_t) h->dim.patternCount;
+    std::vector<double> sum;
+    if (h->f64) {
+        sum.assign((size_t) count, 0.0);
+        const int rc = h->f64->sampleAncestralStates(parentSlots, postBufferIndices, matrixIndices, count, categoryWeightsIndex, seed, 0, outStates,
+                                                     outCategories, sum.data(), stride);
+        if (rc) return rc;
+    } else {
+        // pattern shards: the uniforms are those of the pattern's index in the instance, the children's states and categories are
+        // concatenated, their change counts added (in pattern order)
+        const int rc = each_engine_sum(h, (size_t) count, sum, [&](Instance* c, const Handle::Span& ch, double* part) {
+            return c->sampleAncestralStates(parentSlots, postBufferIndices, matrixIndices, count, categoryWeightsIndex, seed, (long long) ch.start,
+                                            outStates + ch.start, outCategories ? outCategories + ch.start : nullptr, part, stride);
+        });
+        if (rc) return rc;
+    }
+    if (outChangeCounts) std::copy(sum.begin(), sum.end(), outChangeCounts);
+    return BEAGLE_SUCCESS;
+}
+
 // the cross-product matrix of the gradient in the rate matrix (mbamd_crossproducts.h; semantics: beagle.h)
 int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryRateIndices,
                                           const int* categoryWeightsIndices, const double* edgeLengths, int count, double* outSumDerivatives,

@@ -19,6 +19,7 @@
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
+#include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges: a draw of all ancestral states from their joint posterior
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
 
 namespace mbamd {
@@ -201,6 +202,10 @@ struct Instance {
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
                        size_t siteStride, double* sums);
     int categoryPosteriors(int wIdx, double* out, size_t stride);
+    // sampleAncestralStates (mbamdSampleAncestralStates on this engine's patterns; mbamd_ancestral_sampling.h): synchronous;
+    // patternOffset = the index in the instance of this engine's pattern 0, states at [slot * stride + c], changes[i] never null
+    int sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
+                              long long patternOffset, int* states, int* categories, double* changes, size_t stride);
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -369,6 +374,7 @@ private:
     template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
+    template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued or held runs first
@@ -424,6 +430,16 @@ private:
     void afterSync() { syncedClock = launchClock; }
     // launches for kernelTiming to report
     void countLaunches(int n) { pendingLaunches += n; }
+    // ... and, while timing is on, an event pair around the launches of a call (no span: such a call is no evaluation)
+    int timedBegin(hipEvent_t& ev0, hipEvent_t& ev1)
+    {
+        if (!timing) return BEAGLE_SUCCESS;
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, stream));
+        return BEAGLE_SUCCESS;
+    }
+    int timedEnd(hipEvent_t ev0, hipEvent_t ev1) { return launchesEnd(ev0, ev1); }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
@@ -3558,6 +3574,11 @@ inline int Instance::nodePosteriors(const int* post, const int* pre, const int* 
     return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, siteStride, sums);
 }
 inline int Instance::categoryPosteriors(int wIdx, double* out, size_t stride) { return category_posteriors(*this, wIdx, out, stride); }
+inline int Instance::sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
+                                           long long patternOffset, int* states, int* categories, double* changes, size_t stride)
+{
+    return sample_ancestral_states(*this, parentSlots, post, matrices, count, wIdx, seed, patternOffset, states, categories, changes, stride);
+}
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked and in memory, and room for q
 inline int Instance::posteriorOperands(DerivArgs& a)
 {

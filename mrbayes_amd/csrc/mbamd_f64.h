@@ -31,6 +31,7 @@
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout <DERIV_F64, double, 1 and 2>: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors <DERIV_F64, double>: node-state and category posteriors from the pre-order buffers
+#include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges <DERIV_F64, double>: a draw of all ancestral states from their joint posterior
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
 
 namespace mbamd {
@@ -96,6 +97,9 @@ public:
     // node-state and category posteriors (mbamd_posteriors.h), as on the single-precision engine: synchronous
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues, double* sums);
     int categoryPosteriors(int wIdx, double* out);
+    // a draw of all ancestral states from their joint posterior (mbamd_ancestral_sampling.h), as on the single-precision engine: synchronous
+    int sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
+                              long long patternOffset, int* states, int* categories, double* changes, size_t stride);
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -171,6 +175,7 @@ private:
     template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
+    template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued runs first
@@ -204,6 +209,9 @@ private:
     void afterSync() {}
     // launches for kernelTiming to report
     void countLaunches(int n) { preLaunches += (uint64_t) n; }
+    // (no device timing on this engine)
+    int timedBegin(hipEvent_t&, hipEvent_t&) { return BEAGLE_SUCCESS; }
+    int timedEnd(hipEvent_t, hipEvent_t) { return BEAGLE_SUCCESS; }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     // f(this engine's layout as a compile-time constant)
     template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }
@@ -1315,6 +1323,11 @@ inline int Engine64::nodePosteriors(const int* post, const int* pre, const int* 
     return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, (size_t) P, sums);
 }
 inline int Engine64::categoryPosteriors(int wIdx, double* out) { return category_posteriors(*this, wIdx, out, (size_t) P); }
+inline int Engine64::sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
+                                           long long patternOffset, int* states, int* categories, double* changes, size_t stride)
+{
+    return sample_ancestral_states(*this, parentSlots, post, matrices, count, wIdx, seed, patternOffset, states, categories, changes, stride);
+}
 // what ensure_posteriors asks for: the latest log-likelihood call's operands, checked, and room for q
 inline int Engine64::posteriorOperands(DerivArgs& a)
 {

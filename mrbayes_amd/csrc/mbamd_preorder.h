@@ -430,6 +430,7 @@ k_edge_second_mfma(ReadoutArgs a)
 //     beforeRead, beforeWrite, afterWrite around the partials buffers of a call
 //     stageTable, resultScratch           device memory for the call's table and for its results
 //     afterSync, countLaunches            bookkeeping
+//     timedBegin, timedEnd                an event pair around a call's launches while kernel timing is on (the sampling call)
 //     withLayout                          f(layout as a compile-time constant)
 //     posteriorOperands                   the checked operands of the latest log-likelihood call
 

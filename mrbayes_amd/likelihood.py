@@ -527,6 +527,45 @@ class BeagleDivision:
         (q * cat_rates[:, None]).sum(0)."""
         return self.inst.get_category_posteriors(self.cijkIndex[chain])
 
+    def AncestralSamplingEdges(self, chain=0):
+        """The breadth-first edge list of the chain's current tree as sample_ancestral_states takes it -- (nodes, parent slots,
+        post-order buffers, matrices): nodes[0] = the top interior node is slot 0, nodes[i + 1] the lower end of edge i.  The root
+        tip hangs from the top across the top's own matrix (the branch the log-likelihood call integrates); level by level, so
+        that the engine needs one launch per level."""
+        t = self.div.tree
+        top = t.root_left
+        nodes, parents = [top, t.root], [0]
+        mats = [self.tiProbsIndex[chain][top]]
+        level = [(top, 0)]
+        while level:
+            below = []
+            for p, slot in level:
+                for n in (t.left[p], t.right[p]):
+                    parents.append(slot)
+                    mats.append(self.tiProbsIndex[chain][n])
+                    nodes.append(n)
+                    if t.left[n] >= 0:
+                        below.append((n, len(nodes) - 1))
+            level = below
+        return nodes, parents, [self.condLikeIndex[chain][n] for n in nodes[1:]], mats
+
+    def SampleAncestralStates(self, chain=0, seed=0, categories=False, changes=False):
+        """{node: sampled states [patterns]} for every node of the chain's current tree (the root tip included), ONE draw from the
+        joint posterior of all ancestral states after LogLike; no pre-order pass.  categories=True adds the sampled categories
+        [patterns], changes=True {node: sampled number of substitutions on the branch above it} (the root tip: on the root branch):
+        the return value is the tuple of what was asked for, the states first."""
+        if self.step != 1:
+            raise NotImplementedError("SampleAncestralStates: one eigen-system part per division")
+        nodes, parents, posts, mats = self.AncestralSamplingEdges(chain)
+        rc, states, cats, counts = self.inst.sample_ancestral_states(parents, posts, mats, self.cijkIndex[chain], seed,
+                                                                     categories=categories, changes=changes)
+        out = [{n: states[i] for i, n in enumerate(nodes)}]
+        if categories:
+            out.append(cats)
+        if changes:
+            out.append({n: float(counts[i]) for i, n in enumerate(nodes[1:])})
+        return out[0] if len(out) == 1 else tuple(out)
+
     def RateMatrixCrossProducts(self, chain=0):
         """X [S][S], the cross-product matrix of the gradient in the rate matrix, for the chain's current tree after LogLike: the same
         steps as BranchGradient (start vector, pre-order list of the whole tree), then ONE calculate_cross_products call over all
