@@ -1,6 +1,7 @@
 // mbamd_f32.h -- the single-precision engine of one device: `Instance` (arenas, stream, plan cache, schedulers) with the compiled
-// operation lists it runs (`Plan`, `PathStep`), its launch helpers, and new_engine(), the only place one is made.  Included by
-// mbamd_engine.cpp, whose C ABI reaches an engine through the public part of `Instance` and nothing else.
+// operation lists it runs (`Plan`, `PathStep`), its launch helpers, and new_engine(), the only place one is made.  Its scale
+// buffers belong to a `ScaleStore` (mbamd_scale_store.h).  Included by mbamd_engine.cpp, whose C ABI reaches an engine through
+// the public part of `Instance` and nothing else.
 #ifndef MBAMD_F32_H_
 #define MBAMD_F32_H_
 
@@ -11,6 +12,7 @@
 
 #include "mbamd_host.h"          // the HIP runtime, beagle.h, the switches, <algorithm> ... <vector>; diagnostics and the host runtime the engines share
 #include "mbamd_kernels.h"
+#include "mbamd_scale_store.h"   // ScaleStore: the scale buffers, whichever form holds them, and the kernels that move them between forms
 #include "mbamd_reports.h"
 #include "libhmsbeagle/mbamd_reports.h"
 #include "mbamd_walk4_host.h"
@@ -165,7 +167,7 @@ struct Instance {
     int setMatrices(const int* idx, const double* in, int count);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
     int flushPending(bool keepPath = false);
-    // scale buffers, whichever of their forms holds them (scaleState 0 / 1 / 2 in the arenas, an int32 buffer on the level kernels)
+    // scale buffers, whichever of their forms holds them (ScaleStore): the range checks and the scheduling around the store's calls
     int resetScale(int idx, bool mayWait = false);
     int copyScale(int dst, int src);
     int accumulateScale(const int* idx, int n, int cumIdx, int sign, bool afterReset = false);
@@ -242,10 +244,6 @@ private:
     std::vector<int> w4key, w4writer, w4segList;                    // buildWalk scratch: no allocation per compiled list
     std::vector<char> w4written, w4segRead, w4segWritten, w4segScale;
     std::vector<Walk4Entry> w4table;
-    int8_t* arenaExp = nullptr;      // node exponents int8 [block][scale buffer][K][64] (+ one scratch buffer)
-    unsigned estride = 0;            // bytes between blocks
-    std::vector<int32_t*> wideScale; // cumulative exponents int32 [K][Ppad], allocated on first use
-    std::vector<char> scaleState;    // 0 = never written (zero), 1 = node exponents in the arena, 2 = cumulative (wide)
     int lastWalkW = 0, lastWalkSlots = 0, lastWalkEntries = 0, lastWalkPhases = 0, lastWalkCrossing = 0;
     bool walkCumFresh = false;       // the cumulative buffer of the list being submitted holds nothing yet (store, do not add)
     // ---- small subtrees a whole-tree launch did not store (MBAMD_W4_NOSTORE, mbamd_walk4.h).  Such a buffer stays `valid`: it carries a RECIPE
@@ -313,7 +311,7 @@ private:
     bool buildPathG(Plan& plan, const BeagleOperation* ops, int n, const std::vector<int>& starts, int nl);
     Walk4Args walk4Args() const;
     WalkGArgs walkGArgs() const;
-    int prepareCumulative(int idx, bool& fresh);
+    void listLaunched(const BeagleOperation* ops, int n, bool path, bool forked);
     void postResultFlag();
     bool scaleOpsIndependentOfPending(const int* idx, int n, int cumIdx) const;
     uint64_t launchClock = 0, syncedClock = 0;   // launches issued / launches known complete (last stream synchronisation)
@@ -327,8 +325,8 @@ private:
 
     std::vector<float*> partials;      // general path: allocated on first use; 4-state path: slices of the arena
     std::vector<uint8_t*> tipStates;   // non-null while the buffer holds compact tip states
-    std::vector<int32_t*> scale;
-    std::vector<char> valid;           // partials buffer has been written (import or operation destination)
+    ScaleStore scales;                 // the scale buffers (mbamd_scale_store.h)
+    std::vector<char> valid;          // partials buffer has been written (import or operation destination)
     // 4-state path: arenas (see mbamd_kernels.h: partials buffer-major, tips and exponents block-major), one allocation each
     float* arenaPartials = nullptr;
     uint64_t* arenaTips = nullptr;     // state bitplanes uint64 [block][buffer][4]
@@ -400,10 +398,21 @@ private:
     // (nothing to refuse: an engine of this kind holds one partition, and the C ABI turns a partitioned instance away itself)
     int refuses(const char*) const { return BEAGLE_SUCCESS; }
     // the buffer holds compact tip states / something a kernel can read (an unstored buffer is `valid`: beforeRead)
-    bool holdsTip(int b) const { return tipStates[b] != nullptr; }
+    bool holdsTip(int b) const { return operand(b).kind == CHILD_STATES; }
     bool readable(int b) const { return tipStates[b] || valid[b]; }
-    // the buffer as an operand: its tip states or its partials
-    const void* operandPtr(int b) const { return tipStates[b] ? (const void*) tipStates[b] : (const void*) partials[b]; }
+    // the buffer as an operand: its tip states or its partials (asPartials: partials whatever it holds now -- the list being compiled writes them)
+    struct Operand { const void* ptr; ChildKind kind; };
+    Operand operand(int b, bool asPartials = false) const { return tipStates[b] && !asPartials ? Operand{tipStates[b], CHILD_STATES} : Operand{partials[b], CHILD_PARTIALS}; }
+    const void* operandPtr(int b) const { return operand(b).ptr; }
+    // where an integration puts its per-pattern values: pinned host memory once a client has asked for them (getSites), else the device
+    double* siteTarget() { siteOnHost = siteToHost && h_site_dev; return siteOnHost ? h_site_dev : d_site; }
+    // the layout's strides as the kernels take them: partials (s4: f4 between blocks; wg: floats between tiles; level kernels: linear buffers)
+    // and compact tips (s4: uint64 between the blocks of the bitplanes; wg: bytes between tiles; level kernels: none)
+    struct Strides { size_t partials, tips; };
+    Strides strides() const
+    {
+        return s4 ? Strides{geom.pstride, geom.tstride} : wg ? Strides{wgTileBytes / 4, wgTipTileBytes} : Strides{geom.pstride, 0};
+    }
     float* partialsPtr(int b) const { return partials[b]; }
     // the buffers buf(0 .. n) that a call reads are in memory (those below zero: none)
     template <class F> int beforeRead(int n, F buf)
@@ -584,15 +593,7 @@ private:
 
     // small kernel inputs (job lists, pointer lists): placed in the pinned ring and read by the kernel
     // directly over the host link -- no copy engine, no extra stream operation
-    int stageDirect(const void* src, size_t bytes, const void** devPtr)
-    {
-        if (((bytes + 63) & ~(size_t) 63) > stage.capacity() / 2) return fail(BEAGLE_ERROR_OUT_OF_MEMORY, "staging ring too small");
-        size_t off = 0;
-        int rc = stage.put(src, bytes, stream, &off);
-        if (rc) return rc;
-        *devPtr = stage.dev(off);
-        return BEAGLE_SUCCESS;
-    }
+    int stageDirect(const void* src, size_t bytes, const void** devPtr) { return stage.putDirect(src, bytes, stream, devPtr); }
 
     int ensurePartials(int idx)
     {
@@ -602,16 +603,6 @@ private:
         HIP_TRY(hipMalloc(&p, partialsFloats * sizeof(float)));
         HIP_TRY(hipMemsetAsync(p, 0, partialsFloats * sizeof(float), stream));
         partials[idx] = p;
-        return BEAGLE_SUCCESS;
-    }
-    int ensureScale(int idx)
-    {
-        if (scale[idx]) return BEAGLE_SUCCESS;
-        if (arena()) return fail(BEAGLE_ERROR_GENERAL, "exponent arena not initialised");
-        int32_t* p = nullptr;
-        HIP_TRY(hipMalloc(&p, (size_t) Ppad * sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(p, 0, (size_t) Ppad * sizeof(int32_t), stream));
-        scale[idx] = p;
         return BEAGLE_SUCCESS;
     }
     float* matrixPtr(int idx) const { return matrices + (size_t) idx * matrixFloats; }
@@ -625,10 +616,26 @@ private:
     std::vector<char> eigenShield;   // per eigen buffer: the next beagleSetEigenDecomposition is ignored (mbamdSetRateMatricesFrom, mode bit 1)
     int updatePartials4(const BeagleOperation* ops, int n, int cumIdx);
     int buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int* listOf = nullptr, bool perList = false);
-    int ensureWide(int idx);
-    int accumulate4(const int* idx, int n, int cumIdx, int sign);
     int deferredReset = -1;          // a reset that waits for the call after it (resetScale, accumulateScale), or -1
     int checkIntegrate(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx, int count);
+    // the (checked) operands of a log-likelihood call in device pointers: A = IntegrateArgs (level kernels) or IntegrateArgs4 (arenas)
+    template <class A> int integrateOperands(A& a, const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx, const int* cumIdx, int count)
+    {
+        std::memset(&a, 0, sizeof a);
+        a.count = count;
+        for (int n = 0; n < count; ++n) {
+            a.parent[n] = reinterpret_cast<std::decay_t<decltype(a.parent[n])>>(partials[parent[n]]);      // (const float* / const f4*)
+            if (child) {
+                const Operand c = operand(child[n]);
+                a.child[n] = c.ptr; a.child_kind[n] = c.kind;
+                a.matrix[n] = matrixPtr(prob[n]);
+            }
+            a.weights[n] = d_weights + (size_t) wIdx[n] * K;
+            a.freqs[n] = d_freqs + (size_t) fIdx[n] * S;
+            if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE) { int rc = scales.cumulativeForRead(cumIdx[n], a.cum[n]); if (rc) return rc; }
+        }
+        return BEAGLE_SUCCESS;
+    }
     int integrate4(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
                    const int* cumIdx, int count);
     int integrateLevels(const int* parent, const int* child, const int* prob, const int* wIdx, const int* fIdx,
@@ -745,7 +752,6 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
     eigenDoubles = eigen_imag_offset(S) + (size_t) 2 * S;
     partials.assign(nBuffers, nullptr);
     tipStates.assign(nBuffers, nullptr);
-    scale.assign(std::max(nScale, 1), nullptr);
     valid.assign(nBuffers, 0);
     if (s4) {
         // everything up front, like the reference's InitChainCondLikes (src/mcmc.c:5756-5834): one arena per kind.  Partials
@@ -758,47 +764,37 @@ inline int Instance::create(const Dims& dim, int patternCount, int dev, const Sw
         geom.pstride = (unsigned long) K * 64;
         geom.tstride = (unsigned) nBuffers * 4;
         geom.sstride = 64;
-        estride = (unsigned) (scale.size() + MBAMD_W4_SCRATCH_ROWS) * K * 64;       // + the scratch rows (sinks of operations that record no exponents, in rotation)
-        const size_t pBytes = nb * (size_t) nBuffers * K * 64 * 16, tBytes = nb * geom.tstride * 8, eBytes = nb * (size_t) estride;
+        const size_t pBytes = nb * (size_t) nBuffers * K * 64 * 16, tBytes = nb * geom.tstride * 8;
         HIP_TRY(hipMalloc(&arenaPartials, pBytes));
         HIP_TRY(hipMalloc(&arenaTips, tBytes));
-        HIP_TRY(hipMalloc(&arenaExp, eBytes));
         HIP_TRY(hipMemsetAsync(arenaPartials, 0, pBytes, stream));
         HIP_TRY(hipMemsetAsync(arenaTips, 0xFF, tBytes, stream));            // (a tip never set = all states compatible)
-        HIP_TRY(hipMemsetAsync(arenaExp, 0, eBytes, stream));
-        wideScale.assign(scale.size(), nullptr);
-        scaleState.assign(scale.size(), 0);
         unstored.assign((size_t) nBuffers, 0);
         recipes.assign((size_t) nBuffers, Recipe());
         if (sw.verbose)
-            std::fprintf(stderr, "[mbamd] arenas: partials %p +%zu, tips %p +%zu, exponents %p +%zu\n",
-                         (void*) arenaPartials, pBytes, (void*) arenaTips, tBytes, (void*) arenaExp, eBytes);
+            std::fprintf(stderr, "[mbamd] arenas: partials %p +%zu, tips %p +%zu\n", (void*) arenaPartials, pBytes, (void*) arenaTips, tBytes);
         for (int i = 0; i < nBuffers; ++i) partials[i] = arenaPartials + (size_t) i * nb * K * 64 * 4;
     }
     if (wg) {
         // the same for the 20/61-state tree walk (mbamd_walkg.h): tile-major arenas, one extra partials buffer per tile as
         // the sink of NOP entries; exponents in the 4-state path's format (two tiles per 64-pattern block)
-        const size_t nt = (size_t) Ppad / MBAMD_WG_TW, nb = (size_t) Ppad / 64, tb = wg_block_bytes(S);
+        const size_t nt = (size_t) Ppad / MBAMD_WG_TW, tb = wg_block_bytes(S);
         wgTileBytes = (unsigned long) (nBuffers + 1) * K * tb;
         wgTipTileBytes = (unsigned) nBuffers * MBAMD_WG_TW;
-        // (+ the scratch rows: sinks of entries that do not record exponents.  The general-state kernels store an exponent byte with every
-        //  entry -- a conditional store would make the compiler's counted waits stricter -- and every entry of a SCALE_READ evaluation
-        //  storing to ONE row made such an evaluation 29 % slower at 20 states (same-address stores, profiles/r06_scale_read.txt): the
-        //  entries of a program rotate over MBAMD_WG_SCRATCH_ROWS rows)
-        estride = (unsigned) (scale.size() + MBAMD_WG_SCRATCH_ROWS) * K * 64;
-        const size_t pBytes = nt * wgTileBytes, tBytes = nt * wgTipTileBytes, eBytes = nb * (size_t) estride;
+        const size_t pBytes = nt * wgTileBytes, tBytes = nt * wgTipTileBytes;
         HIP_TRY(hipMalloc(&arenaPartials, pBytes));
         HIP_TRY(hipMalloc(&arenaTipStates, tBytes));
-        HIP_TRY(hipMalloc(&arenaExp, eBytes));
         HIP_TRY(hipMemsetAsync(arenaPartials, 0, pBytes, stream));
         HIP_TRY(hipMemsetAsync(arenaTipStates, S, tBytes, stream));           // (a tip never set = missing data)
-        HIP_TRY(hipMemsetAsync(arenaExp, 0, eBytes, stream));
-        wideScale.assign(scale.size(), nullptr);
-        scaleState.assign(scale.size(), 0);
         if (sw.verbose)
-            std::fprintf(stderr, "[mbamd] arenas: partials +%zu, tips +%zu, exponents +%zu bytes\n", pBytes, tBytes, eBytes);
+            std::fprintf(stderr, "[mbamd] arenas: partials +%zu, tips +%zu bytes\n", pBytes, tBytes);
         for (int i = 0; i < nBuffers; ++i) partials[i] = arenaPartials + (size_t) i * K * tb / 4;
     }
+    // The scale buffers; arena layouts: their exponent arena, zeroed behind the other two, with scratch rows behind the buffers of a block:
+    // sinks of entries that record no exponents, in rotation (an exponent byte is stored with every entry -- a conditional store would make the
+    // compiler's counted waits stricter -- and all of them storing to ONE row cost a SCALE_READ evaluation 29 % at 20 states, profiles/r06_scale_read.txt)
+    { int rc = scales.create(stream, &stage, K, Ppad, std::max(nScale, 1), s4 ? MBAMD_W4_SCRATCH_ROWS : MBAMD_WG_SCRATCH_ROWS, arena()); if (rc) return rc; }
+    if (arena() && sw.verbose) std::fprintf(stderr, "[mbamd] arenas: exponents %p +%zu\n", (void*) scales.nodeExponents(), (size_t) Ppad / 64 * scales.blockStride());
 
     HIP_TRY(hipMalloc(&matrices, std::max<size_t>(1, (size_t) nMatrices * matrixFloats) * sizeof(float)));
     HIP_TRY(hipMemsetAsync(matrices, 0, std::max<size_t>(1, (size_t) nMatrices * matrixFloats) * sizeof(float), stream));
@@ -841,13 +837,11 @@ inline Instance::~Instance()
     (void) hipSetDevice(device);
     (void) hipStreamSynchronize(stream);
     if (arena()) {
-        void* arenas[] = {arenaPartials, arenaTips, arenaTipStates, arenaExp};
+        void* arenas[] = {arenaPartials, arenaTips, arenaTipStates};
         for (void* a : arenas) if (a) (void) hipFree(a);
-        for (int32_t* w : wideScale) if (w) (void) hipFree(w);
     } else {
         for (float* p : partials) if (p) (void) hipFree(p);
         for (uint8_t* p : tipStates) if (p) (void) hipFree(p);
-        for (int32_t* p : scale) if (p) (void) hipFree(p);
     }
     pending.clear();
     wgOps.clear(); wgListStart.clear(); wgListCum.clear();
@@ -1063,9 +1057,7 @@ inline int Instance::importPartials(int idx, const double* in, bool hasCategorie
     HIP_TRY(hipMemcpy(d_tmp, in, nIn * sizeof(double), hipMemcpyHostToDevice));
     const size_t total = (size_t) K * P * S;
     const unsigned blocks = (unsigned) ((total + 255) / 256);
-    if (s4) MBAMD_LAUNCH(k_import_partials<1>, blocks, 256, 0, stream, (const double*) d_tmp, hasCategories ? 1 : 0, S, K, P, Ppad, (size_t) geom.pstride, partials[idx]);
-    else if (wg) MBAMD_LAUNCH(k_import_partials<2>, blocks, 256, 0, stream, (const double*) d_tmp, hasCategories ? 1 : 0, S, K, P, Ppad, (size_t) (wgTileBytes / 4), partials[idx]);
-    else    MBAMD_LAUNCH(k_import_partials<0>, blocks, 256, 0, stream, (const double*) d_tmp, hasCategories ? 1 : 0, S, K, P, Ppad, (size_t) geom.pstride, partials[idx]);
+    withLayout([&](auto tag) { MBAMD_LAUNCH(k_import_partials<decltype(tag)::value>, blocks, 256, 0, stream, (const double*) d_tmp, hasCategories ? 1 : 0, S, K, P, Ppad, strides().partials, partials[idx]); });
     HIP_TRY(hipGetLastError());
     valid[idx] = 1;
     if (tipStates[idx]) {                        // a tip switches from compact to partials form
@@ -1086,9 +1078,7 @@ inline int Instance::getPartials(int idx, double* out)
     rc = ensureStored(idx);
     if (rc) return rc;
     const unsigned blocks = (unsigned) ((total + 255) / 256);
-    if (s4) MBAMD_LAUNCH(k_export_partials<1>, blocks, 256, 0, stream, (const float*) partials[idx], S, K, P, Ppad, (size_t) geom.pstride, (double*) d_tmp);
-    else if (wg) MBAMD_LAUNCH(k_export_partials<2>, blocks, 256, 0, stream, (const float*) partials[idx], S, K, P, Ppad, (size_t) (wgTileBytes / 4), (double*) d_tmp);
-    else    MBAMD_LAUNCH(k_export_partials<0>, blocks, 256, 0, stream, (const float*) partials[idx], S, K, P, Ppad, (size_t) geom.pstride, (double*) d_tmp);
+    withLayout([&](auto tag) { MBAMD_LAUNCH(k_export_partials<decltype(tag)::value>, blocks, 256, 0, stream, (const float*) partials[idx], S, K, P, Ppad, strides().partials, (double*) d_tmp); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipMemcpy(out, d_tmp, total * sizeof(double), hipMemcpyDeviceToHost));
@@ -1475,11 +1465,7 @@ inline int Instance::updatePartials(const BeagleOperation* ops, int n, int cumId
     if (s4) return updatePartials4(ops, n, cumIdx);
     if (wg) return updatePartialsG(ops, n, cumIdx);
     int32_t* cumPtr = nullptr;
-    if (cumIdx != BEAGLE_OP_NONE) {
-        int rc = ensureScale(cumIdx);
-        if (rc) return rc;
-        cumPtr = scale[cumIdx];
-    }
+    if (cumIdx != BEAGLE_OP_NONE) { bool fresh; int rc = scales.cumulativeForAdd(cumIdx, cumPtr, fresh); if (rc) return rc; }
     bool build;
     Plan* plan = cachedPlan(reinterpret_cast<const int*>(ops), (size_t) n * 7, build);
     if (!build) return submit(plan, cumIdx, cumPtr);
@@ -1502,20 +1488,17 @@ inline int Instance::updatePartials(const BeagleOperation* ops, int n, int cumId
             rc = ensurePartials(b.destinationPartials);
             if (rc) return rc;
             d.dst = partials[b.destinationPartials];
-            const bool tip1 = tipStates[b.child1Partials] && !written[b.child1Partials], tip2 = tipStates[b.child2Partials] && !written[b.child2Partials];
-            d.c1 = tip1 ? (const void*) tipStates[b.child1Partials] : partials[b.child1Partials];
-            d.c2 = tip2 ? (const void*) tipStates[b.child2Partials] : partials[b.child2Partials];
-            d.c1_kind = tip1 ? CHILD_STATES : CHILD_PARTIALS;
-            d.c2_kind = tip2 ? CHILD_STATES : CHILD_PARTIALS;
+            // (a buffer the list itself wrote is partials even if it held tip states)
+            const Operand c1 = operand(b.child1Partials, written[b.child1Partials]), c2 = operand(b.child2Partials, written[b.child2Partials]);
+            d.c1 = c1.ptr; d.c1_kind = c1.kind;
+            d.c2 = c2.ptr; d.c2_kind = c2.kind;
             d.m1 = matrixPtr(b.child1TransitionMatrix);
             d.m2 = matrixPtr(b.child2TransitionMatrix);
             d.c1_slot = d.c2_slot = d.dst_slot = MBAMD_NO_SLOT;
             d.scale_mode = b.destinationScaleWrite != BEAGLE_OP_NONE ? SCALE_WRITE : (b.destinationScaleRead != BEAGLE_OP_NONE ? SCALE_READ : SCALE_NONE);
             if (d.scale_mode != SCALE_NONE) {
                 const int si = d.scale_mode == SCALE_WRITE ? b.destinationScaleWrite : b.destinationScaleRead;
-                rc = ensureScale(si);
-                if (rc) return rc;
-                d.scale = scale[si];
+                if ((rc = scales.nodeBuffer(si, d.scale)) != BEAGLE_SUCCESS) return rc;
             }
             dstIdx[o] = b.destinationPartials;
             c1Idx[o] = b.child1Partials;
@@ -1570,7 +1553,7 @@ inline int Instance::submit(Plan* plan, int cumIdx, int32_t* cumPtr)
 inline bool Instance::independentOfPending(const Plan& plan, int cumIdx)
 {
     if (pending.empty()) return true;
-    std::vector<char> wr(nBuffers, 0), rd(nBuffers, 0), sc(scale.size(), 0);
+    std::vector<char> wr(nBuffers, 0), rd(nBuffers, 0), sc(scales.count(), 0);
     for (auto& pp : pending) {
         if (pp.first == &plan) return false;
         for (int b : pp.first->bufsWritten) wr[b] = 1;
@@ -1606,7 +1589,7 @@ inline int Instance::flushPending(bool keepPath)
     work.swap(pending);
     ++launchClock;
     for (auto& w : work) w.first->lastLaunch = launchClock;
-    auto cumOf = [&](int idx) { return idx >= 0 ? scale[idx] : (int32_t*) nullptr; };
+    auto cumOf = [&](int idx) { int32_t* p = nullptr; bool fresh; if (idx >= 0) (void) scales.cumulativeForAdd(idx, p, fresh); return p; };   // (it exists since the list was submitted)
     // merged launches need a per-factor-tile kernel for this shape (launch_mfma_split); other shapes -- e.g. three rate
     // categories -- run their lists one after the other, in submission order
     const bool mergeable = (NT == 1 && (K == 1 || K == 2 || K == 4)) || (NT == 2 && (K == 1 || K == 2));
@@ -1756,33 +1739,18 @@ inline int Instance::timedRun(const Plan& plan, int32_t* cum)
 // ---------------------------------------------------------------------------------------------
 // 4-state path: beagleUpdatePartials -> per-wave programs of the tree-walk kernel (mbamd_walk4.h).
 // ---------------------------------------------------------------------------------------------
-inline int Instance::ensureWide(int idx)
+// A compiled list of an arena layout was launched (or is held), compiled now or before: its destinations are valid and hold no recipe (overwritten;
+// the launch leaves its own small subtrees unstored afresh, runWalk), the exponent buffers it writes hold node exponents; the list counters
+inline void Instance::listLaunched(const BeagleOperation* ops, int n, bool path, bool forked)
 {
-    if (!wideScale[idx]) {
-        HIP_TRY(hipMalloc(&wideScale[idx], (size_t) K * Ppad * sizeof(int32_t)));
-        if (scaleState[idx] != 1) HIP_TRY(hipMemsetAsync(wideScale[idx], 0, (size_t) K * Ppad * sizeof(int32_t), stream));
+    for (int o = 0; o < n; ++o) {
+        valid[ops[o].destinationPartials] = 1;
+        dropRecipe(ops[o].destinationPartials);
+        if (ops[o].destinationScaleWrite != BEAGLE_OP_NONE) scales.nodeWritten(ops[o].destinationScaleWrite);
     }
-    if (scaleState[idx] == 1) {                  // node exponents so far: a cumulative buffer continues from them
-        MBAMD_LAUNCH(k_exp_widen, (unsigned) (((size_t) K * Ppad + 255) / 256), 256, 0, stream, (const int8_t*) arenaExp, estride, idx, K, Ppad,
-                     wideScale[idx]);
-        HIP_TRY(hipGetLastError());
-    } else if (scaleState[idx] == 0) {
-        HIP_TRY(hipMemsetAsync(wideScale[idx], 0, (size_t) K * Ppad * sizeof(int32_t), stream));
-    }
-    scaleState[idx] = 2;
-    return BEAGLE_SUCCESS;
-}
-
-// A cumulative buffer a kernel is about to add to.  One that was never written (freshly reset: the rescale-everything pass, or
-// MrBayes-style Reset + Accumulate of every node) is only allocated and marked cumulative -- `fresh`: the kernel STORES its sums,
-// no zero-fill launch; any other is brought into the wide form.
-inline int Instance::prepareCumulative(int idx, bool& fresh)
-{
-    fresh = scaleState[idx] == 0;
-    if (!fresh) return ensureWide(idx);
-    if (!wideScale[idx]) HIP_TRY(hipMalloc(&wideScale[idx], (size_t) K * Ppad * sizeof(int32_t)));
-    scaleState[idx] = 2;
-    return BEAGLE_SUCCESS;
+    listsTotal++;
+    if (path) { listsPath++; if (forked) forkedPaths++; }
+    else { listsWalked++; opsWalked += n; }
 }
 
 inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumIdx)
@@ -1805,11 +1773,7 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
     }
     int32_t* cumPtr = nullptr;
     walkCumFresh = false;
-    if (cumIdx != BEAGLE_OP_NONE) {
-        int rc = prepareCumulative(cumIdx, walkCumFresh);
-        if (rc) return rc;
-        cumPtr = wideScale[cumIdx];
-    }
+    if (cumIdx != BEAGLE_OP_NONE) { int rc = scales.cumulativeForAdd(cumIdx, cumPtr, walkCumFresh); if (rc) return rc; }
     bool build;
     Plan* plan = cachedPlan(reinterpret_cast<const int*>(ops), (size_t) n * 7, build);
     if (build) {
@@ -1822,17 +1786,9 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
         }
         if (planBuilt(*plan, rc)) return rc;
     }
-    // bookkeeping the list implies, whether compiled now or before: destinations valid, exponent buffers in node form
-    for (int o = 0; o < n; ++o) {
-        valid[ops[o].destinationPartials] = 1;
-        dropRecipe(ops[o].destinationPartials);  // (overwritten; the launch leaves its own tip pairs unstored afresh, runWalk)
-        if (ops[o].destinationScaleWrite != BEAGLE_OP_NONE) scaleState[ops[o].destinationScaleWrite] = 1;
-    }
+    listLaunched(ops, n, plan->path, plan->forked);
     int mrc = flushMatrices();
     if (mrc) return mrc;
-    listsTotal++;
-    if (plan->path) { listsPath++; if (plan->forked) forkedPaths++; }
-    else { listsWalked++; opsWalked += n; }
     if (plan->path && !sw.noFusePath && K <= 8 && plan->inlineProg.size() <= MBAMD_W4_INLINE) {
         // hold it: the next call decides (runHeldPath / integratePath4)
         heldPath = plan;
@@ -1849,7 +1805,7 @@ inline int Instance::updatePartials4(const BeagleOperation* ops, int n, int cumI
 // each segment and fill it with this list's buffer / matrix / scale indices.
 inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, const int* listOf, bool perList)
 {
-    const int scratchScale = (int) scale.size();              // sink / source of entries that do not rescale
+    const int scratchScale = (int) scales.count();              // sink / source of entries that do not rescale
     std::vector<int>& segList = w4segList;                     // (20/61-state walk) merged-list index of each operation of the segment
     segList.clear();
     std::vector<char>& written = w4written;
@@ -1861,7 +1817,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
     seg.clear();
     // segment state: buffers / exponent buffers the current segment has read or written
     std::vector<char>&segRead = w4segRead, &segWritten = w4segWritten, &segScale = w4segScale;
-    segRead.assign((size_t) nBuffers, 0); segWritten.assign((size_t) nBuffers, 0); segScale.assign(scale.size() + 1, 0);
+    segRead.assign((size_t) nBuffers, 0); segWritten.assign((size_t) nBuffers, 0); segScale.assign(scales.count() + 1, 0);
     if (w4writer.size() < (size_t) nBuffers) w4writer.assign((size_t) nBuffers, -1);
     int reloads = 0, externals = 0, phases = 0;
     auto flushSegment = [&]() -> int {
@@ -2072,7 +2028,7 @@ inline int Instance::buildWalk(Plan& plan, const BeagleOperation* ops, int n, co
         if (b.destinationScaleWrite != BEAGLE_OP_NONE) {
             w.scaleWrite = b.destinationScaleWrite;
         } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-            if (scaleState[b.destinationScaleRead] == 2 && !segScale[b.destinationScaleRead])
+            if (scales.isCumulative(b.destinationScaleRead) && !segScale[b.destinationScaleRead])
                 return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, "beagleUpdatePartials: destinationScaleRead names a cumulative buffer");
             w.scaleRead = b.destinationScaleRead;
         }
@@ -2163,7 +2119,7 @@ inline bool Instance::recognisePath(const BeagleOperation* ops, int n, int L, bo
     std::vector<char>& written = w4written;          // buffers earlier operations write; after this loop: any operation
     written.assign((size_t) nBuffers, 0);
     std::vector<char>& named = w4segScale;           // how many scale fields of the operations name an exponent buffer (3 = more)
-    named.assign(scale.size() + 1, 0);
+    named.assign(scales.count() + 1, 0);
     for (int o = 0; o < n; ++o) {
         const BeagleOperation& b = ops[o];
         const char* what;
@@ -2214,7 +2170,7 @@ inline bool Instance::recognisePath(const BeagleOperation* ops, int n, int L, bo
             p.scaleMode = SCALE_WRITE;
             p.scaleIdx = b.destinationScaleWrite;
         } else if (b.destinationScaleRead != BEAGLE_OP_NONE) {
-            if (scaleState[b.destinationScaleRead] == 2) return false;
+            if (scales.isCumulative(b.destinationScaleRead)) return false;
             p.scaleMode = SCALE_READ;
             p.scaleIdx = b.destinationScaleRead;
         }
@@ -2248,7 +2204,7 @@ inline Walk4Entry Instance::pathEntry(const PathStep& p, uint32_t pbuf, uint32_t
     e.m1 = (uint32_t) p.mchain * mbuf;
     e.m2 = (uint32_t) p.msib * mbuf;
     e.ewrite = (uint32_t) scratchRow * ebuf;
-    e.eread = (uint32_t) scale.size() * ebuf;
+    e.eread = (uint32_t) scales.count() * ebuf;
     if (p.scaleMode == SCALE_WRITE) e.ewrite = (uint32_t) p.scaleIdx * ebuf;
     else if (p.scaleMode == SCALE_READ) e.eread = (uint32_t) p.scaleIdx * ebuf;
     e.ctl = flags | ((uint32_t) p.scaleMode << 8);
@@ -2277,7 +2233,7 @@ inline bool Instance::buildPath4(Plan& plan, const BeagleOperation* ops, int n)
     plan.inlineProg.resize((size_t) n);
     for (int i = 0; i < n; ++i) {
         const PathStep& p = pathSteps[(size_t) i];
-        plan.inlineProg[(size_t) i] = pathEntry(p, pbuf, 32u, mbuf, (int) scale.size());
+        plan.inlineProg[(size_t) i] = pathEntry(p, pbuf, 32u, mbuf, (int) scales.count());
         plan.inlineProg[(size_t) i].ctl |= (uint32_t) p.arm << 16;
     }
     plan.path = true;
@@ -2305,7 +2261,7 @@ inline bool Instance::buildPathG(Plan& plan, const BeagleOperation* ops, int n, 
     plan.inlineProg.resize((size_t) n);
     for (int o = 0; o < n; ++o) {
         // (a different scratch row for neighbouring entries, see the arena)
-        plan.inlineProg[(size_t) o] = pathEntry(pathSteps[(size_t) o], pbuf, (uint32_t) MBAMD_WG_TW, mbuf, (int) scale.size() + (o % L) % MBAMD_WG_SCRATCH_ROWS);
+        plan.inlineProg[(size_t) o] = pathEntry(pathSteps[(size_t) o], pbuf, (uint32_t) MBAMD_WG_TW, mbuf, (int) scales.count() + (o % L) % MBAMD_WG_SCRATCH_ROWS);
         plan.inlineProg[(size_t) o].ctl |= (uint32_t) (o / L) << 10;
     }
     if (sw.verbose) std::fprintf(stderr, "[mbamd] walk plan: %d list(s) of %d operations each: root-ward paths%s (k_pathg)\n", nl, L, forked ? " that join" : "");
@@ -2323,8 +2279,8 @@ inline Walk4Args Instance::walk4Args() const
     a.pstride = geom.pstride;
     a.tips = arenaTips;
     a.tstride = geom.tstride;
-    a.exps = arenaExp;
-    a.estride = estride;
+    a.exps = scales.nodeExponents();
+    a.estride = scales.blockStride();
     a.matrices = matrices;
     a.K = K;
     a.Ppad = Ppad;
@@ -2441,7 +2397,7 @@ inline int Instance::ensureStored(const int* bufs, int n)
     for (int b : list) if (recipes[(size_t) b].nops > 1) return ensureStoredSubtrees();
     const int m = (int) list.size(), entries = (m + 1) / 2 * 2 + 2;              // the kernel's loop runs two entries a turn and reads two ahead
     const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
-    const uint32_t scratch = (uint32_t) scale.size();
+    const uint32_t scratch = (uint32_t) scales.count();
     storeProg.resize((size_t) entries);
     for (int i = 0; i < entries; ++i) {
         Walk4Entry& e = storeProg[(size_t) i];
@@ -2501,7 +2457,7 @@ inline int Instance::ensureStoredSubtrees()
 {
     const std::vector<int>& list = storeList;
     const uint32_t pbuf = (uint32_t) ((size_t) (Ppad / 64) * K), ebuf = (uint32_t) K * 64u, mbuf = (uint32_t) K * 64u;
-    const uint32_t scratch = (uint32_t) scale.size();
+    const uint32_t scratch = (uint32_t) scales.count();
     storeProg.clear();
     int pairs = 0, subtrees = 0;
     for (int b : list) {
@@ -2677,10 +2633,9 @@ inline int Instance::flushWalkG()
         const int ci = cums[q];
         if (ci == BEAGLE_OP_NONE) continue;
         bool fresh;
-        int rc = prepareCumulative(ci, fresh);
+        int rc = scales.cumulativeForAdd(ci, wgCum[q], fresh);
         if (rc) return rc;
         if (fresh) wgFresh |= 1 << q;
-        wgCum[q] = wideScale[ci];
     }
     bool build;
     Plan* plan = cachedPlan(key.data(), key.size(), build);
@@ -2691,7 +2646,7 @@ inline int Instance::flushWalkG()
         bool independent = nl > 1;
         if (independent) {
             std::vector<int> wr(nBuffers, -1), rd(nBuffers, -1);
-            std::vector<int> sc(scale.size(), -1);
+            std::vector<int> sc(scales.count(), -1);
             for (int o = 0; o < n && independent; ++o) {
                 const BeagleOperation& b = ops[o];
                 const int q = listOf[o];
@@ -2743,14 +2698,8 @@ inline int Instance::flushWalkG()
         }
         if (planBuilt(*plan, rc)) return rc;
     }
-    // what updatePartials4 counts; one flush = one list event, however many eigen-system parts it carries
-    listsTotal++;
-    if (plan->pathG) { listsPath++; if (plan->forked) forkedPaths++; }
-    else { listsWalked++; opsWalked += n; }
-    for (int o = 0; o < n; ++o) {
-        valid[ops[o].destinationPartials] = 1;
-        if (ops[o].destinationScaleWrite != BEAGLE_OP_NONE) scaleState[ops[o].destinationScaleWrite] = 1;
-    }
+    // one flush = one list event, however many eigen-system parts it carries
+    listLaunched(ops.data(), n, plan->pathG, plan->forked);
     return timedRun(*plan, nullptr);
 }
 
@@ -2796,8 +2745,8 @@ inline WalkGArgs Instance::walkGArgs() const
     a.tileBytes = wgTileBytes;
     a.tips = arenaTipStates;
     a.tipTileBytes = wgTipTileBytes;
-    a.exps = arenaExp;
-    a.estride = estride;
+    a.exps = scales.nodeExponents();
+    a.estride = scales.blockStride();
     a.matrices = matrices;
     a.tabOff = (unsigned) (wgTabFloats * 4);
     a.tabBytes = (unsigned) (wg_table_floats(S) * 4);
@@ -3203,22 +3152,9 @@ inline int Instance::accumulate(const int* idx, int n, int cumIdx, int sign, boo
 {
     if (cumIdx < 0 || cumIdx >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "scale factors: cumulative index");
     if (n <= 0) return BEAGLE_SUCCESS;
-    int rc = ensureScale(cumIdx);
-    if (rc) return rc;
-    std::vector<const int32_t*> ptrs(n);
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "scale factors: index");
-        rc = ensureScale(idx[i]);
-        if (rc) return rc;
-        ptrs[i] = scale[idx[i]];
-    }
-    const int32_t* const* dptrs = nullptr;
-    rc = stageDirect(ptrs.data(), sizeof(void*) * n, (const void**) &dptrs);
-    if (rc) return rc;
-    MBAMD_LAUNCH_BARRIER(k_scale_accumulate, (unsigned) ((Ppad + 255) / 256), 256, 0, stream, dptrs, n, sign,
-                 Ppad, scale[cumIdx], fresh ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return BEAGLE_SUCCESS;
+    return scales.accumulate(idx, n, cumIdx, sign, fresh);
 }
 
 // mayWait (beagleResetScaleFactors on the one engine behind a plain handle): on the level kernels the reset of an allocated buffer
@@ -3226,53 +3162,18 @@ inline int Instance::accumulate(const int* idx, int n, int cumIdx, int sign, boo
 // both (accumulateScale); any other entry point runs the reset first (runDeferredReset).  Children reset at once.
 inline int Instance::resetScale(int idx, bool mayWait)
 {
-    if (mayWait && !arena() && idx >= 0 && idx < nScale && scale[idx]) {
+    if (mayWait && idx >= 0 && idx < nScale && scales.allocated(idx)) {
         deferredReset = idx;
         return BEAGLE_SUCCESS;
     }
     if (idx < 0 || idx >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleResetScaleFactors: index");
-    if (arena()) {
-        // MrBayes resets every scale buffer once at start-up (reference src/mcmc.c:6270): nothing is allocated or
-        // launched for a buffer until it is used -- "never written" reads as zero everywhere
-        if (scaleState[idx] == 1) {               // node exponents in the arena: later reads must see zeros
-            MBAMD_LAUNCH(k_exp_copy, (unsigned) (((size_t) K * Ppad + 255) / 256), 256, 0, stream, arenaExp, estride, -1, idx, K, Ppad);
-            HIP_TRY(hipGetLastError());
-        }
-        scaleState[idx] = 0;
-        return BEAGLE_SUCCESS;
-    }
-    if (!scale[idx]) return ensureScale(idx);   // allocated zeroed
-    MBAMD_LAUNCH(k_scale_copy, (unsigned) ((Ppad + 255) / 256), 256, 0, stream, (const int32_t*) nullptr, Ppad, scale[idx]);
-    HIP_TRY(hipGetLastError());
-    return BEAGLE_SUCCESS;
+    return scales.reset(idx);
 }
 
 inline int Instance::copyScale(int dst, int src)
 {
     if (dst < 0 || dst >= nScale || src < 0 || src >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "beagleCopyScaleFactors: index");
-    if (arena()) {
-        const int st = scaleState[src];
-        if (st == 2) {
-            scaleState[dst] = 0;
-            int rc4 = ensureWide(dst);
-            if (rc4) return rc4;
-            HIP_TRY(hipMemcpyAsync(wideScale[dst], wideScale[src], (size_t) K * Ppad * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
-        } else if (st == 1) {
-            MBAMD_LAUNCH(k_exp_copy, (unsigned) (((size_t) K * Ppad + 255) / 256), 256, 0, stream, arenaExp, estride, src, dst, K, Ppad);
-            HIP_TRY(hipGetLastError());
-            scaleState[dst] = 1;
-        } else {
-            return resetScale(dst);
-        }
-        return BEAGLE_SUCCESS;
-    }
-    int rc = ensureScale(dst);
-    if (rc) return rc;
-    rc = ensureScale(src);
-    if (rc) return rc;
-    MBAMD_LAUNCH(k_scale_copy, (unsigned) ((Ppad + 255) / 256), 256, 0, stream, (const int32_t*) scale[src], Ppad, scale[dst]);
-    HIP_TRY(hipGetLastError());
-    return BEAGLE_SUCCESS;
+    return scales.copy(dst, src);
 }
 
 // beagleAccumulate / RemoveScaleFactors (sign -1).  afterReset (beagleAccumulateScaleFactors only): Reset + Accumulate of one
@@ -3296,43 +3197,12 @@ inline int Instance::accumulateScale(const int* idx, int n, int cumIdx, int sign
         int frc = flushPending();
         if (frc != BEAGLE_SUCCESS) return frc;
     }
-    if (!fuse) return arena() ? accumulate4(idx, n, cumIdx, sign) : accumulate(idx, n, cumIdx, sign);
+    if (!fuse) return accumulate(idx, n, cumIdx, sign);
     const int arc = accumulate(idx, n, cumIdx, +1, true);
     if (arc == BEAGLE_SUCCESS) { deferredReset = -1; return arc; }
     // the store did not happen (an index out of range, ...): the reset the caller asked for still does, then the error is theirs
     const int drc = runDeferredReset();
     return drc != BEAGLE_SUCCESS ? drc : arc;
-}
-
-// 4-state path: sources are node-exponent buffers of the arena (int8 per pattern and category) or cumulative ones
-inline int Instance::accumulate4(const int* idx, int n, int cumIdx, int sign)
-{
-    if (cumIdx < 0 || cumIdx >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "scale factors: cumulative index");
-    if (n <= 0) return BEAGLE_SUCCESS;
-    std::vector<ExpSource> src;
-    src.reserve(n);
-    for (int i = 0; i < n; ++i) {
-        if (idx[i] < 0 || idx[i] >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "scale factors: index");
-        if (scaleState[idx[i]] == 0) continue;                       // never written: zero
-        ExpSource e;
-        e.wide = scaleState[idx[i]] == 2 ? wideScale[idx[i]] : nullptr;
-        e.narrow = idx[i];
-        e.pad_ = 0;
-        src.push_back(e);
-    }
-    // (arena buffers in front of the wide ones: the kernel sums them without a branch; the order of an integer sum is free)
-    const int nNarrow = (int) (std::stable_partition(src.begin(), src.end(), [](const ExpSource& e) { return e.wide == nullptr; }) - src.begin());
-    if (src.empty()) return ensureWide(cumIdx);                      // (nothing to add: the buffer is cumulative from here on)
-    bool fresh;
-    int rc = prepareCumulative(cumIdx, fresh);
-    if (rc) return rc;
-    const ExpSource* dsrc = nullptr;
-    rc = stageDirect(src.data(), sizeof(ExpSource) * src.size(), (const void**) &dsrc);
-    if (rc) return rc;
-    MBAMD_LAUNCH_BARRIER(k_exp_accumulate, (unsigned) (((size_t) K * Ppad + 255) / 256), 256, 0, stream, dsrc, (int) src.size(), nNarrow, sign, K, Ppad,
-                 (const int8_t*) arenaExp, estride, wideScale[cumIdx], fresh ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return BEAGLE_SUCCESS;
 }
 
 // The arguments of a log-likelihood call (child == nullptr: at the root), whichever kernel serves it.
@@ -3402,26 +3272,8 @@ inline int Instance::integrateLevels(const int* parent, const int* child, const 
                               const int* cumIdx, int count)
 {
     IntegrateArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.count = count;
-    for (int n = 0; n < count; ++n) {
-        a.parent[n] = partials[parent[n]];
-        if (child) {
-            const int ci = child[n];
-            if (tipStates[ci]) { a.child[n] = tipStates[ci]; a.child_kind[n] = CHILD_STATES; }
-            else { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
-            a.matrix[n] = matrixPtr(prob[n]);
-        }
-        a.weights[n] = d_weights + (size_t) wIdx[n] * K;
-        a.freqs[n] = d_freqs + (size_t) fIdx[n] * S;
-        if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE) {
-            int rc = ensureScale(cumIdx[n]);
-            if (rc) return rc;
-            a.cum[n] = scale[cumIdx[n]];
-        }
-    }
-    double* const siteOut = (siteToHost && h_site_dev) ? h_site_dev : d_site;
-    siteOnHost = siteOut != d_site;
+    { int rc = integrateOperands(a, parent, child, prob, wIdx, fIdx, cumIdx, count); if (rc) return rc; }
+    double* const siteOut = siteTarget();
     if (S >= 8) MBAMD_LAUNCH_BARRIER(k_integrate_lnl_wide, (unsigned) nblocks, 256, 0, stream, a, S, SP, K, P, Ppad, (const double*) d_pweights, siteOut, h_sums_dev);
     else
         MBAMD_LAUNCH(k_integrate_lnl, (unsigned) nblocks, 64, 0, stream, a, S, SP, K, P, Ppad, (const double*) d_pweights, siteOut, h_sums_dev);
@@ -3438,22 +3290,16 @@ inline int Instance::integratePath4(const int* child, const int* prob, const int
     PathLnl4 t;
     std::memset(&t, 0, sizeof t);
     if (child) {
-        const int ci = child[0];
-        if (tipStates[ci]) { t.child = tipStates[ci]; t.child_kind = CHILD_STATES; }
-        else { t.child = partials[ci]; t.child_kind = CHILD_PARTIALS; }
+        const Operand c = operand(child[0]);
+        t.child = c.ptr; t.child_kind = c.kind;
         t.matrix = matrixPtr(prob[0]);
     }
     t.weights = d_weights + (size_t) wIdx[0] * K;
     t.freqs = d_freqs + (size_t) fIdx[0] * S;
     int rc = BEAGLE_SUCCESS;
-    if (cumIdx && cumIdx[0] != BEAGLE_OP_NONE && scaleState[cumIdx[0]] != 0) {
-        rc = ensureWide(cumIdx[0]);
-        t.cum = wideScale[cumIdx[0]];
-    }
-    double* const siteOut = (siteToHost && h_site_dev) ? h_site_dev : d_site;
-    siteOnHost = siteOut != d_site;
+    if (cumIdx && cumIdx[0] != BEAGLE_OP_NONE) rc = scales.cumulativeForRead(cumIdx[0], t.cum);
     t.pattern_weights = d_pweights;
-    t.site = siteOut;
+    t.site = siteTarget();
     t.wsite = h_sums_dev;
     t.P = P;
     hipEvent_t ev0{}, ev1{};
@@ -3486,29 +3332,11 @@ inline int Instance::integrate4(const int* parent, const int* child, const int* 
                          const int* cumIdx, int count)
 {
     IntegrateArgs4 a;
-    std::memset(&a, 0, sizeof a);
-    a.count = count;
-    for (int n = 0; n < count; ++n) {
-        a.parent[n] = reinterpret_cast<const f4*>(partials[parent[n]]);
-        if (child) {
-            const int ci = child[n];
-            if (tipStates[ci]) { a.child[n] = tipStates[ci]; a.child_kind[n] = CHILD_STATES; }
-            else { a.child[n] = partials[ci]; a.child_kind[n] = CHILD_PARTIALS; }
-            a.matrix[n] = matrixPtr(prob[n]);
-        }
-        a.weights[n] = d_weights + (size_t) wIdx[n] * K;
-        a.freqs[n] = d_freqs + (size_t) fIdx[n] * S;
-        if (cumIdx && cumIdx[n] != BEAGLE_OP_NONE && scaleState[cumIdx[n]] != 0) {
-            int rc = ensureWide(cumIdx[n]);
-            if (rc) return rc;
-            a.cum[n] = wideScale[cumIdx[n]];
-        }
-    }
-    double* const siteOut = (siteToHost && h_site_dev) ? h_site_dev : d_site;
-    siteOnHost = siteOut != d_site;
+    { int rc = integrateOperands(a, parent, child, prob, wIdx, fIdx, cumIdx, count); if (rc) return rc; }
+    double* const siteOut = siteTarget();
     if (wg) {
         WgGeom g;
-        g.tileFloats = wgTileBytes / 4; g.tipTileBytes = wgTipTileBytes; g.TP = wg_pairs_padded(S);
+        g.tileFloats = strides().partials; g.tipTileBytes = (unsigned) strides().tips; g.TP = wg_pairs_padded(S);
         MBAMD_LAUNCH_BARRIER(k_integrate_lnl_wg_wide, (unsigned) nblocks, MBAMD_INTEGRATE_WG_THREADS, 0, stream, a, S, SP, K, P, Ppad, g, (const double*) d_pweights, siteOut, h_sums_dev);
     } else {
         MBAMD_LAUNCH(k_integrate_lnl_s4, (unsigned) nblocks, 64, 0, stream, a, K, P, Ppad, geom, (const double*) d_pweights, siteOut, h_sums_dev);
@@ -3522,8 +3350,8 @@ inline DerivArgs Instance::layoutArgs() const
 {
     DerivArgs a;
     std::memset(&a, 0, sizeof a);
-    a.pstride = s4 ? (size_t) geom.pstride : (size_t) (wgTileBytes / 4);
-    a.tstride = s4 ? geom.tstride : wgTipTileBytes;
+    a.pstride = strides().partials;
+    a.tstride = (unsigned) strides().tips;
     a.S = S; a.SP = SP; a.K = K; a.Ppad = Ppad;
     a.first = 0; a.last = P;
     return a;
@@ -3534,26 +3362,13 @@ inline int Instance::lnlOperands(DerivArgs& a, int parent, int child, int prob, 
     a = layoutArgs();
     a.parent = partials[parent];
     if (child >= 0) {
-        a.child_tip = tipStates[child] ? 1 : 0;
-        a.child = tipStates[child] ? (const void*) tipStates[child] : (const void*) partials[child];
+        a.child_tip = holdsTip(child) ? 1 : 0;
+        a.child = operandPtr(child);
         a.matrix[0] = matrixPtr(prob);
     }
     a.weights = d_weights + (size_t) wIdx * K;
     a.freqs = d_freqs + (size_t) fIdx * S;
-    if (cumIdx != BEAGLE_OP_NONE) {
-        if (arena()) {
-            if (scaleState[cumIdx] != 0) {
-                const int rc = ensureWide(cumIdx);
-                if (rc) return rc;
-                a.cum = wideScale[cumIdx];
-            }
-        } else {
-            const int rc = ensureScale(cumIdx);
-            if (rc) return rc;
-            a.cum = scale[cumIdx];
-        }
-    }
-    return BEAGLE_SUCCESS;
+    return cumIdx != BEAGLE_OP_NONE ? scales.cumulativeForRead(cumIdx, a.cum) : BEAGLE_SUCCESS;
 }
 
 // The pre-order pass, the gradient in all branch lengths and the cross products: the bodies are shared with the double-precision
@@ -3772,31 +3587,7 @@ inline int Instance::getScaleExponents(int idx, int* out)
 {
     if (idx < 0 || idx >= nScale) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "scale exponents: index");
     HIP_TRY(hipStreamSynchronize(stream));
-    if (!arena()) {
-        int rc = ensureScale(idx);
-        if (rc) return rc;
-        std::vector<int32_t> h(Ppad);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(h.data(), scale[idx], (size_t) Ppad * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int k = 0; k < K; ++k) for (int c = 0; c < P; ++c) out[(size_t) k * P + c] = h[c];
-        return BEAGLE_SUCCESS;
-    }
-    const int st = scaleState[idx];
-    if (st == 0) { std::fill(out, out + (size_t) K * P, 0); return BEAGLE_SUCCESS; }
-    std::vector<int32_t> h((size_t) K * Ppad);
-    if (st == 2) {
-        HIP_TRY(hipMemcpy(h.data(), wideScale[idx], h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    } else {
-        int rc = grow(&d_tmp, &tmpCap, h.size() * sizeof(int32_t));
-        if (rc) return rc;
-        MBAMD_LAUNCH(k_exp_widen, (unsigned) ((h.size() + 255) / 256), 256, 0, stream, (const int8_t*) arenaExp, estride, idx, K, Ppad,
-                     (int32_t*) d_tmp);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(h.data(), d_tmp, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    for (int k = 0; k < K; ++k) for (int c = 0; c < P; ++c) out[(size_t) k * P + c] = h[(size_t) k * Ppad + c];
-    return BEAGLE_SUCCESS;
+    return scales.download(idx, P, out, [&](size_t bytes, void** p) { const int rc = grow(&d_tmp, &tmpCap, bytes); *p = d_tmp; return rc; });
 }
 
 // ---- reports (csrc/mbamd_reports.h, include/libhmsbeagle/mbamd_reports.h) -------------------------------------------
@@ -3844,14 +3635,12 @@ inline int Instance::finalPass(const MbamdFinalOperation* ops, int count)
         f.down = partials[b.downPartials];
         f.matrix = matrixPtr(b.transitionMatrix);
         if (b.ancestorFinal < 0 && b.rootTip >= 0) {
-            if (tipStates[b.rootTip]) { f.tip = tipStates[b.rootTip]; f.tipKind = CHILD_STATES; }
-            else if (valid[b.rootTip]) { f.tip = partials[b.rootTip]; f.tipKind = CHILD_PARTIALS; }
-            else return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdUpdateFinalPartials: the root tip was never set");
+            if (!readable(b.rootTip)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdUpdateFinalPartials: the root tip was never set");
+            const Operand t = operand(b.rootTip);
+            f.tip = t.ptr; f.tipKind = t.kind;
         }
         const dim3 grid((unsigned) ((P + 63) / 64), (unsigned) K);
-        if (s4) MBAMD_LAUNCH(k_final_pass<1>, grid, 64, 0, stream, f, S, SP, K, P, (size_t) geom.pstride, (size_t) geom.tstride);
-        else if (wg) MBAMD_LAUNCH(k_final_pass<2>, grid, 64, 0, stream, f, S, SP, K, P, (size_t) (wgTileBytes / 4), (size_t) wgTipTileBytes);
-        else MBAMD_LAUNCH(k_final_pass<0>, grid, 64, 0, stream, f, S, SP, K, P, (size_t) geom.pstride, (size_t) 0);
+        withLayout([&](auto tag) { MBAMD_LAUNCH(k_final_pass<decltype(tag)::value>, grid, 64, 0, stream, f, S, SP, K, P, strides().partials, strides().tips); });
         HIP_TRY(hipGetLastError());
         valid[b.destinationPartials] = 1;
         clearPreOrder(b.destinationPartials);
@@ -3863,19 +3652,12 @@ inline int Instance::getScaledPartials(int idx, int cumIdx, float* out, float* o
 {
     if (idx < 0 || idx >= nBuffers || !valid[idx] || tipStates[idx]) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetScaledPartials: buffer");
     if (cumIdx != BEAGLE_OP_NONE && (cumIdx < 0 || cumIdx >= nScale)) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetScaledPartials: cumulative scale index");
-    const int32_t *wide = nullptr, *narrow = nullptr;
+    const int32_t *wide = nullptr, *narrow = nullptr;              // exponents per (pattern, category) / per pattern
     if (cumIdx != BEAGLE_OP_NONE) {
-        if (arena()) {
-            if (scaleState[cumIdx] != 0) {
-                int rc = ensureWide(cumIdx);
-                if (rc) return rc;
-                wide = wideScale[cumIdx];
-            }
-        } else {
-            int rc = ensureScale(cumIdx);
-            if (rc) return rc;
-            narrow = scale[cumIdx];
-        }
+        const int32_t* exps = nullptr;
+        bool perCategory = false;
+        { int rc = scales.cumulativeForRead(cumIdx, exps, &perCategory); if (rc) return rc; }
+        (perCategory ? wide : narrow) = exps;
     }
     const size_t total = (size_t) K * P * S;
     int rc = grow(&d_tmp, &tmpCap, (total + (size_t) Ppad) * sizeof(float));
@@ -3886,9 +3668,7 @@ inline int Instance::getScaledPartials(int idx, int cumIdx, float* out, float* o
     float* d_ln = d_out + total;
     const unsigned blocks = (unsigned) ((total + 255) / 256);
     const int32_t* extra = (idx < (int) finalExpOf.size()) ? finalExpOf[idx] : nullptr;      // final partials carry their pass's own exponents
-    if (s4) MBAMD_LAUNCH(k_export_scaled<1>, blocks, 256, 0, stream, (const float*) partials[idx], wide, narrow, extra, S, K, P, Ppad, (size_t) geom.pstride, d_out, d_ln);
-    else if (wg) MBAMD_LAUNCH(k_export_scaled<2>, blocks, 256, 0, stream, (const float*) partials[idx], wide, narrow, extra, S, K, P, Ppad, (size_t) (wgTileBytes / 4), d_out, d_ln);
-    else MBAMD_LAUNCH(k_export_scaled<0>, blocks, 256, 0, stream, (const float*) partials[idx], wide, narrow, extra, S, K, P, Ppad, (size_t) geom.pstride, d_out, d_ln);
+    withLayout([&](auto tag) { MBAMD_LAUNCH(k_export_scaled<decltype(tag)::value>, blocks, 256, 0, stream, (const float*) partials[idx], wide, narrow, extra, S, K, P, Ppad, strides().partials, d_out, d_ln); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     syncedClock = launchClock;

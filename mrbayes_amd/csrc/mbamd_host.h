@@ -253,6 +253,17 @@ public:
     }
     unsigned char* host(size_t offset) const { return base + offset; }
     unsigned char* dev(size_t offset) const { return baseDev + offset; }      // the same slot as a kernel reads it over the host link
+    // a small kernel input (job list, pointer list): placed in the ring and read by the kernel directly over the host link -- no
+    // copy engine, no extra stream operation
+    int putDirect(const void* src, size_t bytes, hipStream_t stream, const void** devPtr)
+    {
+        if (((bytes + 63) & ~(size_t) 63) > cap / 2) return fail(BEAGLE_ERROR_OUT_OF_MEMORY, "staging ring too small");
+        size_t off = 0;
+        const int rc = put(src, bytes, stream, &off);
+        if (rc) return rc;
+        *devPtr = dev(off);
+        return BEAGLE_SUCCESS;
+    }
 
 private:
     unsigned char *base = nullptr, *baseDev = nullptr;

@@ -448,7 +448,8 @@ def check_scale_factor_calls(lib, kind, ncat, npat, monkeypatch, shards=None):
     with always-rescale on 8 taxa: the three storage forms of a scale buffer (4 states: int8 exponents in the arena; 20: the
     general-state arena; 33: one int32 buffer per pattern on the level kernels, where a reset waits for the accumulate that
     follows it and the two run as one store), and under MBAMD_SHARD child engines.  Expected values are integer sums of the
-    node buffers' exponents: equality is exact."""
+    node buffers' exponents: equality is exact.  The readers of a cumulative buffer (the root log-likelihood, the scaled read-out
+    of partials) give the same bits over a buffer in each form as over its copy, and leave the exponents as they were."""
     if shards is None:
         monkeypatch.delenv("MBAMD_SHARD", raising=False)
     else:
@@ -497,8 +498,27 @@ def check_scale_factor_calls(lib, kind, ncat, npat, monkeypatch, shards=None):
         half = nodes[: len(nodes) // 2]
         inst.remove_scale_factors(half, cum)
         assert np.array_equal(read(cum), total - sum(exps[: len(half)]))
+        # ... and the readers of a cumulative buffer, over each form a buffer can be held in (cumulative, node exponents, never
+        # written) and its copy: the same kernel on equal exponents, so equal results to the bit; reading changes no exponent
+        root = bd.condLikeIndex[0][t.root_left]
+        eig = bd.cijkIndex[0]
+
+        def root_lnl(scale):
+            rc, lnl = inst.calculate_root_log_likelihoods([root], [eig], [eig], [scale])
+            return rc, lnl, inst.get_site_log_likelihoods()
+
         for src, want in ((cum, total - sum(exps[: len(half)])), (nodes[1], exps[1]), (never, zero)):
             inst.copy_scale_factors(fourth, src)
+            assert np.array_equal(read(fourth), want)
+            assert np.array_equal(read(src), want)
+            rc_a, lnl_a, sites_a = root_lnl(fourth)
+            rc_b, lnl_b, sites_b = root_lnl(src)
+            assert rc_a == rc_b
+            assert np.array_equal(sites_a, sites_b)
+            assert np.array_equal(np.float64(lnl_a), np.float64(lnl_b))
+            part_a, ln_a = inst.get_scaled_partials(root, fourth)
+            part_b, ln_b = inst.get_scaled_partials(root, src)
+            assert np.array_equal(part_a, part_b) and np.array_equal(ln_a, ln_b)
             assert np.array_equal(read(fourth), want)
             assert np.array_equal(read(src), want)
     finally:
