@@ -132,6 +132,60 @@ BEAGLE_DLLEXPORT int mbamdSampleAncestralStates(int instance, const int* parentS
                                                 unsigned long long seed, int* outStates, int* outCategories,
                                                 double* outChangeCounts);
 
+/* The log-likelihood of the sites in their ORDER along the sequence under a hidden Markov chain over the rate categories -- Yang's
+ * autocorrelated discrete gamma (rates=adgamma), in general the Felsenstein-Churchill HMM --, and the per-site category posteriors
+ * of that chain, on the single- AND the double-precision engine.
+ *
+ * With the sites s = 0 .. n-1 (n = siteCount), K the category count, c_s = sitePatterns[s], w the weights of categoryWeightsIndex,
+ * T = categoryTransitions (row-major, T[a][b] = P(next site in b | this site in a) at distance 1), T^(j) its j-th power,
+ * j_s = siteJumps[s] >= 1 for s >= 1 (siteJumps[0] is ignored; a NULL array: all jumps are 1), L_k(c) the likelihood of pattern c in
+ * category k and L(c) = sum_k w_k L_k(c):
+ *
+ *     H = sum over all paths k_0 ... k_{n-1} of  w_{k_0} L_{k_0}(c_0) * prod_{s>=1} T^(j_s)[k_{s-1}, k_s] * L_{k_s}(c_s)
+ *
+ * With q_k(c) = w_k L_k(c) / L(c) -- exactly the doubles mbamdGetCategoryPosteriors returns -- and l(c) = ln L(c) -- exactly the
+ * doubles beagleGetSiteLogLikelihoods returns --,
+ *
+ *     ln H = sum_s l(c_s)  +  ln( u^T A_1 A_2 ... A_{n-1} 1 ),      u[k] = q_k(c_0),      A_s = T^(j_s) diag( q_k(c_s) / w_k )
+ *
+ * The second term is a correction to the plain mixture likelihood, made of numbers in [0, 1 / min w]; it vanishes where every row of
+ * T equals w (independent sites).  The per-site category posteriors are the forward-backward quantities of the same chain,
+ *
+ *     gamma_s(k) = alpha_s(k) beta_s(k) / sum_k alpha_s(k) beta_s(k),   alpha_s^T = u^T A_1 ... A_s,   beta_s = A_{s+1} ... A_{n-1} 1
+ *     outSiteCategoryPosteriors[k * siteCount + s] = gamma_s(k)                     (or NULL)
+ *
+ * -- the site rates under the HMM are sum_k gamma_s(k) r_k.  Pattern weights play no part: sites are listed explicitly.  Row sums of T
+ * are the caller's business: the formulas above are what is computed.
+ *
+ * Arithmetic: all in double.  T^(j) is formed on the host, once per distinct jump value of the call, by LEFT-TO-RIGHT BINARY
+ * EXPONENTIATION: from T, for every bit of j below its highest, from the high end, square, then, where the bit is set, multiply by
+ * T on the right.  Any jump is served, any number of distinct jumps.  The ordered product is a tree reduction on the device with the
+ * chunk length 64 (HMM_CHUNK, csrc/mbamd_autocorrelated.h): every run of 64 consecutive sites becomes its ordered K x K product, every
+ * run of 64 products one, until one is left; after every factor the product is scaled by an exact power of two and an integer
+ * exponent is carried beside it, so that scaling rounds nothing and nothing underflows at any n.  sum_s l(c_s) is added in the
+ * same tree: site order within a chunk, chunk order within a run of chunks.  The same inputs give the same bits, call after call;
+ * outLogLikelihood does not depend on whether the posteriors are asked for; a pattern-sharded instance returns the bits of an
+ * unsharded one (the shards' columns are gathered on the first device).
+ *
+ * Operands: those of the latest beagleCalculate{Root,Edge}LogLikelihoods call, as for mbamdGetCategoryPosteriors; q is kept with
+ * that call, so a second call after it -- another T: the correlation move -- costs the reduction alone.  One category: ln H =
+ * sum_s l(c_s), gamma = 1, and T is read only to be checked.
+ *
+ * Refusals.  No log-likelihood call yet is BEAGLE_ERROR_GENERAL, one with count > 1 BEAGLE_ERROR_NO_IMPLEMENTATION, a
+ * categoryWeightsIndex that is not that call's BEAGLE_ERROR_OUT_OF_RANGE; not on a multi-partition instance
+ * (BEAGLE_ERROR_NO_IMPLEMENTATION); whatever makes beagleGetSiteLogLikelihoods refuse makes this call refuse alike.
+ * BEAGLE_ERROR_OUT_OF_RANGE: siteCount < 1; sitePatterns, categoryTransitions or outLogLikelihood NULL; a pattern index outside
+ * [0, patternCount); a jump < 1 at s >= 1; an entry of T that is negative or not finite; a weight w_k that is not positive (the
+ * emission of such a category is not in q).  A refused call writes nothing.  The call is synchronous.
+ *
+ * A listed site whose pattern has L(c) not positive has all its q zero: the result (-inf) is written and
+ * BEAGLE_ERROR_FLOATING_POINT returned, as by the log-likelihood calls; the gamma of a call whose product is zero are all 0. */
+BEAGLE_DLLEXPORT int mbamdCalculateAutocorrelatedLogLikelihood(int instance, int categoryWeightsIndex, const int* sitePatterns,
+                                                               const int* siteJumps, int siteCount,
+                                                               const double* categoryTransitions,       /* [K][K] */
+                                                               double* outLogLikelihood,                /* never NULL */
+                                                               double* outSiteCategoryPosteriors);      /* [K][siteCount], or NULL */
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,7 +67,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
-    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
@@ -161,6 +161,7 @@ class BeagleLibrary:
         L.mbamdCalculateNodePosteriors.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, _dp, _ip, _dp, _dp]
         L.mbamdGetCategoryPosteriors.argtypes = [C.c_int, C.c_int, _dp]
         L.mbamdSampleAncestralStates.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, C.c_int, C.c_ulonglong, _ip, _ip, _dp]
+        L.mbamdCalculateAutocorrelatedLogLikelihood.argtypes = [C.c_int, C.c_int, _ip, _ip, C.c_int, _dp, _dp, _dp]
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -523,6 +524,24 @@ class BeagleInstance:
                                                  counts.ctypes.data_as(_dp) if changes else None)
         self._chk(rc, "mbamdSampleAncestralStates")
         return rc, states, cats, counts
+
+    def autocorrelated_log_likelihood(self, weights_index, site_patterns, transitions, jumps=None, posteriors=False):
+        """The log-likelihood of the listed sites, in their order, under a Markov chain over the rate categories along the sequence
+        (mbamdCalculateAutocorrelatedLogLikelihood): site_patterns[s] is the pattern of site s, transitions [K][K] the chain's
+        matrix at distance 1, jumps[s] >= 1 (s >= 1; None: all 1) the distance between site s - 1 and site s.  The operands are
+        those of the latest log-likelihood call.  Returns (rc, ln H, gamma [K][sites] or None); BEAGLE_ERROR_FLOATING_POINT is
+        passed through, any other error code raises."""
+        c, t, j = _i(site_patterns), _d(transitions), _opt_i(jumps)
+        if j is not None and len(j) != len(c):
+            raise ValueError("autocorrelated_log_likelihood: site_patterns and jumps differ in length")
+        if t.shape != (self.category_count, self.category_count):
+            raise ValueError("autocorrelated_log_likelihood: transitions must be [categories][categories]")
+        out = C.c_double(0.0)
+        gamma = np.empty((self.category_count, len(c))) if posteriors else None
+        rc = self.lib.mbamdCalculateAutocorrelatedLogLikelihood(self.id, weights_index, c.ctypes.data_as(_ip), _ptr(j), len(c), t.ctypes.data_as(_dp),
+                                                                C.byref(out), gamma.ctypes.data_as(_dp) if posteriors else None)
+        self._chk(rc, "mbamdCalculateAutocorrelatedLogLikelihood", allow=(BEAGLE_ERROR_FLOATING_POINT,))
+        return rc, out.value, gamma
 
     def calculate_cross_products(self, posts, pres, rates, weights, edge_lengths, squared=False):
         """The cross-product matrix of the gradient in the rate matrix over every listed branch in one call

@@ -1175,6 +1175,51 @@ int mbamdSampleAncestralStates(int instance, const int* parentSlots, const int* 
     return BEAGLE_SUCCESS;
 }
 
+// the site-order HMM over the rate categories (mbamd_autocorrelated.h; semantics: mbamd_reports.h)
+int mbamdCalculateAutocorrelatedLogLikelihood(int instance, int categoryWeightsIndex, const int* sitePatterns, const int* siteJumps, int siteCount,
+                                              const double* categoryTransitions, double* outLogLikelihood, double* outSiteCategoryPosteriors)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdCalculateAutocorrelatedLogLikelihood(sites=%d%s%s)", siteCount, siteJumps ? ", jumps" : "", outSiteCategoryPosteriors ? ", posteriors" : "");
+    const char* const who = "mbamdCalculateAutocorrelatedLogLikelihood";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (siteCount < 1) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "siteCount is less than 1");
+    if (!sitePatterns || !categoryTransitions || !outLogLikelihood) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "sitePatterns, categoryTransitions or outLogLikelihood is null");
+    const int K = h->dim.categoryCount, P = h->dim.patternCount;
+    for (int s = 0; s < siteCount; ++s) {
+        if (sitePatterns[s] < 0 || sitePatterns[s] >= P) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a pattern index outside [0, patternCount)");
+        if (siteJumps && s >= 1 && siteJumps[s] < 1) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "a jump is less than 1");
+    }
+    for (int i = 0; i < K * K; ++i)
+        if (!(categoryTransitions[i] >= 0.0) || !(categoryTransitions[i] < INFINITY))
+            return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "an entry of categoryTransitions is negative or not finite");
+    HmmSource one;
+    if (h->f64) {
+        const int rc = h->f64->autocorrelatedPrepare(categoryWeightsIndex, one);
+        if (rc) return rc;
+        one.start = 0;
+        return h->f64->autocorrelatedRun(&one, 1, categoryWeightsIndex, sitePatterns, siteJumps, siteCount, categoryTransitions, outLogLikelihood,
+                                         outSiteCategoryPosteriors);
+    }
+    // pattern shards: every child's q and site log-likelihoods are gathered, in pattern order, on the first child's device, which then
+    // runs what the one engine of an unsharded instance runs, on the same numbers
+    std::vector<HmmSource> sources;
+    const int rc = each_engine(h, true, [&](Instance* c, const Handle::Span& ch) -> int {
+        HmmSource src;
+        const int crc = c->autocorrelatedPrepare(categoryWeightsIndex, src);
+        if (crc) return crc;
+        src.start = ch.start;
+        sources.push_back(src);
+        return BEAGLE_SUCCESS;
+    });
+    if (rc) return rc;
+    Instance* const first = h->first();
+    (void) hipSetDevice(first->device);
+    return first->autocorrelatedRun(sources.data(), (int) sources.size(), categoryWeightsIndex, sitePatterns, siteJumps, siteCount, categoryTransitions,
+                                    outLogLikelihood, outSiteCategoryPosteriors);
+}
+
 // the cross-product matrix of the gradient in the rate matrix (mbamd_crossproducts.h; semantics: beagle.h)
 int beagleCalculateCrossProductDerivative(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* categoryRateIndices,
                                           const int* categoryWeightsIndices, const double* edgeLengths, int count, double* outSumDerivatives,

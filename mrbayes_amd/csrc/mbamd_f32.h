@@ -22,6 +22,7 @@
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges: a draw of all ancestral states from their joint posterior
+#include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
 
 namespace mbamd {
@@ -208,6 +209,14 @@ struct Instance {
     // patternOffset = the index in the instance of this engine's pattern 0, states at [slot * stride + c], changes[i] never null
     int sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
                               long long patternOffset, int* states, int* categories, double* changes, size_t stride);
+    // mbamdCalculateAutocorrelatedLogLikelihood (mbamd_autocorrelated.h): the checks on this engine and where its inputs lie, then --
+    // on the first engine of the instance -- the call itself over the sources of all; synchronous
+    int autocorrelatedPrepare(int wIdx, HmmSource& src) { return autocorrelated_prepare(*this, wIdx, src); }
+    int autocorrelatedRun(const HmmSource* sources, int sourceCount, int wIdx, const int* sitePatterns, const int* siteJumps, int n, const double* T,
+                          double* outLnl, double* outPost)
+    {
+        return autocorrelated_run(*this, sources, sourceCount, wIdx, sitePatterns, siteJumps, n, T, outLnl, outPost);
+    }
     int finalPass(const MbamdFinalOperation* ops, int count);
     int getScaledPartials(int idx, int cumIdx, float* out, float* outLn);
     void setTiming(bool on) { timing = on; }
@@ -373,6 +382,9 @@ private:
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
+    template <class E> friend int autocorrelated_prepare(E&, int, HmmSource&);
+    template <class E> friend int autocorrelated_weights(E&, int, double*);
+    template <class E> friend int autocorrelated_run(E&, const HmmSource*, int, int, const int*, const int*, int, const double*, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued or held runs first
@@ -449,6 +461,15 @@ private:
         return BEAGLE_SUCCESS;
     }
     int timedEnd(hipEvent_t ev0, hipEvent_t ev1) { return launchesEnd(ev0, ev1); }
+    // what getSites would return, where a kernel of this stream can read it (host: its host address where that is pinned host memory)
+    int siteLogLikelihoods(const double** dev, const double** host)
+    {
+        if (!haveSite) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteLogLikelihoods: no likelihood computed yet");
+        *dev = derivValid ? h_deriv_dev : siteOnHost ? h_site_dev : d_site;
+        *host = derivValid ? h_deriv : siteOnHost ? h_site : nullptr;
+        return BEAGLE_SUCCESS;
+    }
+    const HostMirror& weightsMirror() const { return h_weights; }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value

@@ -32,6 +32,7 @@
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors <DERIV_F64, double>: node-state and category posteriors from the pre-order buffers
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges <DERIV_F64, double>: a draw of all ancestral states from their joint posterior
+#include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
 
 namespace mbamd {
@@ -100,6 +101,13 @@ public:
     // a draw of all ancestral states from their joint posterior (mbamd_ancestral_sampling.h), as on the single-precision engine: synchronous
     int sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
                               long long patternOffset, int* states, int* categories, double* changes, size_t stride);
+    // mbamdCalculateAutocorrelatedLogLikelihood (mbamd_autocorrelated.h), as on the single-precision engine: synchronous
+    int autocorrelatedPrepare(int wIdx, HmmSource& src) { return autocorrelated_prepare(*this, wIdx, src); }
+    int autocorrelatedRun(const HmmSource* sources, int sourceCount, int wIdx, const int* sitePatterns, const int* siteJumps, int n, const double* T,
+                          double* outLnl, double* outPost)
+    {
+        return autocorrelated_run(*this, sources, sourceCount, wIdx, sitePatterns, siteJumps, n, T, outLnl, outPost);
+    }
     int getSites(double* out);
     // as Instance::kernelTiming: no device timing on this engine, the partials launches (walks and levels) are counted
     int kernelTiming(double* ms, long* launches, int reset);
@@ -176,6 +184,9 @@ private:
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
+    template <class E> friend int autocorrelated_prepare(E&, int, HmmSource&);
+    template <class E> friend int autocorrelated_weights(E&, int, double*);
+    template <class E> friend int autocorrelated_run(E&, const HmmSource*, int, int, const int*, const int*, int, const double*, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
     // everything queued runs first
@@ -212,6 +223,19 @@ private:
     // (no device timing on this engine)
     int timedBegin(hipEvent_t&, hipEvent_t&) { return BEAGLE_SUCCESS; }
     int timedEnd(hipEvent_t, hipEvent_t) { return BEAGLE_SUCCESS; }
+    // what getSites would return, in d_site (after a derivative call its values are the host's: they are sent back)
+    int siteLogLikelihoods(const double** dev, const double** host)
+    {
+        if (!haveSite) return fail(BEAGLE_ERROR_GENERAL, "beagleGetSiteLogLikelihoods: no log-likelihood was calculated");
+        if (derivValid) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipMemcpy(d_site, derivSite.data(), (size_t) P * sizeof(double), hipMemcpyHostToDevice));
+        }
+        *dev = d_site;
+        *host = nullptr;
+        return BEAGLE_SUCCESS;
+    }
+    const HostMirror& weightsMirror() const { return hostWeights; }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
     // f(this engine's layout as a compile-time constant)
     template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }

@@ -433,6 +433,8 @@ k_edge_second_mfma(ReadoutArgs a)
 //     timedBegin, timedEnd                an event pair around a call's launches while kernel timing is on (the sampling call)
 //     withLayout                          f(layout as a compile-time constant)
 //     posteriorOperands                   the checked operands of the latest log-likelihood call
+//     siteLogLikelihoods, weightsMirror   its site log-likelihoods where a kernel can read them; the host copy of the category weights
+//                                         (the site-order HMM of mbamd_autocorrelated.h)
 
 // the arithmetic type of a layout
 template <int LAYOUT> using deriv_real = std::conditional_t<LAYOUT == DERIV_F64, double, float>;

@@ -527,6 +527,16 @@ class BeagleDivision:
         (q * cat_rates[:, None]).sum(0)."""
         return self.inst.get_category_posteriors(self.cijkIndex[chain])
 
+    def AutocorrelatedLogLikelihood(self, chain=0, site_patterns=None, transitions=None, jumps=None, posteriors=False):
+        """ln H of the listed sites under autocorrelated rates after the chain's latest LogLike: a Markov chain with the matrix
+        transitions [categories][categories] over the rate categories along the sequence, site_patterns[s] the pattern of site s,
+        jumps[s] the distance between sites s - 1 and s (None: 1).  posteriors=True: (ln H, gamma [categories][sites]), the
+        per-site category posteriors under the chain -- site rates are (gamma * cat_rates[:, None]).sum(0)."""
+        if site_patterns is None or transitions is None:
+            raise ValueError("AutocorrelatedLogLikelihood: site_patterns and transitions are required")
+        rc, lnh, gamma = self.inst.autocorrelated_log_likelihood(self.cijkIndex[chain], site_patterns, transitions, jumps=jumps, posteriors=posteriors)
+        return (lnh, gamma) if posteriors else lnh
+
     def AncestralSamplingEdges(self, chain=0):
         """The breadth-first edge list of the chain's current tree as sample_ancestral_states takes it -- (nodes, parent slots,
         post-order buffers, matrices): nodes[0] = the top interior node is slot 0, nodes[i + 1] the lower end of edge i.  The root
