@@ -528,6 +528,13 @@ BEAGLE_DLLEXPORT int mbamdGetListCounts(int instance, long* out6);
  * every entry an operation, no prefetch, wait or stored exponent; one wave or several, mbamdGetPlainWaveCounts), out[1] on the generic one.  (As above: for tests;
  * a facade or a double-precision instance reports zeros; a null pointer is BEAGLE_ERROR_OUT_OF_RANGE.) */
 BEAGLE_DLLEXPORT int mbamdGetWalkCounts(int instance, long* out2);
+/* Queue flushes of the tree-walk layout at 40 and 60 ... 63 states since the instance was made: out[0] on the range-safe instantiations
+ * of k_walkg / k_pathg (a list that reads partials of unknown magnitude: set by the client, or written by an operation that did not
+ * rescale -- their bf16 pieces are formed from the value times 2^24, exact down to the smallest subnormal), out[1] on the plain ones
+ * (every partials operand written by a SCALE_WRITE operation, or a compact tip: always-rescaling clients).  A list on the range-safe
+ * ones must keep its partials operands and the factors formed from them below 2^103 (they are scaled by 2^24 on the way).  (For tests; a
+ * facade or a double-precision instance reports zeros; a null pointer is BEAGLE_ERROR_OUT_OF_RANGE.) */
+BEAGLE_DLLEXPORT int mbamdGetRangeSafeCounts(int instance, long* out2);
 /* The launches on the plain instantiations by waves per workgroup: out[W - 1], W = 1 ... 8, launches of plain programs of W waves (a
  * whole-tree list cut over W > 1 waves runs the plain loop on each, values that cross waves travel through LDS; a list that would need
  * an eviction, a prefetch or a stored exponent at that geometry runs on the generic instantiation and is counted there).  (For tests:

@@ -68,7 +68,7 @@ EXPORTS = [
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
     "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
-    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
+    "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRangeSafeCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
@@ -165,6 +165,7 @@ class BeagleLibrary:
         L.mbamdGetKernelTiming.argtypes = [C.c_int, _dp, C.POINTER(C.c_long), C.c_int]
         L.mbamdGetListCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetWalkCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdGetRangeSafeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetPlainWaveCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdGetSubtreeRecomputeCounts.argtypes = [C.c_int, C.POINTER(C.c_long)]
@@ -661,6 +662,12 @@ class BeagleInstance:
         """(launches of the 4-state walk kernel's plain instantiation, launches of the generic one)"""
         out = (C.c_long * 2)()
         self._chk(self.lib.mbamdGetWalkCounts(self.id, out), "mbamdGetWalkCounts")
+        return tuple(int(v) for v in out)
+
+    def get_range_safe_counts(self):
+        """(queue flushes at 40 and 60-63 states on the range-safe instantiations of k_walkg / k_pathg, on the plain ones)"""
+        out = (C.c_long * 2)()
+        self._chk(self.lib.mbamdGetRangeSafeCounts(self.id, out), "mbamdGetRangeSafeCounts")
         return tuple(int(v) for v in out)
 
     def get_plain_wave_counts(self):

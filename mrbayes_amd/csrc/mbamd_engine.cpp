@@ -1293,6 +1293,15 @@ int mbamdGetWalkCounts(int instance, long* out2)
     in->walkCounts(out2);
     return BEAGLE_SUCCESS;
 }
+int mbamdGetRangeSafeCounts(int instance, long* out2)
+{
+    GET_INSTANCE(instance);
+    if (!out2) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetRangeSafeCounts: null output");
+    out2[0] = out2[1] = 0;
+    if (!in) return BEAGLE_SUCCESS;              // (counted by the one single-precision engine only)
+    in->rangeSafeCounts(out2);
+    return BEAGLE_SUCCESS;
+}
 int mbamdGetPlainWaveCounts(int instance, long* out8)
 {
     GET_INSTANCE_NOFLUSH(instance);

@@ -64,6 +64,11 @@ static void raise_walkg_lds(int maxLds)
     if (hipFuncSetAttribute((const void*) k_walkg<SC_, WMAX_, CH_, DEPTH_>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
         hipFuncSetAttribute((const void*) k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgsInline>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess)
         (void) hipGetLastError();
+    if constexpr (WgShape<SC_>::BF) {            // (the range-safe instantiations exist where the pieces are bf16: wg_contract_bf16)
+        if (hipFuncSetAttribute((const void*) k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgs, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess ||
+            hipFuncSetAttribute((const void*) k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgsInline, true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxLds) != hipSuccess)
+            (void) hipGetLastError();
+    }
 }
 
 // 4-state walk: how an unstored result is made again from compact tips alone (Instance::ensureStored) -- the one to three operations of
@@ -223,6 +228,7 @@ struct Instance {
     int kernelTiming(double* ms, long* launches, int reset);
     int stepTiming(double* ms, long* steps, int reset);
     void listCounts(long out6[6]) const { const long c[6] = {listsTotal, listsPath, forkedPaths, fusedPaths, listsWalked, opsWalked}; std::copy(c, c + 6, out6); }
+    void rangeSafeCounts(long out2[2]) const { out2[0] = wgFlushesRangeSafe; out2[1] = wgFlushesPlain; }
     void walkCounts(long out2[2]) const { out2[0] = walksPlain; out2[1] = walksGeneric; }   // launches of the plain instantiations of k_walk4_t (one wave or several) / of the generic ones
     void plainWaveCounts(long out[MBAMD_W4_MAXW]) const { for (int w = 0; w < MBAMD_W4_MAXW; ++w) out[w] += walksPlainByW[w]; }   // ... of the plain ones by waves per workgroup (out[W - 1]; added: the sums over engines)
     int walkTrace(long long* out, int maxSteps, int* outSteps, int* outWaves);
@@ -291,6 +297,16 @@ private:
     std::vector<int> wgListStart, wgListCum;     // first operation / cumulative scale index (or BEAGLE_OP_NONE) of each list
     int32_t* wgCum[MBAMD_WG_MAXLISTS] = {nullptr, nullptr, nullptr, nullptr};
     int wgFresh = 0;
+    // The bf16-piece contraction of 40 and 60..63 states has two instantiations (wg_contract_bf16): the plain one splits a row value
+    // exactly only above about 2^-110.  wgRescaled[b]: buffer b was last written by a SCALE_WRITE operation of this layout -- every
+    // column's maximum in [0.5, 1) (or, its exponent clamped, above 2^-24) --; anything else (a client's partials, an unscaled or
+    // SCALE_READ result, pre-order and final partials) is of unknown magnitude.  A flush whose operations read nothing but rescaled
+    // buffers and compact tips runs the plain instantiation, every other one the range-safe one (wgRangeSafe, for runWalkG).
+    std::vector<uint8_t> wgRescaled;
+    std::vector<int8_t> wgWrote;                 // scratch of flushWalkG
+    bool wgRangeSafe = false;
+    long wgFlushesRangeSafe = 0, wgFlushesPlain = 0;     // flushes at those state counts on either (mbamdGetRangeSafeCounts)
+    void wgForget(int idx) { if (idx >= 0 && idx < (int) wgRescaled.size()) wgRescaled[(size_t) idx] = 0; }
     uint8_t* arenaTipStates = nullptr;           // uint8 [tile][buffer][32]
     unsigned long wgTileBytes = 0;               // partials arena: bytes between 32-pattern tiles
     unsigned wgTipTileBytes = 0;
@@ -437,7 +453,7 @@ private:
     // a destination holds no recipe any more and has memory (buffers of the level kernels are allocated on first use) ...
     int beforeWrite(int d) { dropRecipe(d); return ensurePartials(d); }
     // ... nor the exponents of a final pass
-    void afterWrite(int d) { if (d < (int) finalExpOf.size()) finalExpOf[d] = nullptr; }
+    void afterWrite(int d) { if (d < (int) finalExpOf.size()) finalExpOf[d] = nullptr; wgForget(d); }
     // the PreOp / GradEdge table of a call, on the device
     int stageTable(const void* src, size_t bytes, void** out)
     {
@@ -1048,6 +1064,7 @@ inline int Instance::importPartials(int idx, const double* in, bool hasCategorie
     if (idx < 0 || idx >= nBuffers) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "partials buffer index");
     if (idx < (int) finalExpOf.size()) finalExpOf[idx] = nullptr;
     clearPreOrder(idx);
+    wgForget(idx);
     if (s4 && !hasCategories) {
         // beagleSetTipPartials with 0/1 entries (IUPAC ambiguity codes, reference src/mbbeagle.c:150-166): a state mask
         // per pattern says the same thing in one byte, and the tree walk reads it like any compact tip
@@ -2721,7 +2738,29 @@ inline int Instance::flushWalkG()
     }
     // one flush = one list event, however many eigen-system parts it carries
     listLaunched(ops.data(), n, plan->pathG, plan->forked);
-    return timedRun(*plan, nullptr);
+    // Which instantiation of the bf16-piece contraction (wgRescaled).  Here, not earlier: the plan exists, so every index of every
+    // operation has been checked (checkOperation, when this list or an identical one was compiled).  The operations in the order
+    // they run: a child an earlier operation of the flush writes is what that operation leaves (wgWrote: -1 not written, else
+    // whether it rescales), whatever the buffer held before -- compact states included.  The buffers' own marks change only once
+    // the launch has been accepted; a launch that failed leaves results nobody knows.
+    const bool pieces = S >= MBAMD_WG_BF_MIN;
+    wgRangeSafe = false;
+    if (pieces) {
+        if (wgRescaled.size() != (size_t) nBuffers) wgRescaled.assign((size_t) nBuffers, 0);
+        wgWrote.assign((size_t) nBuffers, -1);
+        for (const BeagleOperation& b : ops) {
+            for (int c : {b.child1Partials, b.child2Partials}) {
+                const int8_t w = wgWrote[(size_t) c];
+                if (w >= 0 ? w == 0 : (!tipStates[c] && !wgRescaled[(size_t) c])) wgRangeSafe = true;
+            }
+            wgWrote[(size_t) b.destinationPartials] = b.destinationScaleWrite != BEAGLE_OP_NONE ? 1 : 0;
+        }
+        ++(wgRangeSafe ? wgFlushesRangeSafe : wgFlushesPlain);
+    }
+    const int rrc = timedRun(*plan, nullptr);
+    if (pieces)
+        for (const BeagleOperation& b : ops) wgRescaled[(size_t) b.destinationPartials] = rrc == BEAGLE_SUCCESS && wgWrote[(size_t) b.destinationPartials] == 1 ? 1 : 0;
+    return rrc;
 }
 
 template <int SC_, int WMAX_, int CH_, int DEPTH_>
@@ -2732,9 +2771,23 @@ inline void Instance::launch_walkg_t(Instance& in, const WalkGArgs& a, int W, in
         ai.a = a;
         ai.a.prog = nullptr;
         std::memcpy(ai.inl, inlineProg->data(), inlineProg->size() * sizeof(Walk4Entry));
+        if constexpr (WgShape<SC_>::BF) {
+            if (in.wgRangeSafe) {
+                auto safe = k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgsInline, true>;
+                MBAMD_LAUNCH_BARRIER(safe, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, ai);
+                return;
+            }
+        }
         auto kern = k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgsInline>;
         MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, ai);
         return;
+    }
+    if constexpr (WgShape<SC_>::BF) {
+        if (in.wgRangeSafe) {
+            auto safe = k_walkg<SC_, WMAX_, CH_, DEPTH_, WalkGArgs, true>;
+            MBAMD_LAUNCH_BARRIER(safe, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, a);
+            return;
+        }
     }
     auto kern = k_walkg<SC_, WMAX_, CH_, DEPTH_>;
     MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 64 * W * (a.spread ? 2 : 1), wg_lds_bytes(W, nslots, in.S), in.stream, a);
@@ -2747,6 +2800,18 @@ inline void Instance::launch_pathg_t(Instance& in, const WalkGArgs& a, const std
     ai.a = a;
     ai.a.prog = nullptr;
     std::memcpy(ai.inl, prog.data(), prog.size() * sizeof(Walk4Entry));
+    if constexpr (WgShape<SC_>::BF) {
+        if (in.wgRangeSafe) {
+            if (forked) {
+                auto safe = k_pathg<SC_, WalkGArgsInline, true, true>;
+                MBAMD_LAUNCH_BARRIER(safe, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S, true), in.stream, ai);
+            } else {
+                auto safe = k_pathg<SC_, WalkGArgsInline, false, true>;
+                MBAMD_LAUNCH_BARRIER(safe, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S), in.stream, ai);
+            }
+            return;
+        }
+    }
     if (forked) {
         auto kern = k_pathg<SC_, WalkGArgsInline, true>;
         MBAMD_LAUNCH_BARRIER(kern, walkg_grid(in.Ppad / MBAMD_WG_TW, in.K * a.lists), 128, pathg_lds_bytes(in.S, true), in.stream, ai);
@@ -3665,6 +3730,7 @@ inline int Instance::finalPass(const MbamdFinalOperation* ops, int count)
         HIP_TRY(hipGetLastError());
         valid[b.destinationPartials] = 1;
         clearPreOrder(b.destinationPartials);
+        wgForget(b.destinationPartials);
     }
     return BEAGLE_SUCCESS;
 }

@@ -44,7 +44,8 @@ __host__ __device__ inline size_t pathg_lds_bytes(int S, bool forked = false)
 }
 
 // FORK = false is the single path's kernel: no arm can start or join in it, and nothing of the arms' code or registers is in it.
-template <int SC, class ARGS = WalkGArgs, bool FORK = false>
+// RS: the range-safe form of the bf16-piece contraction (wg_contract_bf16), as k_walkg's.
+template <int SC, class ARGS = WalkGArgs, bool FORK = false, bool RS = false>
 __global__ void __launch_bounds__(128)
 k_pathg(ARGS AA)
 {
@@ -97,7 +98,11 @@ k_pathg(ARGS AA)
 #pragma unroll
             for (int r = 0; r < ACC; ++r) f[it][r] = 0.0f;
         if constexpr (BF) {
-            wg_contract_bf16<NT, NKB, TP>(a, b, f);      // (k_walkg's arithmetic: the same bits)
+            wg_contract_bf16<NT, NKB, TP, RS>(a, b, f);      // (k_walkg's arithmetic: the same bits)
+            if constexpr (RS) {
+#pragma unroll
+                for (int it = 0; it < NT; ++it) f[it] *= WG_RS_DOWN;
+            }
         } else {
 #pragma unroll
             for (int tc = 0; tc < TP; ++tc)

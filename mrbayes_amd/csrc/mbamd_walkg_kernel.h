@@ -60,7 +60,16 @@ __device__ __forceinline__ void wg_split_pair(float v0, float v1, unsigned& p, u
 // k_walkb and k_pathg give the same bits.
 //   a     the chunk's table operands, index (kb NT + it) 3 + piece (wg_table_put)
 //   rows  the child's block rows of the chunk: K-block kb = rows 8 kb .. 8 kb + 7 (NR of them exist; the rest are zero)
-template <int NT, int NKBC, int NR, class VECA>
+// RS, the RANGE-SAFE form: the split above is exact only while the third piece is a normal bf16, i.e. for values of about 2^-110 and
+// more.  With RS every row value is multiplied by 2^24 before the split -- exact for every finite float below 2^103: a normal value has
+// its last bit at 2^-149 or above, scaled 2^-125, a normal bf16; a subnormal k 2^-149 becomes k 2^-125, and every remainder is a
+// multiple of 2^-125 -- and the factor comes out times 2^24 exactly (a power of two commutes with every product, alignment and
+// rounding of the contraction): the caller multiplies the finished factor by WG_RS_DOWN, which rounds only where the factor is
+// subnormal.  For rows the plain form splits exactly, both give the same bits.  The host chooses per list (Instance::flushWalkG).
+// (The other end pays: a row value or a finished factor of 2^104 and more overflows in the scaled domain, where the plain form
+//  reaches 2^127 -- the limit of lists that run this form, stated in DESIGN.md "Operand range" and beagle.h; not guarded.)
+constexpr float WG_RS_UP = 16777216.0f, WG_RS_DOWN = 1.0f / 16777216.0f;
+template <int NT, int NKBC, int NR, bool RS = false, class VECA>
 __device__ __forceinline__ void wg_contract_bf16(const VECA* a, const float* rows, mbd_acc16 (&f)[NT])
 {
     constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};     // a3 b1, a1 b3, a2 b2, a2 b1, a1 b2, a1 b1
@@ -71,7 +80,11 @@ __device__ __forceinline__ void wg_contract_bf16(const VECA* a, const float* row
         for (int jj = 0; jj < 4; ++jj) {
             const int t0 = 8 * kb + 2 * jj;
             unsigned p = 0, q = 0, w = 0;
-            if (t0 < NR) wg_split_pair(rows[t0 < NR ? t0 : 0], t0 + 1 < NR ? rows[t0 + 1 < NR ? t0 + 1 : 0] : 0.0f, p, q, w);
+            if (t0 < NR) {
+                const float v0 = rows[t0 < NR ? t0 : 0], v1 = t0 + 1 < NR ? rows[t0 + 1 < NR ? t0 + 1 : 0] : 0.0f;
+                if constexpr (RS) wg_split_pair(v0 * WG_RS_UP, v1 * WG_RS_UP, p, q, w);
+                else wg_split_pair(v0, v1, p, q, w);
+            }
             pc[0][jj] = __builtin_bit_cast(float, p); pc[1][jj] = __builtin_bit_cast(float, q); pc[2][jj] = __builtin_bit_cast(float, w);
         }
 #pragma unroll
@@ -104,7 +117,8 @@ template <int I> struct WgInt { static constexpr int value = I; };
 //   20 states: CH 1, DEPTH 2 -- a job is 10 MFMAs = 640 cycles, less than a memory round trip; three sets of 15 registers;
 //   61 states: CH 2, DEPTH 1 -- a chunk is 31 MFMAs = 2000 cycles; two sets of 48 registers fit beside the 64 accumulators
 //              (whole jobs did not: the allocator shuttled LOADED operands through AccVGPRs, a vmcnt(0) per job).
-template <int SC, int WMAX, int CH, int DEPTH, class ARGS = WalkGArgs>
+// RS: the range-safe form of the bf16-piece contraction (wg_contract_bf16) -- lists that read partials of unknown magnitude.
+template <int SC, int WMAX, int CH, int DEPTH, class ARGS = WalkGArgs, bool RS = false>
 __global__ void __launch_bounds__(64 * WMAX, MBAMD_WG_MINWAVES(SC))
 k_walkg(ARGS AA)
 {
@@ -250,7 +264,13 @@ k_walkg(ARGS AA)
             float rows[TPC];
 #pragma unroll
             for (int tc = 0; tc < TPC; ++tc) rows[tc] = Vb::get(b[tc / V], tc % V);
-            wg_contract_bf16<NT, NKBC, TPC>(o.a, rows, f);
+            wg_contract_bf16<NT, NKBC, TPC, RS>(o.a, rows, f);
+            if constexpr (RS) {
+                if (h == CH - 1) {                   // the finished factor, times 2^24: back (rounds only where it is subnormal)
+#pragma unroll
+                    for (int it = 0; it < NT; ++it) f[it] *= WG_RS_DOWN;
+                }
+            }
         } else {
 #pragma unroll
             for (int tc = 0; tc < TPC; ++tc)

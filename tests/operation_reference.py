@@ -1,4 +1,4 @@
-"""High-precision restatement of the engine's arithmetic operations, for tests/test_operation_bounds.py.
+"""High-precision restatement of the engine's arithmetic operations, for tests/test_operation_bounds.py and its neighbours.
 
 One partials operation, the root / edge integration and a pruning pass over explicit transition matrices (no eigen-system), as plain
 numpy einsum in np.longdouble where its unit roundoff is at most 2^-60 (x86: 2^-64), and EXACTLY, in fractions.Fraction, where it is
@@ -120,6 +120,11 @@ class Reference:
     def operation(self, m1, v1, m2, v2):
         """One partials operation: (m1 . v1) * (m2 . v2), [K][P][S]"""
         return self.contract(m1, v1) * self.contract(m2, v2)
+
+    def factors(self, m1, v1, m2, v2):
+        """The two factors of every element of one operation, (m1 . v1, m2 . v2): what an absolute error per rounding of one
+        factor is multiplied by in the product (tests/test_exponent_range.py)"""
+        return self.contract(m1, v1), self.contract(m2, v2)
 
     def root(self, weights, freqs, partials):
         """L_c = sum_k w_k sum_i pi_i partials[k][c][i]"""

@@ -20,9 +20,11 @@ Every term of every sum is non-negative, so these relative bounds hold for any o
 u_e is the roundoff of the arithmetic the integration kernel really uses (integration_roundoff below).
 
 Operand ranges: buffer A's (category, pattern) columns are spread over 2^-100 ... 2^0 (single) / 2^-900 ... 2^0 (double) -- clear of
-the double-precision engine's exponent clamp at -1000 and of the bf16 pieces' operand range (columns below about 2^-110
-lose their third piece); buffer B's ELEMENTS are spread over the 40 binades 2^-10 ... 2^30, so that every unscaled result stays a
-normal float32 (>= 2^-104.4 * 2^-14.4), with one pattern all zero and one pattern zero in category 0 only.
+the double-precision engine's exponent clamp at -1000; buffer B's ELEMENTS are spread over the 40 binades 2^-10 ... 2^30, so that
+every unscaled result stays a normal float32 (>= 2^-104.4 * 2^-14.4), with one pattern all zero and one pattern zero in category 0
+only.  The single-precision engine's range below that -- columns at 2^-104 ... 2^-146, subnormal results, where the bounds carry an
+absolute term and the bf16-piece contraction runs its range-safe instantiation ("Operand range") -- is
+tests/test_exponent_range.py's, which uses the helpers of this module.
 
 Each check prints the worst error / bound it met (pytest -s shows them).
 """
