@@ -411,7 +411,12 @@ BEAGLE_DLLEXPORT int mbamdGetSecondDerivativeLaunches(int instance, long* out2);
  * with t_e = edgeLengths[e], r_k the category rates of categoryRateIndices[e] (beagleSetCategoryRates[WithIndex]), q_k(c) the
  * posterior category probabilities of beagleCalculateEdgeDerivatives (1 with one category) and weight_c the pattern weights.  A
  * category whose den is not positive has underflowed and is skipped.  Every scale factor of either buffer cancels per (pattern,
- * category).  This is upstream's quantity: sum_ij X[i,j] M[i,j] is exactly d lnL / d epsilon for Q -> Q + epsilon M whenever M
+ * category) -- for operands down to the smallest subnormal: this call, beagleUpdatePrePartials, beagleCalculateEdgeDerivatives,
+ * mbamdCalculateEdgeSecondDerivatives and the derivative arguments of beagleCalculateEdgeLogLikelihoods take the own power of two
+ * out of every post-order column (exactly) before its first product, so an UNSCALED column of a dynamically rescaling client, at
+ * 2^-140 say, is read with the bits it holds and den never flushes for a live column.  All of them are functions of the buffers AS
+ * STORED: an unscaled column below 2^-126 holds fewer than 24 bits (three at 2^-146), and a client that wants derivatives of full
+ * accuracy that close to underflow must rescale.  This is upstream's quantity: sum_ij X[i,j] M[i,j] is exactly d lnL / d epsilon for Q -> Q + epsilon M whenever M
  * commutes with Q (M = Q gives sum_e t_e d lnL / d t_e), and upstream's approximation otherwise.
  * outSumSquaredDerivatives must be NULL (BEAGLE_ERROR_NO_IMPLEMENTATION otherwise: upstream's implementations do not fill it
  * either); not served on a multi-partition instance (BEAGLE_ERROR_NO_IMPLEMENTATION).  With more than one category the rules of

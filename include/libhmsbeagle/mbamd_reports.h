@@ -55,7 +55,11 @@ BEAGLE_DLLEXPORT int mbamdGetScaledPartials(int instance, int bufferIndex, int c
  *     outBestPosteriors[i * patternCount + c] = that maximum                                              (or NULL)
  *     outSumPosteriors[i * stateCount + a]    = sum_c weight_c p_c(a)      the expected number of sites in state a; never NULL
  * The products are formed in the engine's precision, the sums in double.  Whatever scale a column (pattern, category) of
- * either buffer carries leaves the ratio j_k / den_k: no scale buffer is named.  q_k(c) are the posterior category
+ * either buffer carries leaves the ratio j_k / den_k: no scale buffer is named -- and this holds for operands down to the
+ * smallest subnormal: the own power of two of a post-order column is taken out, exactly, before the first product, here and in
+ * mbamdGetCategoryPosteriors (where it joins the category's exponent).  Both calls are functions of the buffers AS STORED: an
+ * unscaled column below 2^-126 holds fewer than 24 bits, and a client that wants posteriors of full accuracy that close to
+ * underflow must rescale.  q_k(c) are the posterior category
  * probabilities of beagleCalculateEdgeDerivatives (1 with one category: nothing is then asked of a log-likelihood call); a
  * category whose den is not positive has underflowed and is skipped.  A compact tip is its indicator vector, a MISSING state the
  * vector of ones (p_c is then the normalised mixture of the pre-order columns), four-state bitplanes give the compatible

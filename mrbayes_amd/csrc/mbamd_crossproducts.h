@@ -9,6 +9,9 @@
 // -- per edge and category a product A B^T of two [S x patterns] matrices, A the pre-order columns times one coefficient per pattern,
 // B the post-order columns: a GEMM with an S x S result whose reduction runs over edges x categories x patterns.  Every scale factor
 // of either buffer cancels per (pattern, category); a category with den <= 0 has underflowed and is skipped, as in k_edge_readout.
+// The post-order column has its own power of two taken out before its first product (pre_exponent / pre_scaled of
+// mbamd_derivatives.h, on the staged column in LDS or in registers -- no second pass over memory): den is formed from columns at
+// [0.5, 1) and the coefficient ... / den cannot overflow over a subnormal den.
 //
 // Grid (64-pattern blocks, edge chunks), one wave per workgroup; the wave LOOPS over the edges of its chunk, so that what a launch
 // leaves behind is one S x S double matrix per (block, chunk) -- never one per edge.  Arithmetic as in k_edge_readout: products in
@@ -62,6 +65,7 @@ __device__ __forceinline__ void cross_stage(const CrossArgs& a, const GradEdge& 
     const int S = g.S;
     double den = 0.0;
     if (live) {
+        Real mx = (Real) 0;
         // (sixteen states at a time: their loads are issued together -- one state after the other, every load's latency is waited for)
         for (int l0 = 0; l0 < S; l0 += 16) {
             Real p[16], v[16];
@@ -77,9 +81,17 @@ __device__ __forceinline__ void cross_stage(const CrossArgs& a, const GradEdge& 
                 if (l0 + u < S) {
                     colA[(l0 + u) * MBAMD_XP_ROW] = p[u];
                     colB[(l0 + u) * MBAMD_XP_ROW] = v[u];
-                    den += (double) (p[u] * v[u]);
+                    mx = v[u] > mx ? v[u] : mx;
                 }
             }
+        }
+        // the post-order column's own power of two goes out where it lies, in LDS, before its first product (mbamd_derivatives.h:
+        // an unscaled column may be subnormal); a compact tip's power is 2^0
+        const int ev = ed.postTip ? 0 : pre_exponent(mx);
+        for (int l = 0; l < S; ++l) {
+            const Real v = pre_scaled(colB[l * MBAMD_XP_ROW], ev);
+            colB[l * MBAMD_XP_ROW] = v;
+            den += (double) (colA[l * MBAMD_XP_ROW] * v);
         }
     }
     Real coef = (Real) 0;
@@ -126,6 +138,7 @@ k_cross_products(CrossArgs a)
                 } else {
                     const f4 q4 = reinterpret_cast<const f4*>(ed.post)[at];
                     v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
+                    pre_scale4(v);
                 }
                 double den = 0.0;
 #pragma unroll

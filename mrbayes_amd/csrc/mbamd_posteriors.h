@@ -8,7 +8,8 @@
 // category), which leaves the ratio inside a category:
 //     j_k(a) = pre_n[k,c,a] post_n[k,c,a],     den_k = sum_a j_k(a),     p_c(a) = sum_k q_k(c) j_k(a) / den_k
 // with q the posterior category probabilities of the pattern (k_category_posteriors; one category: q = 1).  This is DESIGN 4.4.2's
-// argument with the identity in the place of the differential matrix: no matrix, no quotient of two buffers, no exponents.  A
+// argument with the identity in the place of the differential matrix: no matrix, no quotient of two buffers, no exponents (the
+// post-order column's own power of two is taken out before the product, mbamd_derivatives.h: an unscaled column may be subnormal).  A
 // category whose den_k is zero has underflowed and is skipped, as k_edge_readout skips it.  A compact tip is the indicator of its
 // state, a missing state the vector of ones, the four-state bitplanes give the compatible columns; where ONE state is compatible
 // the posterior is that indicator and is written as such -- exactly 1 and 0, where the formula would give sum_k q_k.
@@ -72,7 +73,9 @@ k_node_posteriors(PosteriorArgs a)
                         for (int l = 0; l < 4; ++l) j[l] = (tip >> l & 1u) ? j[l] : 0.0f;
                     } else {
                         const f4 q4 = reinterpret_cast<const f4*>(nd.post)[at];
-                        j[0] *= q4.x; j[1] *= q4.y; j[2] *= q4.z; j[3] *= q4.w;
+                        float v[4] = {q4.x, q4.y, q4.z, q4.w};
+                        pre_scale4(v);
+                        j[0] *= v[0]; j[1] *= v[1]; j[2] *= v[2]; j[3] *= v[3];
                     }
                     double den = 0.0;
 #pragma unroll
@@ -99,17 +102,21 @@ k_node_posteriors(PosteriorArgs a)
             } else {
                 for (int l = 0; l < S; ++l) col[l * 64] = 0.0;
                 for (int k = 0; k < K; ++k) {
+                    // (the post-order column's own power of two goes out before the first product: an unscaled column may be
+                    //  subnormal.  Staging the column in LDS instead of walking it a third time was measured: slower, +54 %
+                    //  on the call against +15 %, profiles/preorder_exponent_range.txt)
+                    const PostColumn<LAYOUT, Real> post(nd.postTip ? nullptr : nd.post, g, k, c);
                     double den = 0.0;
                     for (int l = 0; l < S; ++l) {
                         const Real p = deriv_partial<LAYOUT, Real>(nd.pre, g, k, l, c);
                         // (a compact tip here has a missing state: the vector of ones)
-                        den += (double) (nd.postTip ? p : p * deriv_partial<LAYOUT, Real>(nd.post, g, k, l, c));
+                        den += (double) (nd.postTip ? p : p * post[l]);
                     }
                     if (den > 0.0) {
                         const double f = (a.q != nullptr ? a.q[(size_t) k * g.Ppad + c] : 1.0) / den;
                         for (int l = 0; l < S; ++l) {
                             const Real p = deriv_partial<LAYOUT, Real>(nd.pre, g, k, l, c);
-                            col[l * 64] += f * (double) (nd.postTip ? p : p * deriv_partial<LAYOUT, Real>(nd.post, g, k, l, c));
+                            col[l * 64] += f * (double) (nd.postTip ? p : p * post[l]);
                         }
                     }
                 }

@@ -14,6 +14,13 @@
 // k_category_posteriors from that call's operands (the L-sum of k_edge_derivatives, per-category exponents recombined).  A category
 // whose denominator is zero has underflowed and carries nothing: it is skipped.
 //
+// Post-order operands may be UNSCALED (a dynamically rescaling client rescales only after an underflow): columns anywhere down to
+// 2^-149.  Every kernel here, in mbamd_crossproducts.h, mbamd_posteriors.h and mbamd_derivatives.h therefore takes the own power of
+// two out of a post-order column before its first product (pre_exponent / pre_scaled of mbamd_derivatives.h: on the column where a
+// kernel stages it, in LDS or in registers, pre_scale4; PostColumn where it is read straight from memory) -- exact, and invisible
+// on columns in the normal range.  The ratios drop the exponent; where categories are combined (k_category_posteriors,
+// k_edge_derivatives) it joins the category's exponent.  An all-zero column stays a skipped category.
+//
 // Arithmetic as everywhere: products in the engine's precision (FMA chains over the states, ascending), sums over states and
 // categories of the read-outs in double, block sums through mbd_wave_sum_store (fixed order).
 //
@@ -69,10 +76,7 @@ struct ReadoutArgs {
     int                nb, edgeCount;
 };
 
-__device__ __forceinline__ int pre_exponent(float mx) { return (mx > 0.0f && mx < 3.0e38f) ? mbd_frexp_exp(mx) : 0; }
-__device__ __forceinline__ int pre_exponent(double mx) { int e = 0; if (mx > 0.0 && mx < 1.0e300) (void) frexp(mx, &e); return e; }
-__device__ __forceinline__ float pre_scaled(float v, int e) { return mbd_ldexp(v, -e); }
-__device__ __forceinline__ double pre_scaled(double v, int e) { return ldexp(v, -e); }
+// (pre_exponent, pre_scaled and PostColumn, the power of two of a column: mbamd_derivatives.h)
 
 // dynamic LDS of the general kernel: the two matrices [from][to], then two columns [state][thread]
 template <class Real> inline size_t pre_lds_bytes(int S) { return ((size_t) 2 * S * S + (size_t) 2 * S * 64) * sizeof(Real); }
@@ -103,6 +107,7 @@ k_pre_partials(PreArgs a)
             } else {
                 const f4 q = reinterpret_cast<const f4*>(op.sib)[at];
                 v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+                pre_scale4(v);
             }
             const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(op.mSib)) + k * 16;      // m[j * 4 + i] = P(i -> j)
             t.x *= fmaf(m[12], v[3], fmaf(m[8], v[2], fmaf(m[4], v[1], m[0] * v[0])));
@@ -137,8 +142,17 @@ k_pre_partials(PreArgs a)
         if (c >= g.last) return;
         unsigned tip = 0;
         if (op.sibKind == 1) tip = deriv_tip<LAYOUT>(op.sib, g, c);
-        else if (op.sibKind == 0)
-            for (int j = 0; j < S; ++j) colA[j * 64] = deriv_partial<LAYOUT, Real>(op.sib, g, k, j, c);
+        else if (op.sibKind == 0) {
+            // (the sibling's column with its own power of two taken out, where it lies: mbamd_derivatives.h)
+            Real sx = (Real) 0;
+            for (int j = 0; j < S; ++j) {
+                const Real v = deriv_partial<LAYOUT, Real>(op.sib, g, k, j, c);
+                colA[j * 64] = v;
+                sx = v > sx ? v : sx;
+            }
+            const int es = pre_exponent(sx);
+            for (int j = 0; j < S; ++j) colA[j * 64] = pre_scaled(colA[j * 64], es);
+        }
         for (int i = 0; i < S; ++i) {
             Real f = (Real) 1;
             if (op.sibKind == 1) {
@@ -167,6 +181,12 @@ k_pre_partials(PreArgs a)
     }
 }
 
+template <bool PER_CATEGORY>
+__device__ __forceinline__ int category_exponent(const DerivArgs& a, int k, int c)
+{
+    return PER_CATEGORY && a.cum != nullptr ? a.cum[(size_t) k * a.Ppad + c] : 0;
+}
+
 // q[k][c]: the posterior probability of category k at pattern c under the operands of a log-likelihood call (a: as for
 // k_edge_derivatives -- parent, child or null, matrix[0], weights, freqs, cum; site = q, [K][Ppad]).  One thread per pattern.
 template <int LAYOUT, class Real>
@@ -177,16 +197,15 @@ k_category_posteriors(DerivArgs a)
     const int S = a.S, K = a.K;
     const int c = (int) blockIdx.x * 64 + (int) threadIdx.x;
     if (c >= a.last) return;
-    int emax = 0;
-    if (a.cum != nullptr && PER_CATEGORY) {
-        emax = -2147483647;
-        for (int k = 0; k < K; ++k) { const int e = a.cum[(size_t) k * a.Ppad + c]; emax = e > emax ? e : emax; }
-    }
+    // as k_edge_derivatives: the categories meet at the largest exponent among the live ones (the stored one + the powers of two
+    // taken out of the two columns); a.site holds the categories' own sums until that exponent is known
     const unsigned tip = a.child_tip ? deriv_tip<LAYOUT>(a.child, a, c) : 0u;
-    double L = 0.0;
+    int emax = 0;
+    bool any = false;
     for (int k = 0; k < K; ++k) {
+        const PostColumn<LAYOUT, Real> parent(a.parent, a, k, c), child(a.child_tip ? nullptr : a.child, a, k, c);
         double cat = 0.0;
-        for (int i = 0; i < S; ++i) {
+        for (int i = 0; i < S && parent.live && child.live; ++i) {
             Real f = (Real) 1;
             if (a.child != nullptr) {
                 if (a.child_tip && LAYOUT != DERIV_S4) {
@@ -194,15 +213,28 @@ k_category_posteriors(DerivArgs a)
                 } else {
                     f = (Real) 0;
                     for (int j = 0; j < S; ++j) {
-                        const Real v = a.child_tip ? ((tip >> j & 1u) ? (Real) 1 : (Real) 0) : deriv_partial<LAYOUT, Real>(a.child, a, k, j, c);
+                        const Real v = a.child_tip ? ((tip >> j & 1u) ? (Real) 1 : (Real) 0) : child[j];
                         f = deriv_fma(deriv_matrix<LAYOUT, Real>(a.matrix[0], a, k, i, j), v, f);
                     }
                 }
             }
-            cat += (double) (deriv_partial<LAYOUT, Real>(a.parent, a, k, i, c) * f) * a.freqs[i];
+            cat += (double) (parent[i] * f) * a.freqs[i];
         }
-        double l = cat * a.weights[k];
-        if constexpr (PER_CATEGORY) l = ldexp(l, (a.cum != nullptr ? a.cum[(size_t) k * a.Ppad + c] : 0) - emax);
+        a.site[(size_t) k * a.Ppad + c] = cat * a.weights[k];
+        if (cat > 0.0) {
+            const int E = category_exponent<PER_CATEGORY>(a, k, c) + parent.e + child.e;
+            emax = !any || E > emax ? E : emax;
+            any = true;
+        }
+    }
+    double L = 0.0;
+    for (int k = 0; k < K; ++k) {
+        double l = a.site[(size_t) k * a.Ppad + c];
+        if (l > 0.0) {
+            // (the columns once more, for their powers of two: K integers have no room in registers for every K)
+            const PostColumn<LAYOUT, Real> parent(a.parent, a, k, c), child(a.child_tip ? nullptr : a.child, a, k, c);
+            l = ldexp(l, category_exponent<PER_CATEGORY>(a, k, c) + parent.e + child.e - emax);
+        }
         a.site[(size_t) k * a.Ppad + c] = l;
         L += l;
     }
@@ -236,6 +268,7 @@ k_edge_readout(ReadoutArgs a)
                 } else {
                     const f4 q4 = reinterpret_cast<const f4*>(ed.post)[at];
                     v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
+                    pre_scale4(v);
                 }
                 const MBAMD_AS_CONST float* m = as_const(reinterpret_cast<const float*>(ed.D)) + k * 16;          // m[j * 4 + l] = D(l -> j)
 #pragma unroll
@@ -250,6 +283,7 @@ k_edge_readout(ReadoutArgs a)
                     den += (double) (p[l] * v[l]);
                 }
             } else {
+                const PostColumn<LAYOUT, Real> post(ed.postTip ? nullptr : ed.post, g, k, c);
                 for (int l = 0; l < S; ++l) {
                     const Real p = deriv_partial<LAYOUT, Real>(ed.pre, g, k, l, c);
                     Real f = (Real) 0, f2 = (Real) 0, v;
@@ -262,11 +296,11 @@ k_edge_readout(ReadoutArgs a)
                         }
                     } else {
                         for (int j = 0; j < S; ++j) {
-                            const Real x = deriv_partial<LAYOUT, Real>(ed.post, g, k, j, c);
+                            const Real x = post[j];
                             f = deriv_fma(deriv_matrix<LAYOUT, Real>(ed.D, g, k, l, j), x, f);
                             if constexpr (ORDER == 2) f2 = deriv_fma(deriv_matrix<LAYOUT, Real>(D2, g, k, l, j), x, f2);
                         }
-                        v = deriv_partial<LAYOUT, Real>(ed.post, g, k, l, c);
+                        v = post[l];
                     }
                     num += (double) (p * f);
                     if constexpr (ORDER == 2) num2 += (double) (p * f2);
@@ -343,6 +377,7 @@ k_edge_second_mfma(ReadoutArgs a)
     for (int k = 0; k < K; ++k) {
         double den = 0.0;
         if (live) {
+            float mx = 0.0f;
             // (sixteen states at a time, as cross_stage: their loads are issued together)
             for (int l0 = 0; l0 < S; l0 += 16) {
                 float p[16], v[16];
@@ -358,8 +393,18 @@ k_edge_second_mfma(ReadoutArgs a)
                     if (l0 + u < S) {
                         pre[(l0 + u) * 64] = p[u];
                         post[(l0 + u) * 64] = (ed.postTip && tip >= (unsigned) S) ? 0.0f : v[u];
-                        den += (double) (p[u] * v[u]);
+                        if (ed.postTip) den += (double) (p[u] * v[u]);
+                        mx = v[u] > mx ? v[u] : mx;
                     }
+                }
+            }
+            if (!ed.postTip) {
+                // (the post-order column's own power of two goes out where it lies, before its first product, as in cross_stage)
+                const int ev = pre_exponent(mx);
+                for (int l = 0; l < S; ++l) {
+                    const float v = pre_scaled(post[l * 64], ev);
+                    post[l * 64] = v;
+                    den += (double) (pre[l * 64] * v);
                 }
             }
         }

@@ -1,5 +1,5 @@
 """What the tests of the calls on the pre-order buffers share (tests/test_preorder_gradient.py, test_cross_products.py,
-test_edge_second_derivatives.py, test_node_posteriors.py, and the tree part of test_complex_eigen.py): the divisions and cases, the
+test_edge_second_derivatives.py, test_node_posteriors.py, test_preorder_exponent_range.py, and the tree part of test_complex_eigen.py): the divisions and cases, the
 numpy float64 reference of both passes and of the gradient, and its a-priori bounds.  No engine code and no tests.
 
 The reference is numpy float64 from the `Division` alone: post-order pruning as in tests/pruning_reference.py, the pre-order
@@ -9,6 +9,8 @@ recursion un-normalised,
 and Q = U diag(lambda) U^-1, D_k = r_k Q.  Per branch (node n) and pattern c
     N_c = sum_k w_k sum_l pre_n[k,c,l] sum_j D_k[l,j] post_n[k,c,j],   A_c the same with |D_k|,   L_c = sum_k w_k sum_l pre_n[k,c,l] post_n[k,c,l]
     d_c = N_c / L_c.
+pre_operation, pre_order_given, lnl_posteriors, edge_terms and mixed are the same formulas on columns and matrices AS GIVEN -- what an
+engine holds, read back -- for tests/test_preorder_exponent_range.py, which measures the readers and not the post-order pass.
 The bounds (`bounds`, `unit_roundoff`, `bound_factor`) are derived in the module docstrings of tests/test_preorder_gradient.py and
 tests/test_cross_products.py.
 """
@@ -63,17 +65,55 @@ def post_order(div, lengths):
     return cl, mats
 
 
+def pre_operation(parent, m_own, sib=None, m_sib=None):
+    """one pre-order operation, un-normalised, on columns [K][P][S] and matrices [K][S][S] as given:
+    tmp[k,c,i] = parent[k,c,i] sum_j m_sib[k,i,j] sib[k,c,j] (no sibling: the factor 1), out[k,c,j] = sum_i m_own[k,i,j] tmp[k,c,i]"""
+    tmp = parent if sib is None else parent * np.einsum("kij,kcj->kci", m_sib, sib)
+    return np.einsum("kij,kci->kcj", m_own, tmp)
+
+
+def pre_order_given(t, pre_top, post, mats):
+    """the recursion below the top interior node from columns and matrices AS GIVEN (a `Division`'s own float64 ones, or what an
+    engine holds, read back): {node: un-normalised pre-order partials [K][P][S]}"""
+    pre = {t.root_left: pre_top}
+    for p in reversed(t.int_down_pass):
+        for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
+            pre[n] = pre_operation(pre[p], mats[n], post[sib], mats[sib])
+    return pre
+
+
 def pre_order(div, post, mats):
     """un-normalised pre-order partials [K][P][S] of every node below the root tip"""
     t = div.tree
     pi = np.asarray(div.pi, dtype=np.float64)
     top = t.root_left
-    pre = {top: np.einsum("kij,ci->kcj", mats[top], pi[None, :] * tip_vector(div, t.root))}
-    for p in reversed(t.int_down_pass):
-        for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
-            tmp = pre[p] * np.einsum("kij,kcj->kci", mats[sib], post[sib])
-            pre[n] = np.einsum("kij,kci->kcj", mats[n], tmp)
-    return pre
+    return pre_order_given(t, np.einsum("kij,ci->kcj", mats[top], pi[None, :] * tip_vector(div, t.root)), post, mats)
+
+
+def lnl_posteriors(w, pi, parent, matrix=None, child=None):
+    """q [K][P] of a log-likelihood call on operands as given (child None: a root call), and its per-category sums
+    l_k(c) = w_k sum_i pi_i parent[k,c,i] sum_j matrix[k,i,j] child[k,c,j]; a pattern without likelihood: q = 0"""
+    f = parent if child is None else parent * np.einsum("kij,kcj->kci", matrix, child)
+    l = w[:, None] * np.einsum("i,kci->kc", pi, f)
+    L = l.sum(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(L > 0, l / L, 0.0), l
+
+
+def edge_terms(pre, post, D):
+    """per category and pattern [K][P], from columns and a (differential) matrix as given:
+    N = sum_l pre[l] sum_j D[l,j] post[j], A the same with |D|, den = sum_l pre[l] post[l]"""
+    N = np.einsum("kcl,klj,kcj->kc", pre, D, post)
+    A = np.einsum("kcl,klj,kcj->kc", pre, np.abs(D), post)
+    return N, A, np.einsum("kcl,kcl->kc", pre, post)
+
+
+def mixed(q, num, den):
+    """sum_k q_k num_k / den_k over the categories with a denominator [P] -- the read-outs' form (include/libhmsbeagle/beagle.h): a
+    category whose den is zero carries nothing.  With q_k = w_k den_k / sum w den (one tree, seen from any branch) this is
+    (sum_k w_k num_k) / (sum_k w_k den_k), the N_c / L_c of the module docstring."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, q * num / den, 0.0).sum(0)
 
 
 def rate_matrix(div):
@@ -101,11 +141,7 @@ def reference(states, ncat, npat, ntaxa=NTAXA):
     w, pi = div.category_weights(0), np.asarray(div.pi, dtype=np.float64)
     D = np.asarray(div.cat_rates, dtype=np.float64)[:, None, None] * rate_matrix(div)[None, :, :]
     top = t.root_left
-    pre = {top: np.einsum("kij,ci->kcj", mats[top], pi[None, :] * tip_vector(div, t.root))}
-    for p in reversed(t.int_down_pass):
-        for n, sib in ((t.left[p], t.right[p]), (t.right[p], t.left[p])):
-            tmp = pre[p] * np.einsum("kij,kcj->kci", mats[sib], post[sib])
-            pre[n] = np.einsum("kij,kci->kcj", mats[n], tmp)
+    pre = pre_order(div, post, mats)
     res = {"nodes": list(t.all_down_pass), "lengths": lengths}
     dmax = max(depth_of(t, n) for n in range(t.ntaxa) if n != t.root)
     res["h"] = (dmax - 1) + dmax

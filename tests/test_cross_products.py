@@ -138,7 +138,7 @@ def cross_indices(bd, nodes):
                 weights=[bd.cijkIndex[0]] * len(nodes))
 
 
-def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
+def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
     div = division(states, ncat, npat, ntaxa)
     ref = reference(states, ncat, npat, ntaxa)
     gref = gradient_reference(states, ncat, npat, ntaxa)
@@ -147,7 +147,7 @@ def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
     f = bound_factor(div, ref, u)
     nodes = ref["nodes"]
     lengths = [ref["lengths"][n] for n in nodes]
-    bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, pre_order=True)
+    bd = lk.BeagleDivision(div, lib, scaling=scaling, double_precision=double_precision, pre_order=True)
     try:
         inst = bd.inst
         name = inst.details.implName.decode()

@@ -78,14 +78,14 @@ def interior_edge_indices(bd):
 
 
 # ---- the per-case check -----------------------------------------------------------------------------------------------------
-def check_case(lib, states, ncat, npat, double_precision=False, interior_child=False):
+def check_case(lib, states, ncat, npat, double_precision=False, interior_child=False, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
     div = make_division(states, ncat, npat)
     t = div.tree
     ref = reference(states, ncat, npat, interior=interior_child)
     S, tl = div.nstates, ref["t"]
     u = U64 * kappa(div, tl) if double_precision else U32
     um = U64 if double_precision else U32                   # the matrices: the bound is on the spectral terms themselves
-    bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision)
+    bd = lk.BeagleDivision(div, lib, scaling=scaling, double_precision=double_precision)
     try:
         inst = bd.inst
         name = inst.details.implName.decode()

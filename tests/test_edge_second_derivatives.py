@@ -154,11 +154,11 @@ def gradient_of(ix):
     return dict(posts=ix["posts"], pres=ix["pres"], dmats=ix["dmats1"], weights=ix["weights"])
 
 
-def new_division(lib, div, double_precision=False):
-    return lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, second_order=True)
+def new_division(lib, div, double_precision=False, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
+    return lk.BeagleDivision(div, lib, scaling=scaling, double_precision=double_precision, second_order=True)
 
 
-def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
+def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
     div = division(states, ncat, npat, ntaxa)
     ref = reference(states, ncat, npat, ntaxa)
     g = ref["g"]
@@ -167,7 +167,7 @@ def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
     mfma = matrix_core(states, double_precision)
     b = bounds(div, ref, u, mfma)
     nodes = ref["nodes"]
-    bd = new_division(lib, div, double_precision)
+    bd = new_division(lib, div, double_precision, scaling)
     try:
         inst = bd.inst
         name = inst.details.implName.decode()

@@ -86,8 +86,8 @@ def node_indices(bd):
     return dict(posts=[bd.condLikeIndex[0][n] for n in nodes], pres=[bd.preOrderIndex[n] for n in nodes], weights=[bd.cijkIndex[0]] * len(nodes))
 
 
-def new_division(lib, div, double_precision=False):
-    return lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, pre_order=True)
+def new_division(lib, div, double_precision=False, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
+    return lk.BeagleDivision(div, lib, scaling=scaling, double_precision=double_precision, pre_order=True)
 
 
 def observed(div, n):
@@ -106,13 +106,13 @@ def worst_ratio(got, want, bound):
 
 
 # ---- 1. values, 2. best states, 3. tips -------------------------------------------------------------------------------------------
-def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
+def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
     div = division(states, ncat, npat, ntaxa)
     ref = reference(states, ncat, npat, ntaxa)
     t, S, w = div.tree, div.nstates, div.weights
     f = rel_error(div, ref, unit_roundoff(div, ref["g"], double_precision))
     nodes = ref["nodes"]
-    bd = new_division(lib, div, double_precision)
+    bd = new_division(lib, div, double_precision, scaling)
     try:
         inst = bd.inst
         name = inst.details.implName.decode()

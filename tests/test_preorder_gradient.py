@@ -80,13 +80,13 @@ def test_reference_against_finite_differences():
 
 
 # ---- the per-case check -------------------------------------------------------------------------------------------------------
-def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA):
+def check_case(lib, states, ncat, npat, double_precision=False, ntaxa=NTAXA, scaling=lk.MB_BEAGLE_SCALE_ALWAYS):
     div = division(states, ncat, npat, ntaxa)
     ref = reference(states, ncat, npat, ntaxa)
     t, S, w = div.tree, div.nstates, div.weights
     u = unit_roundoff(div, ref, double_precision)
     b = bounds(div, ref, u)
-    bd = lk.BeagleDivision(div, lib, scaling=lk.MB_BEAGLE_SCALE_ALWAYS, double_precision=double_precision, pre_order=True)
+    bd = lk.BeagleDivision(div, lib, scaling=scaling, double_precision=double_precision, pre_order=True)
     try:
         inst = bd.inst
         name = inst.details.implName.decode()
