@@ -513,6 +513,32 @@ BEAGLE_DLLEXPORT int mbamdSetRateMatrices(int instance, int firstEigenIndex, int
  * of reference UpDateCijk, src/likelihood.c:10476-10804: integration/mrbayes/mbamd_eigen_glue.c). */
 BEAGLE_DLLEXPORT int mbamdSetRateMatricesFrom(int instance, int firstEigenIndex, int count, const double* q, const double* pi, int mode,
                                               int warmFirstEigenIndex);
+/* Transition matrices of ANY rate matrix, with no eigen-system: for every listed branch i and every category k, with r_k the
+ * instance's category rate (beagleSetCategoryRates), matrix buffer probabilityIndices[i] takes P_k = exp(Q r_k t_i) and, where the
+ * lists are given (either may be NULL, independently), firstDerivativeIndices[i] takes P'_k = r_k Q P_k and
+ * secondDerivativeIndices[i] takes P''_k = r_k Q P'_k -- ordinary, unclamped matrix buffers, as beagleUpdateTransitionMatrices
+ * fills them.  Computed on the device by uniformization with scaling and squaring: every quantity is non-negative,
+ * so no entry of P is negative, structural zeros of P are exact, and defective or non-reversible matrices (absorbing states,
+ * one-way chains, complex eigenvalues) are served like any other.  Asynchronous on the instance's stream.  Q travels with the call
+ * and is not stored: a client with several rate matrices calls once per matrix.
+ *   rateMatrix   S x S doubles, row-major.  Entries finite, off-diagonals >= 0, each diagonal minus its row's off-diagonal sum to
+ *                within S 2^-52 of that sum (what summing in double, in any order, can lose); else BEAGLE_ERROR_OUT_OF_RANGE.  The
+ *                engine then uses the off-diagonals only and forms the diagonal itself.  A Q of all zeros gives identities and
+ *                zero derivatives.
+ *   edgeLengths  t_i finite and >= 0, and mu r_k t_i <= 2^20 for every k, mu = max_i sum_{j != i} q_ij; else
+ *                BEAGLE_ERROR_OUT_OF_RANGE (as for a category rate that is negative or not finite).  t = 0 or r_k = 0.0 gives
+ *                P = I exactly, P' = r_k Q and P'' = r_k^2 Q^2 rounded once -- exact zeros for r_k = 0.0.
+ *   indices      BEAGLE_ERROR_OUT_OF_RANGE for an index outside the matrix buffers, for a NULL rateMatrix, probabilityIndices or
+ *                edgeLengths with count > 0, for a negative count, and for an output index that occurs twice among the three
+ *                lists.  count == 0 is a successful no-op.
+ * Everything is checked before anything is written: a refused call changes no matrix.  Served on both engines, on real and complex
+ * instances alike (no eigen buffer is read), on 2 ... 64 states, and on pattern-sharded instances (every shard computes its own
+ * copy); BEAGLE_ERROR_NO_IMPLEMENTATION on a multi-partition instance (beagleSetPatternPartitions).  The result is an ordinary
+ * matrix buffer: every copy the engine keeps is written, and nothing tells it from the same values given to
+ * beagleSetTransitionMatrix. */
+BEAGLE_DLLEXPORT int mbamdUpdateTransitionMatricesFromRateMatrix(int instance, const double* rateMatrix, const int* probabilityIndices,
+                                                                 const int* firstDerivativeIndices, const int* secondDerivativeIndices,
+                                                                 const double* edgeLengths, int count);
 /* The doubles of an eigen buffer read back (single-precision engine; waits for the instance's stream): outU, outUi S x S each,
  * outLambda S values -- what the matrix kernels read, whoever wrote them.  outV (may be NULL): the S x S orthonormal eigenvectors of
  * the symmetrised matrix that the device solver keeps for warm starts; BEAGLE_ERROR_OUT_OF_RANGE where the buffer was last written by

@@ -70,6 +70,7 @@ EXPORTS = [
     "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRangeSafeCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
+    "mbamdUpdateTransitionMatricesFromRateMatrix",
     # BEAGLE v3 surface (multi-partition instances, resource benchmark)
     "beagleGetBenchmarkedResourceList", "beagleSetCPUThreadCount", "beagleSetPatternPartitions",
     "beagleSetCategoryRatesWithIndex", "beagleUpdateTransitionMatricesWithMultipleModels", "beagleUpdatePartialsByPartition",
@@ -140,6 +141,7 @@ class BeagleLibrary:
         L.beagleConvolveTransitionMatrices.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int]
         L.beagleTransposeTransitionMatrices.argtypes = [C.c_int, _ip, _ip, C.c_int]
         L.beagleSetTransitionMatrices.argtypes = [C.c_int, _ip, _dp, _dp, C.c_int]
+        L.mbamdUpdateTransitionMatricesFromRateMatrix.argtypes = [C.c_int, _dp, _ip, _ip, _ip, _dp, C.c_int]
         L.beagleUpdatePartials.argtypes = [C.c_int, C.POINTER(BeagleOperation), C.c_int, C.c_int]
         L.beagleWaitForPartials.argtypes = [C.c_int, _ip, C.c_int]
         L.beagleAccumulateScaleFactors.argtypes = [C.c_int, _ip, C.c_int, C.c_int]
@@ -357,6 +359,18 @@ class BeagleInstance:
         a = _d(matrices).reshape(len(idx), self.category_count, self.state_count, self.state_count)
         self._chk(self.lib.beagleSetTransitionMatrices(self.id, idx.ctypes.data_as(_ip), a.ctypes.data_as(_dp), None, len(idx)),
                   "beagleSetTransitionMatrices")
+
+    def update_transition_matrices_from_rate_matrix(self, q, prob_indices, edge_lengths, first=None, second=None):
+        """P = exp(Q r_k t) of ANY rate matrix q [states][states] (non-reversible, defective: no eigen-system), on the device;
+        first / second: matrix buffers that take P' = r_k Q P and P'' = r_k Q P' (either may be None).  Asynchronous."""
+        a = _d(q).reshape(self.state_count, self.state_count)
+        p, e = _i(prob_indices), _d(edge_lengths)
+        d1, d2 = _opt_i(first), _opt_i(second)
+        if len(e) != len(p) or any(d is not None and len(d) != len(p) for d in (d1, d2)):
+            raise ValueError("update_transition_matrices_from_rate_matrix: the lists differ in length")
+        self._chk(self.lib.mbamdUpdateTransitionMatricesFromRateMatrix(self.id, a.ctypes.data_as(_dp), p.ctypes.data_as(_ip), _ptr(d1), _ptr(d2),
+                                                                       e.ctypes.data_as(_dp), len(p)),
+                  "mbamdUpdateTransitionMatricesFromRateMatrix")
 
     # ---- partials / scaling -----------------------------------------------------------------------
     def update_partials(self, operations, cumulative_scale_index=BEAGLE_OP_NONE):

@@ -737,6 +737,19 @@ int beagleSetTransitionMatrices(int instance, const int* matrixIndices, const do
     if (h->f64) return h->f64->setMatrices(matrixIndices, inMatrices, count);
     EACH_ENGINE(true, c->setMatrices(matrixIndices, inMatrices, count));
 }
+// exp(Q r_k t) of any rate matrix, no eigen-system read (mbamd_rate_exponential.h): every shard computes its own copy
+int mbamdUpdateTransitionMatricesFromRateMatrix(int instance, const double* rateMatrix, const int* probabilityIndices,
+                                                const int* firstDerivativeIndices, const int* secondDerivativeIndices,
+                                                const double* edgeLengths, int count)
+{
+    StatTimer st_(ST_MATRICES);
+    GET_INSTANCE(instance);
+    const char* who = "mbamdUpdateTransitionMatricesFromRateMatrix";
+    API_TRACE("%s(count=%d)", who, count);
+    if (h->f64) return h->f64->updateMatricesFromRateMatrix(rateMatrix, probabilityIndices, firstDerivativeIndices, secondDerivativeIndices, edgeLengths, count);
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    EACH_ENGINE(true, c->updateMatricesFromRateMatrix(rateMatrix, probabilityIndices, firstDerivativeIndices, secondDerivativeIndices, edgeLengths, count));
+}
 int beagleUpdatePartials(int instance, const BeagleOperation* operations, int operationCount, int cumulativeScaleIndex)
 {
     StatTimer st_(ST_PARTIALS);

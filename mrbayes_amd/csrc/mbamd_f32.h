@@ -24,6 +24,7 @@
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges: a draw of all ancestral states from their joint posterior
 #include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
+#include "mbamd_rate_exponential.h" // k_rate_exp_*: exp(Q t) of any rate matrix, no eigen-system
 
 namespace mbamd {
 
@@ -171,6 +172,7 @@ struct Instance {
     int convolveMatrices(const int* first, const int* second, const int* result, int count);
     int transposeMatrices(const int* input, const int* result, int count);
     int setMatrices(const int* idx, const double* in, int count);
+    int updateMatricesFromRateMatrix(const double* q, const int* prob, const int* d1, const int* d2, const double* lengths, int count);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
     int flushPending(bool keepPath = false);
     // scale buffers, whichever of their forms holds them (ScaleStore): the range checks and the scheduling around the store's calls
@@ -403,6 +405,7 @@ private:
     template <class E> friend int autocorrelated_run(E&, const HmmSource*, int, int, const int*, const int*, int, const double*, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
+    template <class E> friend int rate_exponential_run(E&, const char*, const double*, const int*, const int*, const int*, const double*, int);
     // everything queued or held runs first
     int runQueued() { return hasWork() ? flushPending() : BEAGLE_SUCCESS; }
     // ---- ... and the bodies of the matrix-product calls (mbamd_matrix_products.h) ----
@@ -1411,6 +1414,10 @@ inline int Instance::transposeMatrices(const int* input, const int* result, int 
     return matrix_list_run(*this, "beagleTransposeTransitionMatrices", false, input, (const int*) nullptr, result, count);
 }
 inline int Instance::setMatrices(const int* idx, const double* in, int count) { return matrix_list_set(*this, "beagleSetTransitionMatrices", idx, in, count); }
+inline int Instance::updateMatricesFromRateMatrix(const double* q, const int* prob, const int* d1, const int* d2, const double* lengths, int count)
+{
+    return rate_exponential_run(*this, "mbamdUpdateTransitionMatricesFromRateMatrix", q, prob, d1, d2, lengths, count);
+}
 
 inline int Instance::getMatrix(int idx, double* out)
 {

@@ -34,6 +34,7 @@
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges <DERIV_F64, double>: a draw of all ancestral states from their joint posterior
 #include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF64
+#include "mbamd_rate_exponential.h" // k_rate_exp_*: exp(Q t) of any rate matrix, no eigen-system
 
 namespace mbamd {
 
@@ -69,6 +70,7 @@ public:
     int convolveMatrices(const int* first, const int* second, const int* result, int count);
     int transposeMatrices(const int* input, const int* result, int count);
     int setMatrices(const int* idx, const double* in, int count);
+    int updateMatricesFromRateMatrix(const double* q, const int* prob, const int* d1, const int* d2, const double* lengths, int count);
     int updatePartials(const BeagleOperation* ops, int n, int cumIdx);
     // (operations `stride` bytes apart, queued: see the definition)
     int updatePartialsEx(const void* opsRaw, size_t stride, int n, const int* partition, const int* cumOf);
@@ -189,6 +191,7 @@ private:
     template <class E> friend int autocorrelated_run(E&, const HmmSource*, int, int, const int*, const int*, int, const double*, double*, double*);
     template <class E> friend int matrix_list_run(E&, const char*, bool, const int*, const int*, const int*, int);
     template <class E> friend int matrix_list_set(E&, const char*, const int*, const double*, int);
+    template <class E> friend int rate_exponential_run(E&, const char*, const double*, const int*, const int*, const int*, const double*, int);
     // everything queued runs first
     int runQueued() { return flushQueue(); }
     // ---- ... and the bodies of the matrix-product calls (mbamd_matrix_products.h) ----
@@ -620,6 +623,10 @@ inline int Engine64::transposeMatrices(const int* input, const int* result, int 
     return matrix_list_run(*this, "beagleTransposeTransitionMatrices", false, input, (const int*) nullptr, result, count);
 }
 inline int Engine64::setMatrices(const int* idx, const double* in, int count) { return matrix_list_set(*this, "beagleSetTransitionMatrices", idx, in, count); }
+inline int Engine64::updateMatricesFromRateMatrix(const double* q, const int* prob, const int* d1, const int* d2, const double* lengths, int count)
+{
+    return rate_exponential_run(*this, "mbamdUpdateTransitionMatricesFromRateMatrix", q, prob, d1, d2, lengths, count);
+}
 inline int Engine64::getMatrix(int idx, double* out)
 {
     { const int rcq = flushQueue(); if (rcq) return rcq; }
