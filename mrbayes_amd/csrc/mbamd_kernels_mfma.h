@@ -21,7 +21,7 @@
 // The per-pattern maximum over (k, i) -- the reference's separate CondLikeScaler pass -- is fused
 // (register reduction + LDS exchange), and the rescaled result is written exactly once.
 //
-// Kernels (the host picks per operation list, Instance::runGeneric / flushPending in mbamd_f32.h):
+// Kernels (the host picks per operation list, Instance::runGeneric / flushMerged in mbamd_f32_levels.h):
 //   k_partials_tips        operations on two compact tips (a full evaluation's first dependency level)
 //   k_partials_mfma_split  one launch per dependency level, one wave per factor tile (the default)
 //   k_partials_mfma_spine  narrow lists / trailing single-operation levels: one launch walks them, software-pipelined

@@ -60,7 +60,7 @@ namespace mbamd {
 #define MBAMD_W4_NEXT_READS 0x04000000u  // the NEXT entry of this wave is SCALE_READ: fetch its stored exponents now (4-state walk; set by the host)
 // A SMALL SUBTREE (compact tips alone below it: a tip pair, or three or four tips, MBAMD_UNSTORED_TIPS) of a whole-tree list on the plain instantiation: the 1 KiB result is NOT stored -- its parent reads
 // the LDS slot or the forwarding registers, and it is a pure function of 64 bytes of tip planes and two matrices: whoever needs it later has
-// it recomputed (the host keeps a recipe and a snapshot of the matrices, Instance::ensureStored).  Exponent byte, slot, cum_e: as ever.
+// it recomputed (the host keeps a recipe and a snapshot of the matrices, Walk4Unstored::ensureStored, mbamd_walk4_unstored.h).  Exponent byte, slot, cum_e: as ever.
 // Honoured by k_walk4_t<Walk4Args, true> (one wave or several: a flagged result whose parent runs on another wave reaches it through its
 // slot like any value that crosses) only; the host sets it nowhere else.
 #define MBAMD_W4_NOSTORE  0x20000000u

@@ -1,7 +1,7 @@
 """Subtrees of up to four compact tips that a whole-tree launch of the plain 4-state walk kernel does not store (MBAMD_UNSTORED_TIPS,
 MBAMD_W4_NOSTORE in mbamd_walk4.h): beside the tip pairs of test_walk4_tip_pairs.py, a subtree of three or four tips keeps a recipe that
 stands alone -- its tips, its two or three operations with their scale modes, a snapshot of all its matrices -- and is recomputed by one
-launch of the plain instantiation before the first call that reads it (Instance::ensureStored, mbamd_f32.h); its inner results land
+launch of the plain instantiation before the first call that reads it (Walk4Unstored::ensureStored, mbamd_walk4_unstored.h); its inner results land
 nowhere.
 
   * CPU (`not gpu`): the host-emulation build of the same sources;

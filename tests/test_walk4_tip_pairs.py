@@ -1,6 +1,6 @@
 """Tip pairs that a whole-tree launch of the plain 4-state walk kernel does not store (MBAMD_W4_NOSTORE, mbamd_walk4.h): the buffer
 keeps a recipe -- its two compact tips, its scale mode, a snapshot of its two matrices -- and is recomputed by one launch of the
-generic kernel before the first call that reads it (Instance::ensureStored, mbamd_f32.h).
+generic kernel before the first call that reads it (Walk4Unstored::ensureStored, mbamd_walk4_unstored.h).
 
   * CPU (`not gpu`): the host-emulation build of the same sources;
   * GPU (`gpu`): the product library on a MI355X.
