@@ -173,6 +173,11 @@ inline int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, cons
     // the operation of this list that writes them, a second writer after the first writer and all its readers
     std::unordered_map<const void*, std::pair<int, int>> scaleLevels;     // scale buffer -> (last write level, last read level)
     int nLevels = 0;
+    // The serial kernels (k_partials_mfma_serial / _spine) fetch an operation's operands -- the exponents a SCALE_READ divides by
+    // among them -- while the operation before it computes and the writer wave still stores the one before that: partials of
+    // the last two results are forwarded through LDS, exponents are not.  A list in which an operation reads the exponents an
+    // earlier operation of the list writes (MrBayes never sends one) therefore runs level by level: a launch boundary orders them.
+    bool scaleForward = false;
     for (int o = 0; o < n; ++o) {
         int l = 0;
         l = std::max(l, lastWrite[c1Idx[o]] + 1);
@@ -182,6 +187,7 @@ inline int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, cons
         if (dev[o].scale_mode != SCALE_NONE) {
             auto it = scaleLevels.find(dev[o].scale);
             if (it != scaleLevels.end()) {
+                if (dev[o].scale_mode == SCALE_READ && it->second.first >= 0) scaleForward = true;
                 l = std::max(l, it->second.first + 1);
                 if (dev[o].scale_mode == SCALE_WRITE) l = std::max(l, it->second.second + 1);
             }
@@ -210,7 +216,7 @@ inline int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, cons
     plan.anyScale = false;
     for (const PartialsOp& d : sorted) plan.anyScale |= d.scale_mode != SCALE_NONE;
     plan.start = start;
-    plan.narrow = serialRatio > 0 && n <= serialRatio * nLevels;
+    plan.narrow = serialRatio > 0 && !scaleForward && n <= serialRatio * nLevels;
     // Independent sub-lists.  A list often is several root-ward paths interleaved (MrBayes puts the operations of all
     // eigen-system parts of a codon model into one list, reference src/mbbeagle.c:1029-1100).  chainsOf() splits a
     // subset of the list (original indices, list order) into connected components of the "touches a buffer a member
@@ -269,7 +275,7 @@ inline int Instance::buildGeneric(Plan& plan, std::vector<PartialsOp>& dev, cons
         const auto bins = chainsOf(all);
         if (bins.size() > 1) appendBins(bins, plan.chains);
         else plan.chains.emplace_back(0, n);
-    } else if (serialRatio > 0) {
+    } else if (serialRatio > 0 && !scaleForward) {
         // the tail of a level-launched list: trailing levels of a few operations each.  If they fall apart into parallel
         // chains (three codon parts -> three chains) one serial launch walks them side by side; otherwise only the
         // strictly single-operation levels (the spine towards the root) go serial.
