@@ -427,6 +427,40 @@ BEAGLE_DLLEXPORT int beagleCalculateCrossProductDerivative(int instance, const i
                                                            const int* categoryRateIndices, const int* categoryWeightsIndices,
                                                            const double* edgeLengths, int count, double* outSumDerivatives,
                                                            double* outSumSquaredDerivatives);
+/* The gradient in the SITE MODEL (an engine extension: upstream has no such call): the rate of every category, the weight of every
+ * category and the direct term of the state frequencies at the root -- the gamma shape, FreeRate's rates and weights, a zero-rate
+ * "+I" category, pi -- from the buffers the branch-length gradient reads.  Edge e = 0 .. count-1 names its buffers and its
+ * differential matrix D = derivativeMatrixIndices[e] exactly as beagleCalculateEdgeDerivatives does; q_k(c), den, compact tips,
+ * missing states, skipped categories and the power of two taken out of post-order columns are those of that call.  With K the
+ * category count, S the state count and weight_c the pattern weights:
+ *     den_k(c)   = sum_l pre_e[k,c,l] post_e[k,c,l]
+ *     g_e,k(c)   = (sum_l pre_e[k,c,l] sum_j D_k[l,j] post_e[k,c,j]) / den_k(c)
+ *     outEdgeCategoryDerivatives[e * K + k] = sum_c weight_c q_k(c) g_e,k(c)           (a category with den <= 0 is skipped)
+ *     outRateDerivatives[k] = sum_e edgeLengths[e] outEdgeCategoryDerivatives[e * K + k]     (the edges in their order, in double)
+ *     outCategoryCounts[k]  = sum_c weight_c q_k(c)                                    the expected number of sites in category k
+ *     outRootFrequencyDerivatives[i] = sum_c weight_c sum_k q_k(c) parent[k,c,i] f_k(c,i) / sum_l pi_l parent[k,c,l] f_k(c,l)
+ * each of the four may be NULL (all four: BEAGLE_ERROR_OUT_OF_RANGE), and each is the same, bit for bit, whichever others are asked
+ * for.  With D_k = Q for every k (UNIT rate) outRateDerivatives[k] is exactly d lnL / d r_k, r_k the rate of category k -- also
+ * where r_k = 0, there is no division by a rate; with D_k = r_k Q the sum over k of outEdgeCategoryDerivatives[e * K + k] is
+ * beagleCalculateEdgeDerivatives' outSumDerivatives[e].  d lnL / d w_k is outCategoryCounts[k] / w_k, w_k the category weights
+ * (one category: q = 1, the count is sum_c weight_c).  In the root term parent, pi and f_k are the operands of the latest
+ * beagleCalculate{Root,Edge}LogLikelihoods call as they are now: f_k = 1 for a root call, f_k(c,i) = sum_j P_k[i,j] child[k,c,j]
+ * for an edge call; a category whose denominator is not positive is skipped.  It is d lnL / d pi_i at FIXED Q -- the direct
+ * term only, the term through Q is beagleCalculateCrossProductDerivative's -- and has no division by pi_i: pi_i = 0 is served.
+ * Every scale of every buffer cancels inside its (pattern, category) ratio.  MrBayes' host-side pInvar mixing stays outside, as
+ * for the other calls of this family.
+ * The rules of beagleCalculateEdgeDerivatives on the latest log-likelihood call, on categoryWeightsIndices, on pre-order buffers,
+ * on multi-partition instances (BEAGLE_ERROR_NO_IMPLEMENTATION), on NULL index arrays and on indices out of range hold unchanged,
+ * with its statuses.  edgeLengths may be NULL only if outRateDerivatives is; a length that is negative or not finite is
+ * BEAGLE_ERROR_OUT_OF_RANGE.  outRootFrequencyDerivatives needs a log-likelihood call even with one category
+ * (BEAGLE_ERROR_GENERAL without, as mbamdSampleAncestralStates answers); with one category and that output NULL none is needed.
+ * count == 0 is legal: outRateDerivatives is zeros, the counts and the root term are computed.  A refused call writes nothing.
+ * The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdCalculateSiteModelDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices,
+                                                        const int* derivativeMatrixIndices, const int* categoryWeightsIndices,
+                                                        const double* edgeLengths, int count, double* outEdgeCategoryDerivatives,
+                                                        double* outRateDerivatives, double* outCategoryCounts,
+                                                        double* outRootFrequencyDerivatives);
 
 /* ---------------------------------------------------------------------------------------------
  * engine extensions (not part of the upstream API; used by bench.py / the multi-GPU driver)

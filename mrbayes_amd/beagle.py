@@ -66,7 +66,7 @@ EXPORTS = [
     "beagleAccumulateScaleFactors", "beagleRemoveScaleFactors", "beagleResetScaleFactors", "beagleCopyScaleFactors",
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
-    "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateEdgeSecondDerivatives",
+    "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateSiteModelDerivatives", "mbamdCalculateEdgeSecondDerivatives",
     "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRangeSafeCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
@@ -158,6 +158,7 @@ class BeagleLibrary:
         L.beagleSetDifferentialMatrix.argtypes = [C.c_int, C.c_int, _dp]
         L.beagleCalculateEdgeDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp]
         L.beagleCalculateCrossProductDerivative.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp]
+        L.mbamdCalculateSiteModelDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp, _dp, _dp]
         L.mbamdCalculateEdgeSecondDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp]
         L.mbamdGetSecondDerivativeLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdCalculateNodePosteriors.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, _dp, _ip, _dp, _dp]
@@ -571,6 +572,24 @@ class BeagleInstance:
                                                             sq.ctypes.data_as(_dp) if squared else None)
         self._chk(rc, "beagleCalculateCrossProductDerivative")
         return rc, x
+
+    def calculate_site_model_derivatives(self, posts, pres, dmats, weights, edge_lengths=None, edges=True, rates=True, counts=True, root=True):
+        """The gradient in the site model over every listed branch in one call (mbamdCalculateSiteModelDerivatives): dmats name the
+        differential matrices (unit rate, D_k = Q, for d lnL / d r_k).  Returns (rc, per edge and category [count][categories],
+        d lnL / d r_k [categories], expected sites per category [categories], d lnL / d pi_i at fixed Q [states]) -- each None unless
+        asked for; `rates` needs edge_lengths.  An error code raises."""
+        po, pr, dm, w = _i(posts), _i(pres), _i(dmats), _i(weights)
+        t = None if edge_lengths is None else _d(edge_lengths)
+        n, K, S = len(po), self.category_count, self.state_count
+        per = np.empty((n, K)) if edges else None
+        r = np.empty(K) if rates else None
+        c = np.empty(K) if counts else None
+        f = np.empty(S) if root else None
+        dptr = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        rc = self.lib.mbamdCalculateSiteModelDerivatives(self.id, po.ctypes.data_as(_ip), pr.ctypes.data_as(_ip), dm.ctypes.data_as(_ip),
+                                                         w.ctypes.data_as(_ip), dptr(t), n, dptr(per), dptr(r), dptr(c), dptr(f))
+        self._chk(rc, "mbamdCalculateSiteModelDerivatives")
+        return rc, per, r, c, f
 
     # ---- BEAGLE v3: multi-partition instances (reference src/mbbeagle.c:1500-3010) -------------------------------
     def child_count(self) -> int:

@@ -1259,6 +1259,59 @@ int beagleCalculateCrossProductDerivative(int instance, const int* postBufferInd
     return BEAGLE_SUCCESS;
 }
 
+// the gradient in category rates, category weights and root frequencies (mbamd_site_model.h; semantics: beagle.h)
+int mbamdCalculateSiteModelDerivatives(int instance, const int* postBufferIndices, const int* preBufferIndices, const int* derivativeMatrixIndices,
+                                       const int* categoryWeightsIndices, const double* edgeLengths, int count,
+                                       double* outEdgeCategoryDerivatives, double* outRateDerivatives, double* outCategoryCounts,
+                                       double* outRootFrequencyDerivatives)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdCalculateSiteModelDerivatives(count=%d%s%s%s%s)", count, outEdgeCategoryDerivatives ? ", per edge" : "",
+              outRateDerivatives ? ", rates" : "", outCategoryCounts ? ", counts" : "", outRootFrequencyDerivatives ? ", root" : "");
+    const char* const who = "mbamdCalculateSiteModelDerivatives";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!postBufferIndices || !preBufferIndices || !derivativeMatrixIndices || !categoryWeightsIndices)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    if (!outEdgeCategoryDerivatives && !outRateDerivatives && !outCategoryCounts && !outRootFrequencyDerivatives)
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "every output is null");
+    if (outRateDerivatives) {
+        if (!edgeLengths) return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "edgeLengths is null and outRateDerivatives is not");
+        const int rc = cross_check_lengths(who, edgeLengths, count);
+        if (rc) return rc;
+    }
+    // one array for what the engines return: G [count][K] (also behind the rates), then the counts [K], then the root term [S]
+    const size_t K = (size_t) h->dim.categoryCount, S = (size_t) h->dim.stateCount;
+    const size_t nEdge = outEdgeCategoryDerivatives || outRateDerivatives ? (size_t) count * K : 0, nCounts = outCategoryCounts ? K : 0;
+    const size_t n = nEdge + nCounts + (outRootFrequencyDerivatives ? S : 0);
+    const bool edges = outEdgeCategoryDerivatives || outRateDerivatives;
+    std::vector<double> sum;
+    auto call = [&](auto* engine, double* part) {
+        return engine->siteModelDerivatives(postBufferIndices, preBufferIndices, derivativeMatrixIndices, categoryWeightsIndices, count,
+                                            edges ? part : nullptr, outCategoryCounts ? part + nEdge : nullptr,
+                                            outRootFrequencyDerivatives ? part + nEdge + nCounts : nullptr);
+    };
+    int rc;
+    if (h->f64) {
+        sum.assign(n, 0.0);
+        rc = call(h->f64.get(), sum.data());
+    } else {
+        // pattern shards: the children's sums are added, in child order
+        rc = each_engine_sum(h, n, sum, [&](Instance* c, const Handle::Span&, double* part) { return call(c, part); });
+    }
+    if (rc) return rc;
+    if (outEdgeCategoryDerivatives) std::copy(sum.begin(), sum.begin() + nEdge, outEdgeCategoryDerivatives);
+    if (outRateDerivatives)
+        for (size_t k = 0; k < K; ++k) {
+            double r = 0.0;
+            for (int e = 0; e < count; ++e) r += edgeLengths[e] * sum[(size_t) e * K + k];
+            outRateDerivatives[k] = r;
+        }
+    if (outCategoryCounts) std::copy(sum.begin() + nEdge, sum.begin() + nEdge + nCounts, outCategoryCounts);
+    if (outRootFrequencyDerivatives) std::copy(sum.end() - S, sum.end(), outRootFrequencyDerivatives);
+    return BEAGLE_SUCCESS;
+}
+
 // ---- engine extensions ---------------------------------------------------------------------
 int mbamdSynchronize(int instance)
 {

@@ -31,6 +31,7 @@
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges: a draw of all ancestral states from their joint posterior
+#include "mbamd_site_model.h"    // k_edge_category_readout, k_root_frequency_readout: the gradient in category rates, weights and root frequencies
 #include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
 #include "mbamd_matrix_products.h" // k_matrix_products_*, k_matrix_transpose: matrices made out of matrices; MatrixLayoutF32
 #include "mbamd_rate_exponential.h" // k_rate_exp_*: exp(Q t) of any rate matrix, no eigen-system
@@ -110,6 +111,10 @@ struct Instance {
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
                        size_t siteStride, double* sums);
     int categoryPosteriors(int wIdx, double* out, size_t stride);
+    // siteModelDerivatives (mbamdCalculateSiteModelDerivatives on this engine's patterns; mbamd_site_model.h): synchronous; edgeCat
+    // [count][K], counts [K], rootFreq [S], each or null
+    int siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat, double* counts,
+                             double* rootFreq);
     // sampleAncestralStates (mbamdSampleAncestralStates on this engine's patterns; mbamd_ancestral_sampling.h): synchronous;
     // patternOffset = the index in the instance of this engine's pattern 0, states at [slot * stride + c], changes[i] never null
     int sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
@@ -306,6 +311,7 @@ private:
     template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
+    template <class E> friend int site_model_derivatives(E&, const int*, const int*, const int*, const int*, int, double*, double*, double*);
     template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
     template <class E> friend int autocorrelated_prepare(E&, int, HmmSource&);
     template <class E> friend int autocorrelated_weights(E&, int, double*);
@@ -1554,6 +1560,11 @@ inline int Instance::nodePosteriors(const int* post, const int* pre, const int* 
     return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, siteStride, sums);
 }
 inline int Instance::categoryPosteriors(int wIdx, double* out, size_t stride) { return category_posteriors(*this, wIdx, out, stride); }
+inline int Instance::siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat,
+                                          double* counts, double* rootFreq)
+{
+    return site_model_derivatives(*this, post, pre, dmat, wIdx, count, edgeCat, counts, rootFreq);
+}
 inline int Instance::sampleAncestralStates(const int* parentSlots, const int* post, const int* matrices, int count, int wIdx, unsigned long long seed,
                                            long long patternOffset, int* states, int* categories, double* changes, size_t stride)
 {

@@ -46,7 +46,7 @@ struct Switches {
     bool eigen256 = false;                 // MBAMD_EIGEN_256: the device eigen-solver on 256 threads at every state count
     bool xprodGeneric = false;             // MBAMD_XPROD_GENERIC: cross products of 16 ... 64 states on the plain kernel instead of the matrix-core one
     bool curvGeneric = false;              // MBAMD_CURV_GENERIC: second derivatives of 16 ... 64 states on the plain kernel instead of the matrix-core one
-    std::optional<int> posteriorNodes;     // MBAMD_POSTERIOR_NODES=<n>: at most n nodes per launch of mbamdCalculateNodePosteriors (test only: a chunk boundary at a small shape)
+    std::optional<int> posteriorNodes;     // MBAMD_POSTERIOR_NODES=<n>: at most n nodes per launch of mbamdCalculateNodePosteriors, or edges of mbamdCalculateSiteModelDerivatives (test only: a chunk boundary at a small shape)
     std::optional<int> samplePatterns;     // MBAMD_SAMPLE_PATTERNS=<n>: at most n patterns in flight in mbamdSampleAncestralStates (test only: several pattern ranges at a small shape)
     // ---- A/B references used by tests: the parsimony scorer
     std::optional<int> parsPhaseLimit;     // MBAMD_PARS_PHASE_LIMIT=<n>: phases per launch of the parsimony walk

@@ -505,6 +505,23 @@ class BeagleDivision:
         curv = {n: (float(sums1[i]), float(sums2[i])) for i, n in enumerate(nodes)}
         return (curv, {n: (per1[i], per2[i]) for i, n in enumerate(nodes)}) if sites else curv
 
+    def SiteModelGradient(self, chain=0):
+        """(d lnL / d r_k [categories], expected sites per category [categories], d lnL / d pi_i at fixed Q [states]) of the
+        chain's current tree, after LogLike and BranchGradient (whose pre-order buffers it reads): the UNIT-rate differential
+        matrix D_k = Q goes where BranchGradient keeps r_k Q (BranchGradient sets its own again), and ONE
+        calculate_site_model_derivatives call reads every branch.  d lnL / d w_k is the count divided by the category weight; the
+        chain rule to a gamma shape or a constrained parameterisation is the client's."""
+        if not self.pre_order:
+            raise ValueError("SiteModelGradient needs BeagleDivision(..., pre_order=True)")
+        d, t = self.div, self.div.tree
+        self.inst.set_differential_matrix(self.diffMatrixIndex, np.broadcast_to(self._RateMatrix(), (d.ncat, d.nstates, d.nstates)))
+        nodes = list(t.all_down_pass)
+        lengths = [min(max(t.length[n], BRLENS_MIN), BRLENS_MAX) for n in nodes]
+        rc, _, rates, counts, root = self.inst.calculate_site_model_derivatives(
+            self._EdgePosts(chain, nodes), self._EdgePres(nodes), [self.diffMatrixIndex] * len(nodes), [self.cijkIndex[chain]] * len(nodes),
+            lengths, edges=False)
+        return rates, counts, root
+
     def NodePosteriors(self, chain=0, sites=False, best=False):
         """{node: expected number of sites in every state [states]} for the lower end of all 2N-3 branches of the chain's current
         tree (every interior node and every tip but the root tip), after LogLike: the pre-order pass of BranchGradient, then ONE

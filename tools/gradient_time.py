@@ -21,7 +21,11 @@ branches at 157.3 TFLOP/s.
 A fourth line times ONE mbamdCalculateNodePosteriors call over the same (post-order, pre-order) pairs (the posterior of every state at
 every node) without per-pattern outputs, ALTERNATING with the first-derivative call, against the same byte model: the
 call reads the same two buffers per node and has no matrix; then with best states only, alternating with the first-derivative call
-that returns its per-site values (count x patterns results cross the host link in both)."""
+that returns its per-site values (count x patterns results cross the host link in both).
+
+A fifth line times ONE mbamdCalculateSiteModelDerivatives call over the same branches with a unit-rate differential matrix (the
+gradient in category rates, category weights and root frequencies) -- all outputs but the per-edge values, and the
+rates alone --, ALTERNATING with the first-derivative call, against the same byte model: the edge part reads the same two buffers."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -157,5 +161,30 @@ try:
           (case, len(nodes), psum, min(sums_ms), max(sums_ms), model_read, 100.0 * model_read / psum, first, min(first_ms), max(first_ms),
            100.0 * model_read / first, out_mib, pbest, min(best_ms), max(best_ms), out_mib * 2.0 / 3.0, first2, min(first2_ms), max(first2_ms),
            float(np.abs(psums.sum(1) - float(np.asarray(div.weights, dtype=np.float64).sum())).max())))
+    inst.set_differential_matrix(bd.diffMatrix2Index, np.broadcast_to(Q, (div.ncat, S, S)))           # (unit rate: D_k = Q)
+    mx = dict(posts=ix["posts"], pres=ix["pres"], dmats=[bd.diffMatrix2Index] * len(nodes), weights=ix["weights"], edge_lengths=lengths)
+    rc, _, expect, _, _ = inst.calculate_site_model_derivatives(edges=False, **mx)                    # (the warm-up)
+    inst.get_kernel_timing(reset=True)
+    first_ms, model_ms, rates_ms = [], [], []
+    for i in range(repeats):
+        t0 = time.perf_counter()
+        rc, _, sums, _ = inst.calculate_edge_gradient(sites=False, **ix)
+        t1 = time.perf_counter()
+        rc2, _, rates, counts, root = inst.calculate_site_model_derivatives(edges=False, **mx)
+        t2 = time.perf_counter()
+        rc3, _, rates1, _, _ = inst.calculate_site_model_derivatives(edges=False, counts=False, root=False, **mx)
+        t3 = time.perf_counter()
+        first_ms.append((t1 - t0) * 1e3)
+        model_ms.append((t2 - t1) * 1e3)
+        rates_ms.append((t3 - t2) * 1e3)
+    _, launches = inst.get_kernel_timing(reset=True)
+    assert rc == 0 and rc2 == 0 and rc3 == 0 and np.array_equal(rates, expect) and np.array_equal(rates1, expect)
+    first, model, rates_only = (float(np.median(v)) for v in (first_ms, model_ms, rates_ms))
+    print("%s: site-model derivatives of %d branches x %d categories (rates, counts, root frequencies): %.3f ms a call (%.3f ... %.3f; byte "
+          "model %.3f ms: %.0f %%), the rates alone %.3f ms (%.3f ... %.3f), against the first-derivative call alternating with them %.3f ms "
+          "(%.3f ... %.3f): %.2f x and %.2f x; %d launches a round of the three; sum of the counts %.6f, sum pi F %.6f against %.6f sites" %
+          (case, len(nodes), div.ncat, model, min(model_ms), max(model_ms), model_read, 100.0 * model_read / model, rates_only, min(rates_ms),
+           max(rates_ms), first, min(first_ms), max(first_ms), model / first, rates_only / first, launches // repeats, float(counts.sum()),
+           float(np.asarray(div.pi, dtype=np.float64) @ root), float(np.asarray(div.weights, dtype=np.float64).sum())))
 finally:
     bd.finalize()
