@@ -401,6 +401,54 @@ BEAGLE_DLLEXPORT int mbamdCalculateEdgeSecondDerivatives(int instance, const int
  * states in single precision unless MBAMD_CURV_GENERIC is set); one per chunk of edges */
 BEAGLE_DLLEXPORT int mbamdGetSecondDerivativeLaunches(int instance, long* out2);
 
+/* Regraft and placement scores (an engine extension: upstream has no such call): what the log-likelihood WOULD be with a subtree
+ * attached at each of `count` points of the tree, from one read of the buffers the gradient call reads -- every regraft position
+ * of a pruned clade, or every placement of a query sequence on a fixed tree, in one call.  Entry e = 0 .. count-1 names
+ *     preBufferIndices[e]       the pre-order buffer AT the insertion point (beagleUpdatePrePartials wrote it)
+ *     postBufferIndices[e]      post-order partials or compact tip states of the node below the point
+ *     postMatrixIndices[e]      the matrix from the point down to that node; BEAGLE_OP_NONE: the point IS the node
+ *     subtreeBufferIndices[e]   post-order partials or compact tip states of the clade / query to attach
+ *     subtreeMatrixIndices[e]   the matrix of the pendant branch
+ *     subtreeScaleIndices[e]    the cumulative scale buffer of the subtree, or BEAGLE_OP_NONE
+ * and for pattern c and category k, with a = pre[k,c,:],
+ *     b[m]   = post[k,c,m]                         (postMatrix NONE)    or   sum_j Pb_k[m,j] post[k,c,j]
+ *     s[m]   = sum_j Pc_k[m,j] sub[k,c,j]
+ *     den_k  = sum_m a[m] b[m]          num_k = sum_m a[m] b[m] s[m]
+ *     R_c    = sum_k q_k(c) (num_k / den_k) 2^{x_k(c)}
+ *     outSiteLogRatios[e * patternCount + c] = log R_c (unweighted),   outSumLogRatios[e] = sum_c weight_c log R_c;
+ * either output may be NULL.  q_k(c) are the posterior category probabilities of beagleCalculateEdgeDerivatives (1 with one
+ * category), from the latest log-likelihood call.  x_k(c) is the subtree's cumulative exponent -- what subtreeScaleIndices[e]
+ * holds for the pattern (and, where the implementation keeps one per category, for the category) -- plus the power of two the
+ * call takes out of the subtree's own column before its first product (exact; an unscaled column may lie anywhere down to the
+ * smallest subnormal).  log R_c is the log-likelihood of pattern c on the tree with the subtree attached minus that on the tree
+ * without it, to rounding: the powers of two `pre` and `post` carry per (pattern, category) cancel in num_k / den_k, the
+ * subtree's does not and comes out exactly.  A category whose den_k is not positive has underflowed and is skipped.  R_c = 0 --
+ * the attachment is impossible for that pattern -- gives -infinity there and in the sum; the call still succeeds.  A compact tip
+ * in `post` or `sub` is its indicator column; a missing state is the vector of ones (under a matrix: the factor 1) where the
+ * implementation stores state codes, the four-state bitplanes add the compatible columns.  An entry's result does not depend
+ * on the other entries of the list or on their order.
+ *   Insertion at the CHILD END of the branch above node n: pass pre(n), post(n) and postMatrix = BEAGLE_OP_NONE; nothing else
+ * is needed.  One call over all branches ranks every regraft position of a pruned clade: the tree without the clade is the one
+ * whose log-likelihood and pre-order list were just run.
+ *   Insertion ELSEWHERE on the branch: write the pre-order vector at that point with one ordinary pre-order operation into a
+ * scratch buffer -- the parent's pre-order buffer, the sibling, and as its own matrix the UPPER part of the branch (all
+ * candidates are independent: beagleUpdatePrePartials runs them in one launch) -- and pass the LOWER part of the branch as
+ * postMatrix.
+ *   Refusals, the same on both engines; a refused call writes nothing.  BEAGLE_ERROR_NO_IMPLEMENTATION: a multi-partition
+ * instance, or a latest log-likelihood call over several subsets.  BEAGLE_ERROR_GENERAL: more than one category and no
+ * log-likelihood call yet.  BEAGLE_ERROR_OUT_OF_RANGE: a weights index other than that call's, a pre index that no pre-order
+ * operation wrote (or that was overwritten since), a post or subtree buffer that holds nothing, a matrix or scale index out of
+ * range, a subtree matrix of BEAGLE_OP_NONE, NULL index arrays with count > 0, count < 0.  count == 0 succeeds; with both
+ * outputs NULL the call succeeds after the checks.  The call is synchronous. */
+BEAGLE_DLLEXPORT int mbamdCalculateInsertionLogLikelihoods(int instance, const int* preBufferIndices, const int* postBufferIndices,
+                                                           const int* postMatrixIndices, const int* subtreeBufferIndices,
+                                                           const int* subtreeMatrixIndices, const int* subtreeScaleIndices,
+                                                           const int* categoryWeightsIndices, int count, double* outSiteLogRatios,
+                                                           double* outSumLogRatios);
+/* its launches since the instance was created: out2[0] on the plain kernel, out2[1] on the matrix-core kernel (16 ... 64 states
+ * in single precision unless MBAMD_INSERT_GENERIC is set); one per chunk of entries */
+BEAGLE_DLLEXPORT int mbamdGetInsertionLaunches(int instance, long* out2);
+
 /* The gradient in the rate matrix (upstream's name and argument order): the S x S cross-product matrix a client contracts with
  * dQ / d theta.  Edge e = 0 .. count-1 names postBufferIndices[e] and preBufferIndices[e] exactly as
  * beagleCalculateEdgeDerivatives does (a post-order buffer may hold partials or compact tip states: a tip is its indicator

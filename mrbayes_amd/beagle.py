@@ -67,7 +67,7 @@ EXPORTS = [
     "beagleGetScaleFactors", "beagleCalculateRootLogLikelihoods", "beagleCalculateEdgeLogLikelihoods",
     "beagleGetSiteLogLikelihoods", "beagleGetSiteDerivatives", "beagleUpdatePrePartials", "beagleSetDifferentialMatrix",
     "beagleCalculateEdgeDerivatives", "beagleCalculateCrossProductDerivative", "mbamdCalculateSiteModelDerivatives", "mbamdCalculateEdgeSecondDerivatives",
-    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
+    "mbamdGetSecondDerivativeLaunches", "mbamdCalculateInsertionLogLikelihoods", "mbamdGetInsertionLaunches", "mbamdCalculateNodePosteriors", "mbamdGetCategoryPosteriors", "mbamdSampleAncestralStates", "mbamdCalculateAutocorrelatedLogLikelihood", "mbamdSynchronize", "mbamdGetLastError", "mbamdKernelTiming",
     "mbamdGetKernelTiming", "mbamdGetListCounts", "mbamdGetWalkCounts", "mbamdGetRangeSafeCounts", "mbamdGetPlainWaveCounts", "mbamdGetRecomputeCounts", "mbamdGetSubtreeRecomputeCounts", "mbamdGetStepTiming", "mbamdUpdateFinalPartials", "mbamdGetScaledPartials", "mbamdSetKernelPath", "mbamdSetDeferredResult", "mbamdFetchLogLikelihood", "mbamdReduceLogLikelihood", "mbamdGetResourcePciBusId", "mbamdGetInstanceDevices",
     "mbamdGetScaleExponents", "mbamdGetChildCount", "mbamdSetRateMatrices", "mbamdSetRateMatricesFrom", "mbamdGetEigenDecomposition",
     "mbamdUpdateTransitionMatricesFromRateMatrix",
@@ -161,6 +161,8 @@ class BeagleLibrary:
         L.mbamdCalculateSiteModelDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _dp, C.c_int, _dp, _dp, _dp, _dp]
         L.mbamdCalculateEdgeSecondDerivatives.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp, _dp, _dp]
         L.mbamdGetSecondDerivativeLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
+        L.mbamdCalculateInsertionLogLikelihoods.argtypes = [C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.c_int, _dp, _dp]
+        L.mbamdGetInsertionLaunches.argtypes = [C.c_int, C.POINTER(C.c_long)]
         L.mbamdCalculateNodePosteriors.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, _dp, _ip, _dp, _dp]
         L.mbamdGetCategoryPosteriors.argtypes = [C.c_int, C.c_int, _dp]
         L.mbamdSampleAncestralStates.argtypes = [C.c_int, _ip, _ip, _ip, C.c_int, C.c_int, C.c_ulonglong, _ip, _ip, _dp]
@@ -498,6 +500,30 @@ class BeagleInstance:
         """(read-out launches of calculate_edge_second_derivatives on the plain kernel, on the matrix-core kernel)"""
         out = (C.c_long * 2)()
         self._chk(self.lib.mbamdGetSecondDerivativeLaunches(self.id, out), "mbamdGetSecondDerivativeLaunches")
+        return tuple(int(v) for v in out)
+
+    def calculate_insertion_log_likelihoods(self, pres, posts, post_matrices, subtrees, subtree_matrices, subtree_scales, weights, sites=True):
+        """The log-likelihood with a subtree attached at every listed point, minus that of the tree without it, in one call
+        (mbamdCalculateInsertionLogLikelihoods): pres[e] the pre-order buffer at the point, posts[e] the node below it,
+        post_matrices[e] the matrix from the point down to that node (BEAGLE_OP_NONE: the point is the node), subtrees[e] /
+        subtree_matrices[e] / subtree_scales[e] the clade to attach, its pendant matrix and its cumulative scale buffer (or
+        BEAGLE_OP_NONE).  Returns (rc, per-site log ratios [count][patterns] or None without `sites`, sums [count]); -inf where the
+        attachment is impossible; an error code raises."""
+        arrays = [_i(v) for v in (pres, posts, post_matrices, subtrees, subtree_matrices, subtree_scales, weights)]
+        n = len(arrays[0])
+        if any(len(v) != n for v in arrays):
+            raise ValueError("calculate_insertion_log_likelihoods: the index lists differ in length")
+        per = np.empty((n, self.pattern_count)) if sites else None
+        sums = np.zeros(n)
+        rc = self.lib.mbamdCalculateInsertionLogLikelihoods(self.id, *[v.ctypes.data_as(_ip) for v in arrays], n,
+                                                            per.ctypes.data_as(_dp) if sites else None, sums.ctypes.data_as(_dp))
+        self._chk(rc, "mbamdCalculateInsertionLogLikelihoods")
+        return rc, per, sums
+
+    def get_insertion_launches(self):
+        """(launches of calculate_insertion_log_likelihoods on the plain kernel, on the matrix-core kernel)"""
+        out = (C.c_long * 2)()
+        self._chk(self.lib.mbamdGetInsertionLaunches(self.id, out), "mbamdGetInsertionLaunches")
         return tuple(int(v) for v in out)
 
     def calculate_node_posteriors(self, posts, pres, weights, sites=True, best=False):

@@ -1146,6 +1146,44 @@ int mbamdCalculateNodePosteriors(int instance, const int* postBufferIndices, con
     std::copy(sum.begin(), sum.end(), outSumPosteriors);
     return BEAGLE_SUCCESS;
 }
+// the log-likelihood with a subtree attached at every listed point (mbamd_insertions.h; semantics: beagle.h)
+int mbamdCalculateInsertionLogLikelihoods(int instance, const int* preBufferIndices, const int* postBufferIndices, const int* postMatrixIndices,
+                                          const int* subtreeBufferIndices, const int* subtreeMatrixIndices, const int* subtreeScaleIndices,
+                                          const int* categoryWeightsIndices, int count, double* outSiteLogRatios, double* outSumLogRatios)
+{
+    StatTimer st_(ST_LNL);
+    GET_INSTANCE(instance);
+    API_TRACE("mbamdCalculateInsertionLogLikelihoods(count=%d%s)", count, outSiteLogRatios ? ", per site" : "");
+    const char* const who = "mbamdCalculateInsertionLogLikelihoods";
+    if (h->partitionCount > 1) return fail(BEAGLE_ERROR_NO_IMPLEMENTATION, who, "not on a multi-partition instance");
+    if (count < 0 || (count > 0 && (!preBufferIndices || !postBufferIndices || !postMatrixIndices || !subtreeBufferIndices || !subtreeMatrixIndices ||
+                                    !subtreeScaleIndices || !categoryWeightsIndices)))
+        return fail(BEAGLE_ERROR_OUT_OF_RANGE, who, "null index array");
+    if (h->f64)
+        return h->f64->insertionLogLikelihoods(preBufferIndices, postBufferIndices, postMatrixIndices, subtreeBufferIndices, subtreeMatrixIndices,
+                                               subtreeScaleIndices, categoryWeightsIndices, count, outSiteLogRatios, outSumLogRatios);
+    // pattern shards: every child answers for its own patterns; the sums are added in child order, the site rows gathered
+    const size_t stride = (size_t) h->dim.patternCount;
+    const bool any = outSiteLogRatios || outSumLogRatios;
+    std::vector<double> sum;
+    const int rc = each_engine_sum(h, (size_t) std::max(count, 0), sum, [&](Instance* c, const Handle::Span& ch, double* part) {
+        return c->insertionLogLikelihoods(preBufferIndices, postBufferIndices, postMatrixIndices, subtreeBufferIndices, subtreeMatrixIndices,
+                                          subtreeScaleIndices, categoryWeightsIndices, count, outSiteLogRatios ? outSiteLogRatios + ch.start : nullptr,
+                                          stride, any ? part : nullptr);
+    });
+    if (rc) return rc;
+    if (outSumLogRatios) std::copy(sum.begin(), sum.end(), outSumLogRatios);
+    return BEAGLE_SUCCESS;
+}
+// its launches so far: out2[0] of the plain form, out2[1] of the matrix-core form (children: the sums over them)
+int mbamdGetInsertionLaunches(int instance, long* out2)
+{
+    GET_INSTANCE_NOFLUSH(instance);
+    if (!out2) return fail(BEAGLE_ERROR_OUT_OF_RANGE, "mbamdGetInsertionLaunches: null output");
+    out2[0] = out2[1] = 0;
+    if (h->f64) { h->f64->insertionLaunchCounts(out2); return BEAGLE_SUCCESS; }
+    EACH_ENGINE(false, (c->insertionLaunchCounts(out2), BEAGLE_SUCCESS));
+}
 int mbamdGetCategoryPosteriors(int instance, int categoryWeightsIndex, double* outPosteriors)
 {
     GET_INSTANCE(instance);

@@ -30,6 +30,7 @@
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products, k_cross_products_mfma: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors: node-state and category posteriors from the pre-order buffers
+#include "mbamd_insertions.h"    // k_insertion_readout: the log-likelihood with a subtree attached at every listed point
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges: a draw of all ancestral states from their joint posterior
 #include "mbamd_site_model.h"    // k_edge_category_readout, k_root_frequency_readout: the gradient in category rates, weights and root frequencies
 #include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
@@ -111,6 +112,11 @@ struct Instance {
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues,
                        size_t siteStride, double* sums);
     int categoryPosteriors(int wIdx, double* out, size_t stride);
+    // insertionLogLikelihoods (mbamdCalculateInsertionLogLikelihoods on this engine's patterns; mbamd_insertions.h): synchronous;
+    // sums[i] (or null), per-pattern log ratios (or null) at [i * siteStride + c]
+    int insertionLogLikelihoods(const int* pre, const int* post, const int* postM, const int* sub, const int* subM, const int* subScale,
+                                const int* wIdx, int count, double* sites, size_t siteStride, double* sums);
+    void insertionLaunchCounts(long out2[2]) const { out2[0] += insertionLaunches[0]; out2[1] += insertionLaunches[1]; }   // its launches: plain / matrix-core form
     // siteModelDerivatives (mbamdCalculateSiteModelDerivatives on this engine's patterns; mbamd_site_model.h): synchronous; edgeCat
     // [count][K], counts [K], rootFreq [S], each or null
     int siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat, double* counts,
@@ -311,6 +317,7 @@ private:
     template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
+    template <class E> friend int insertion_log_likelihoods(E&, const int*, const int*, const int*, const int*, const int*, const int*, const int*, int, double*, size_t, double*);
     template <class E> friend int site_model_derivatives(E&, const int*, const int*, const int*, const int*, int, double*, double*, double*);
     template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
     template <class E> friend int autocorrelated_prepare(E&, int, HmmSource&);
@@ -396,6 +403,9 @@ private:
     }
     const HostMirror& weightsMirror() const { return h_weights; }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
+    long insertionLaunches[2] = {0, 0};   // launches of insertion_log_likelihoods: plain / matrix-core form
+    // the cumulative exponents of a scale buffer as a kernel reads them ([K][Ppad] on the arena layouts, [Ppad] otherwise; null: all zero)
+    int cumulativeExponents(int idx, const int32_t*& out) { return scales.cumulativeForRead(idx, out); }
     int posteriorOperands(DerivArgs& a);
     RateSets rateSets;                // category rates by index (beagleSetCategoryRatesWithIndex; index 0 = beagleSetCategoryRates), passed to kernels by value
     int pendingRateSet = 0;           // the rate set of the queued transition-matrix jobs
@@ -1560,6 +1570,11 @@ inline int Instance::nodePosteriors(const int* post, const int* pre, const int* 
     return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, siteStride, sums);
 }
 inline int Instance::categoryPosteriors(int wIdx, double* out, size_t stride) { return category_posteriors(*this, wIdx, out, stride); }
+inline int Instance::insertionLogLikelihoods(const int* pre, const int* post, const int* postM, const int* sub, const int* subM, const int* subScale,
+                                             const int* wIdx, int count, double* sites, size_t siteStride, double* sums)
+{
+    return insertion_log_likelihoods(*this, pre, post, postM, sub, subM, subScale, wIdx, count, sites, siteStride, sums);
+}
 inline int Instance::siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat,
                                           double* counts, double* rootFreq)
 {

@@ -31,6 +31,7 @@
 #include "mbamd_preorder.h"      // k_pre_partials, k_edge_readout <DERIV_F64, double, 1 and 2>: the pre-order pass and the gradient in all branch lengths
 #include "mbamd_crossproducts.h" // k_cross_products <DERIV_F64, double>: the cross-product matrix of the gradient in the rate matrix
 #include "mbamd_posteriors.h"    // k_node_posteriors <DERIV_F64, double>: node-state and category posteriors from the pre-order buffers
+#include "mbamd_insertions.h"    // k_insertion_readout <DERIV_F64, double, 0>: the log-likelihood with a subtree attached at every listed point
 #include "mbamd_ancestral_sampling.h"   // k_sample_top, k_sample_edges <DERIV_F64, double>: a draw of all ancestral states from their joint posterior
 #include "mbamd_site_model.h"    // k_edge_category_readout, k_root_frequency_readout <DERIV_F64, double>: the gradient in category rates, weights and root frequencies
 #include "mbamd_autocorrelated.h"  // k_hmm_products, k_hmm_vectors, k_hmm_posteriors: the site-order HMM over the rate categories
@@ -101,6 +102,10 @@ public:
     // node-state and category posteriors (mbamd_posteriors.h), as on the single-precision engine: synchronous
     int nodePosteriors(const int* post, const int* pre, const int* wIdx, int count, double* sites, int* bestStates, double* bestValues, double* sums);
     int categoryPosteriors(int wIdx, double* out);
+    // insertion log-likelihoods (mbamd_insertions.h), as on the single-precision engine: synchronous
+    int insertionLogLikelihoods(const int* pre, const int* post, const int* postM, const int* sub, const int* subM, const int* subScale,
+                                const int* wIdx, int count, double* sites, double* sums);
+    void insertionLaunchCounts(long out2[2]) const { out2[0] += insertionLaunches[0]; out2[1] += insertionLaunches[1]; }   // its launches: plain / matrix-core form (none here)
     // the gradient in the site model (mbamd_site_model.h), as on the single-precision engine: synchronous
     int siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat, double* counts,
                              double* rootFreq);
@@ -188,6 +193,7 @@ private:
     template <class E> friend int edge_readout(E&, const int*, const int*, const int*, const int*, const int*, int, double*, double*, size_t, double*, double*);
     template <class E, class L, class S> friend int chunked_readout(E&, int, const ReadoutShape&, L&&, S&&);
     template <class E> friend int node_posteriors(E&, const int*, const int*, const int*, int, double*, int*, double*, size_t, double*);
+    template <class E> friend int insertion_log_likelihoods(E&, const int*, const int*, const int*, const int*, const int*, const int*, const int*, int, double*, size_t, double*);
     template <class E> friend int category_posteriors(E&, int, double*, size_t);
     template <class E> friend int site_model_derivatives(E&, const int*, const int*, const int*, const int*, int, double*, double*, double*);
     template <class E> friend int sample_ancestral_states(E&, const int*, const int*, const int*, int, int, unsigned long long, long long, int*, int*, double*, size_t);
@@ -245,6 +251,9 @@ private:
     }
     const HostMirror& weightsMirror() const { return hostWeights; }
     long secondLaunches[2] = {0, 0};  // order-2 read-out launches of edge_readout: plain / matrix-core kernel
+    long insertionLaunches[2] = {0, 0};   // launches of insertion_log_likelihoods: plain / matrix-core form
+    // the cumulative exponents of a scale buffer as a kernel reads them: [Ppad]
+    int cumulativeExponents(int idx, const int32_t*& out) { out = d_scale + (size_t) idx * Ppad; return BEAGLE_SUCCESS; }
     // f(this engine's layout as a compile-time constant)
     template <class F> auto withLayout(F&& f) const { return f(std::integral_constant<int, DERIV_F64>()); }
     int posteriorOperands(DerivArgs& a);
@@ -1359,6 +1368,11 @@ inline int Engine64::nodePosteriors(const int* post, const int* pre, const int* 
     return node_posteriors(*this, post, pre, wIdx, count, sites, bestStates, bestValues, (size_t) P, sums);
 }
 inline int Engine64::categoryPosteriors(int wIdx, double* out) { return category_posteriors(*this, wIdx, out, (size_t) P); }
+inline int Engine64::insertionLogLikelihoods(const int* pre, const int* post, const int* postM, const int* sub, const int* subM, const int* subScale,
+                                             const int* wIdx, int count, double* sites, double* sums)
+{
+    return insertion_log_likelihoods(*this, pre, post, postM, sub, subM, subScale, wIdx, count, sites, (size_t) P, sums);
+}
 inline int Engine64::siteModelDerivatives(const int* post, const int* pre, const int* dmat, const int* wIdx, int count, double* edgeCat,
                                           double* counts, double* rootFreq)
 {

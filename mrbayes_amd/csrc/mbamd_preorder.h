@@ -468,7 +468,7 @@ k_edge_second_mfma(ReadoutArgs a)
 
 // ---- host side, shared by the two engines ----------------------------------------------------------------------------------------
 // The calls are written once, as templates on the engine (Instance, Engine64).  They read its members of the same name -- the sizes
-// S, K, P, Ppad, nBuffers, nMatrices, stream, valid, preOrder, lastLnl, qStamp, d_q, d_pweights, rateSets, sw, secondLaunches, layoutArgs(),
+// S, K, P, Ppad, nBuffers, nMatrices, nScale, stream, valid, preOrder, lastLnl, qStamp, d_q, d_pweights, rateSets, sw, secondLaunches, insertionLaunches, layoutArgs(),
 // partialsPtr(), matrixPtr() -- and ask it for the rest through a few small hooks, which each engine keeps in one block:
 //     runQueued, refuses                  before anything else: what is queued or held runs; an instance the calls do not serve
 //     holdsTip, readable, operandPtr      a buffer holds compact tip states / something to read; where that is
@@ -478,6 +478,7 @@ k_edge_second_mfma(ReadoutArgs a)
 //     timedBegin, timedEnd                an event pair around a call's launches while kernel timing is on (the sampling call)
 //     withLayout                          f(layout as a compile-time constant)
 //     posteriorOperands                   the checked operands of the latest log-likelihood call
+//     cumulativeExponents                 a scale buffer's cumulative exponents as a kernel reads them (the insertion call of mbamd_insertions.h)
 //     siteLogLikelihoods, weightsMirror   its site log-likelihoods where a kernel can read them; the host copy of the category weights
 //                                         (the site-order HMM of mbamd_autocorrelated.h)
 

@@ -46,7 +46,8 @@ struct Switches {
     bool eigen256 = false;                 // MBAMD_EIGEN_256: the device eigen-solver on 256 threads at every state count
     bool xprodGeneric = false;             // MBAMD_XPROD_GENERIC: cross products of 16 ... 64 states on the plain kernel instead of the matrix-core one
     bool curvGeneric = false;              // MBAMD_CURV_GENERIC: second derivatives of 16 ... 64 states on the plain kernel instead of the matrix-core one
-    std::optional<int> posteriorNodes;     // MBAMD_POSTERIOR_NODES=<n>: at most n nodes per launch of mbamdCalculateNodePosteriors, or edges of mbamdCalculateSiteModelDerivatives (test only: a chunk boundary at a small shape)
+    bool insertGeneric = false;            // MBAMD_INSERT_GENERIC: insertion log-likelihoods of 16 ... 64 states on the plain kernel instead of the matrix-core one
+    std::optional<int> posteriorNodes;     // MBAMD_POSTERIOR_NODES=<n>: at most n nodes per launch of mbamdCalculateNodePosteriors, or edges of mbamdCalculateSiteModelDerivatives, or entries of mbamdCalculateInsertionLogLikelihoods (test only: a chunk boundary at a small shape)
     std::optional<int> samplePatterns;     // MBAMD_SAMPLE_PATTERNS=<n>: at most n patterns in flight in mbamdSampleAncestralStates (test only: several pattern ranges at a small shape)
     // ---- A/B references used by tests: the parsimony scorer
     std::optional<int> parsPhaseLimit;     // MBAMD_PARS_PHASE_LIMIT=<n>: phases per launch of the parsimony walk
@@ -81,7 +82,8 @@ inline Switches read_switches()
     s.walkWaves = num("MBAMD_WALK_WAVES"); s.maxLdsSlots = num("MBAMD_MAX_LDS_SLOTS"); s.walkSmallPhase = num("MBAMD_WALK_SMALL_PHASE");
     s.walkPlainMinOps = num("MBAMD_WALK_PLAIN_MIN_OPS");
     s.walkPrefetch = num("MBAMD_WALK_PREFETCH"); s.walkSafe = on("MBAMD_WALK_SAFE"); s.eigen256 = on("MBAMD_EIGEN_256");
-    s.xprodGeneric = on("MBAMD_XPROD_GENERIC"); s.curvGeneric = on("MBAMD_CURV_GENERIC"); s.posteriorNodes = num("MBAMD_POSTERIOR_NODES");
+    s.xprodGeneric = on("MBAMD_XPROD_GENERIC"); s.curvGeneric = on("MBAMD_CURV_GENERIC"); s.insertGeneric = on("MBAMD_INSERT_GENERIC");
+    s.posteriorNodes = num("MBAMD_POSTERIOR_NODES");
     s.samplePatterns = num("MBAMD_SAMPLE_PATTERNS");
     s.parsPhaseLimit = num("MBAMD_PARS_PHASE_LIMIT"); s.parsWaves = num("MBAMD_PARS_WAVES");
     s.f64NoWalk = on("MBAMD_F64_NO_WALK"); s.f64WalkAlways = on("MBAMD_F64_WALK_ALWAYS"); s.f64WalkSlots = num("MBAMD_F64_WALK_SLOTS");

@@ -40,11 +40,12 @@ class BeagleDivision:
 
     def __init__(self, div: Division, lib: Optional[bg.BeagleLibrary] = None, nchains: int = 1,
                  scaling: int = MB_BEAGLE_SCALE_ALWAYS, resource: Optional[int] = None, device_eigen: bool = False,
-                 double_precision: bool = False, pre_order: bool = False, second_order: bool = False):
+                 double_precision: bool = False, pre_order: bool = False, second_order: bool = False, spare: int = 0):
         self.div = div
         pre_order = pre_order or second_order
         self.pre_order = pre_order                      # reserve the buffers of BranchGradient (behind every existing one)
         self.second_order = second_order                # ... and the second differential matrix of BranchCurvature (behind those)
+        self.spare = int(spare)
         self.double_precision = double_precision        # `set beagleprecision=double` (src/command.c:6765-6766): a preference flag
         self.device_eigen = device_eigen and div.rate_matrices is not None and bool(np.all(np.asarray(div.pi) > 0))
         self.lib = lib or bg.library()
@@ -121,9 +122,15 @@ class BeagleDivision:
         req = bg.BEAGLE_FLAG_SCALERS_LOG if self.scaling == MB_BEAGLE_SCALE_ALWAYS else 0   # src/mbbeagle.c:191-194
         if d.complex_eigen:                                               # a non-reversible model: eigenvalues in conjugate pairs
             req |= bg.BEAGLE_FLAG_EIGEN_COMPLEX
+        # `spare` partials, matrix and scale buffers of each kind behind every other one (spareBufferIndex, spareMatrixIndex,
+        # spareScalerIndex: scratch for a client's own operations, as InsertionLogLikelihoods' subtree); 0: none
+        self.spareBufferIndex = (self.numCondLikes + self.numPreOrder) * self.step
+        self.spareMatrixIndex = (self.numTiProbs + self.numDiffMatrices) * self.step
+        self.spareScalerIndex = self.numScalers * self.step
         self.inst = bg.BeagleInstance(
-            self.lib, self.N, (self.numCondLikes + self.numPreOrder) * self.step, self.N - num_part_ambig, d.nstates, d.npatterns,
-            (self.nchains + 1) * self.step, (self.numTiProbs + self.numDiffMatrices) * self.step, d.ncat, self.numScalers * self.step,
+            self.lib, self.N, (self.numCondLikes + self.numPreOrder) * self.step + self.spare, self.N - num_part_ambig, d.nstates, d.npatterns,
+            (self.nchains + 1) * self.step, (self.numTiProbs + self.numDiffMatrices) * self.step + self.spare, d.ncat,
+            self.numScalers * self.step + self.spare,
             resource=resource, requirement_flags=req,
             preference_flags=bg.BEAGLE_FLAG_PRECISION_DOUBLE if self.double_precision else bg.BEAGLE_FLAG_PRECISION_SINGLE)
         for i in range(self.N):                                           # src/mbbeagle.c:123-167
@@ -538,6 +545,23 @@ class BeagleDivision:
         if best:
             out.append({n: (states[i], values[i]) for i, n in enumerate(nodes)})
         return out[0] if len(out) == 1 else tuple(out)
+
+    def InsertionLogLikelihoods(self, chain=0, subtree=None, subtree_matrix=None, subtree_scale=None, sites=False):
+        """{node: lnL(the chain's current tree with the subtree attached at the child end of node's branch) - lnL(the tree)} for all
+        2N-3 branches, after LogLike: the pre-order pass of BranchGradient, then ONE calculate_insertion_log_likelihoods call.
+        subtree: a partials buffer (or a buffer of compact tip states) that holds the clade or the query, subtree_matrix the matrix
+        buffer of the pendant branch, subtree_scale the subtree's cumulative scale buffer (None: unscaled).  sites=True: (that,
+        {node: per-site log ratios [patterns]})."""
+        if subtree is None or subtree_matrix is None:
+            raise ValueError("InsertionLogLikelihoods: subtree and subtree_matrix are required")
+        self._PreOrderPass(chain, "InsertionLogLikelihoods")
+        nodes = list(self.div.tree.all_down_pass)
+        n = len(nodes)
+        rc, per, sums = self.inst.calculate_insertion_log_likelihoods(
+            self._EdgePres(nodes), self._EdgePosts(chain, nodes), [bg.BEAGLE_OP_NONE] * n, [subtree] * n, [subtree_matrix] * n,
+            [bg.BEAGLE_OP_NONE if subtree_scale is None else subtree_scale] * n, [self.cijkIndex[chain]] * n, sites=sites)
+        score = {node: float(sums[i]) for i, node in enumerate(nodes)}
+        return (score, {node: per[i] for i, node in enumerate(nodes)}) if sites else score
 
     def CategoryPosteriors(self, chain=0):
         """q [categories][patterns], the posterior category probabilities of the chain's latest LogLike: site rates are
